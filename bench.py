@@ -3,7 +3,7 @@
 1e6-Gaussian 1080p scene (surfel rasterizer — the one gaussian_renderer calls — + fused deferred reflection / cubemap lookup,
 then their backward with synthetic upstream gradients).
 
-    python bench.py --gpus N --steps K --warmup W [--views V]
+    python bench.py --gpus N --steps K --warmup W [--views V] [--dump-outputs DIR]
 
 N = 1 (default): BASELINE config C3 — ONE view per step, no collective.
 N > 1 (launched by torch.distributed.run, one rank per GPU): BASELINE config C4 — a batch of V = 8 views per step sharded over
@@ -151,9 +151,17 @@ def main():
                          "rasterize + reflect path (the reflection's pixel code inside the tile kernels)")
     ap.add_argument("--sharded-adam", action="store_true",
                     help="N > 1, full_train_step: reduce-scatter -> Adam on this rank's 1/N of the flat buffer -> all-gather instead of all-reduce -> full Adam")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: its views' rasterizer + reflection outputs and "
+                         "the reduced parameter gradients) to DIR/<name>.npy, float32; arrays above a fixed size as a fixed, seeded sample of "
+                         "their elements (dump_outputs below).  Same arguments, same inputs: two builds compare output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
+    if args.only_c5 and args.dump_outputs is not None:
+        raise SystemExit("bench: --dump-outputs writes the headline step's outputs; --only-c5 does not run it")
 
     # ---- launcher.  `python bench.py --gpus N` with N > 1 and no torchrun environment starts its N ranks itself, BEFORE this process
     # makes any GPU call (fresh children through `python -m torch.distributed.run`; a process that has initialised the GPU is never
@@ -216,6 +224,8 @@ def main():
     g_allmap = torch.from_numpy(g["dL_dplanes"]).to(dev)
     means2D = scene.means2D
     info = {}
+    # --dump-outputs: the outputs of every view of the last timed step, kept by render() while `on` is set (that step only)
+    captured = {"on": False, "views": []}
 
     def render(view, refl_sink, accumulate, sc=None):
         sc = sc or scene
@@ -236,6 +246,9 @@ def main():
                                                                                          async_tail=async_tail, **kw)
         if base.grad_fn is not None:
             info["R"] = base.grad_fn.num_rendered
+        if captured["on"]:
+            captured["views"].append({"final": final, "refl_color": refl_color, "rend_normal": nrm, "base_color": base, "radii": radii,
+                                      "allmap": allmap, "refl_strength_map": refl_map, "gaussian_weights": gw})
         return final, allmap
 
     # The backward kernels write their parameter gradients straight into the flat all-reduce buffer (gradient sinks): the first
@@ -313,11 +326,25 @@ def main():
     t0 = time.perf_counter()
     host_t[0] = t0
     for i in range(args.steps):
+        captured["on"] = args.dump_outputs is not None and i == args.steps - 1
         step()
         host_t[i + 1] = time.perf_counter()
     sync_all()
     dt = time.perf_counter() - t0
     pygc.callbacks.remove(on_gc)
+    captured["on"] = False
+    if args.dump_outputs is not None and rank == 0:
+        # before the instrumented pass below overwrites the gradient buffer
+        arrays = {}
+        for v, outs in zip(my_views, captured["views"]):
+            for k, x in outs.items():
+                arrays[k if len(views) == 1 else "view%d_%s" % (v, k)] = x
+        for k, x in scene.p.items():
+            arrays["grad_" + k] = x.grad
+        if means2D.grad is not None:
+            arrays["grad_means2D"] = means2D.grad      # (the last view's: the step resets it before every view)
+        dump_outputs(args.dump_outputs, arrays)
+    captured["views"] = []
     host_step_ms = [(host_t[i + 1] - host_t[i]) * 1e3 for i in range(args.steps)]
     # the same K steps again, instrumented: one event per step (percentiles) and the library's per-stage hipEvent timers
     _gsr.profile_enable(True)
@@ -582,7 +609,7 @@ def main():
             out["full_train_step"] = full
         if not args.no_c5 and world == 1:
             torch.cuda.empty_cache()
-            out["c5"] = c5_object(S, dev, settle_steps=args.settle_steps // 2)
+            out["c5"] = c5_object(S, dev, steps=args.steps, settle_steps=args.settle_steps // 2)
         if not args.no_dropin and world == 1:
             torch.cuda.empty_cache()
             out["dropin"] = dropin_object(args, S, dev)
@@ -597,6 +624,32 @@ def main():
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+DUMP_MAX_ELEMENTS = 2 ** 19
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array to out_dir/<name>.npy as float32 (integer outputs such as radii are exact in it).  An array of more than
+    DUMP_MAX_ELEMENTS elements (fewer when there are many arrays: all files together stay under 64 MiB) is written as the elements at a
+    fixed sample of flat indices, drawn without replacement by a generator seeded from the array's name and size and kept in ascending
+    order, so that the same arguments select the same elements on every run and every build."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    cap = min(DUMP_MAX_ELEMENTS, DUMP_BUDGET_BYTES // 4 // max(1, len(arrays)))
+    total = 0
+    for name, x in arrays.items():
+        flat = x.detach().reshape(-1)
+        if flat.numel() > cap:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), flat.numel()])
+            idx = np.sort(rng.choice(flat.numel(), size=cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET_BYTES, total
+    print("bench: %d arrays (%.1f MB) written to %s" % (len(arrays), total / 1e6, out_dir), file=sys.stderr, flush=True)
 
 
 def launch_ranks(n):

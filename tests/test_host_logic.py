@@ -133,3 +133,25 @@ def test_bench_refuses_a_world_size_that_differs_from_gpus():
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=300)
     assert p.returncode == 2 and "--gpus 4" in p.stderr and "WORLD_SIZE=2" in p.stderr and not p.stdout.strip()
+
+
+def test_bench_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """bench.py --dump-outputs: float32 files under the 64 MiB budget; small arrays whole, large ones as the same seeded sample of elements on
+    every call (two builds of the project compare output for output)."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"final": torch.rand(3, 540, 960, generator=g), "radii": torch.randint(0, 300, (1_000_000,), dtype=torch.int32, generator=g),
+              "grad_fail": torch.randn(3, generator=g)}
+    arrays.update({"big%d" % i: torch.rand(4_000_000, generator=g) for i in range(40)})
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), arrays)
+    bench.dump_outputs(str(b), arrays)
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(k + ".npy" for k in arrays)
+    assert sum((a / n).stat().st_size for n in names) <= 64 * 2 ** 20
+    for n in names:
+        x = np.load(a / n)
+        assert x.dtype == np.float32 and x.ndim == 1 and np.array_equal(x, np.load(b / n))
+    assert np.array_equal(np.load(a / "grad_fail.npy"), arrays["grad_fail"].numpy())
+    r = np.load(a / "radii.npy")
+    assert 0 < r.size < 1_000_000 and np.isin(r, arrays["radii"].numpy().astype(np.float32)).all()
