@@ -41,7 +41,7 @@ class ReflForward(ctypes.Structure):
                 ("scratch", c_void_p), ("scratch_floats", c_size_t), ("async_sort", c_int)]
 
 
-GSR_ABI_VERSION = 101      # GSR_ABI_VERSION of include/gsr_hip.h this binding was written against
+GSR_ABI_VERSION = 102      # GSR_ABI_VERSION of include/gsr_hip.h this binding was written against
 
 
 def _load():
@@ -70,6 +70,9 @@ def _load():
     lib.gsr_surfel_backward_ex.argtypes = lib.gsr_surfel_backward.argtypes[:-2] + [c_int, P, c_int, P]
     lib.gsr_surfel_forward_refl.restype = c_int
     lib.gsr_surfel_forward_refl.argtypes = lib.gsr_surfel_forward.argtypes[:-2] + [ctypes.POINTER(ReflForward), c_int, P]
+    lib.gsr_surfel_forward_eval.restype = c_int
+    lib.gsr_surfel_forward_eval.argtypes = [ALLOC_FN, P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, c_float, P, P, P, P, P,
+                                            c_float, c_float, c_int, P, P, P, P, P, ctypes.POINTER(ReflForward), c_int, P]
     lib.gsr_gauss_forward.restype = c_int
     lib.gsr_gauss_forward.argtypes = [ALLOC_FN, P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, P, c_float, P, P, P, P, P,
                                       c_float, c_float, c_int, P, P, P, P, c_int, P, c_int, P]
@@ -175,7 +178,7 @@ def compiled_binding():
 PYBIND = compiled_binding()
 
 EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_backward", "gsr_surfel_backward_accum", "gsr_surfel_backward_ex",
-            "gsr_surfel_forward_refl", "gsr_deferred_reflection_backward_keys", "gsr_deferred_reflection_forward_keys",
+            "gsr_surfel_forward_refl", "gsr_surfel_forward_eval", "gsr_deferred_reflection_backward_keys", "gsr_deferred_reflection_forward_keys",
             "gsr_deferred_reflection_backward_accum", "gsr_deferred_reflection_backward_ex", "gsr_deferred_reflection_forward_ex", "gsr_side_join", "gsr_normal_world_forward", "gsr_normal_world_backward", "gsr_gauss_forward", "gsr_gauss_backward", "gsr_gauss_backward_accum",
             "gsr_mark_visible", "gsr_debug_fetch", "gsr_cubemap_forward", "gsr_cubemap_backward", "gsr_deferred_reflection_forward",
             "gsr_deferred_reflection_scratch_floats", "gsr_deferred_reflection_backward", "gsr_ssim_l1_scratch_floats", "gsr_ssim_l1_forward", "gsr_ssim_l1_backward", "gsr_normal_loss_scratch_floats", "gsr_normal_loss_forward", "gsr_normal_loss_backward", "gsr_adam_step", "gsr_adam_step_range", "gsr_densification_stats", "gsr_gather_rows", "gsr_split_children", "gsr_surface_forward", "gsr_surface_backward", "gsr_profile_enable",

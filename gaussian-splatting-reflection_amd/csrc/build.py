@@ -9,6 +9,7 @@ the tree to the GPU box.
 import concurrent.futures
 import hashlib
 import os
+import re
 import subprocess
 import sys
 
@@ -17,7 +18,24 @@ PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libgsr_hip.so")
 OBJ_DIR = os.path.join(HERE, "_obj")
 SOURCES = ["gsr_common.hip", "gsr_gauss.hip", "gsr_surfel.hip", "gsr_cubemap.hip", "gsr_train.hip", "gsr_surface.hip", "gsr_densify.hip"]
-HEADERS = ["gsr_internal.hpp", "gsr_math.hpp", "gsr_sort.hpp", os.path.join("..", "..", "include", "gsr_hip.h")]
+
+
+def local_headers(sources=SOURCES):
+    """Every local header reached through `#include "..."` from `sources`, transitively, as paths relative to this directory."""
+    found, todo = [], list(sources)
+    while todo:
+        f = todo.pop()
+        with open(os.path.join(HERE, f)) as fh:
+            text = fh.read()
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', text, re.M):
+            rel = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+            if rel not in found and os.path.exists(os.path.join(HERE, rel)):
+                found.append(rel)
+                todo.append(rel)
+    return sorted(found)
+
+
+HEADERS = local_headers()     # an edit to any of them rebuilds the library
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fhip-fp32-correctly-rounded-divide-sqrt is hipcc's default; stated because parity of the integer outputs
 # (radii, tile rects, sort keys) relies on IEEE division and square root in the per-Gaussian kernels.
@@ -36,9 +54,14 @@ if os.environ.get("GSR_SLP") == "1":      # development switch for A/B measureme
     EXTRA_FLAGS = {}
 
 
+def digest_inputs():
+    """Files whose contents make up the build digest (paths relative to this directory)."""
+    return SOURCES + HEADERS + ["build.py"]
+
+
 def _digest():
     h = hashlib.sha256()
-    for f in SOURCES + HEADERS + ["build.py"]:
+    for f in digest_inputs():
         p = os.path.join(HERE, f)
         if os.path.exists(p):
             with open(p, "rb") as fh:

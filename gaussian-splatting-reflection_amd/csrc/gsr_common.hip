@@ -228,12 +228,12 @@ ImageState carve_image(void* buf, size_t HW, size_t tiles, int planes_T, int pla
 	if (total) *total = c.size();
 	return s;
 }
-BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_bytes, size_t* total) {
+BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_bytes, size_t* total, bool blend_masks) {
 	Carver c(buf);
 	BinningState b;
 	b.point_list = c.take<uint32_t>(R);
-	b.mask_stride = R / 64 + tiles + 1;
-	b.blend_mask = c.take<unsigned long long>(16 * b.mask_stride);
+	b.mask_stride = blend_masks ? R / 64 + tiles + 1 : 0;
+	b.blend_mask = blend_masks ? c.take<unsigned long long>(16 * b.mask_stride) : nullptr;
 	b.tile_keys = c.take<uint32_t>(R);
 	b.tile_keys_unsorted = c.take<uint32_t>(R);
 	b.vals_unsorted = c.take<uint32_t>(R);
@@ -583,7 +583,7 @@ static Readback* readback_slot() {
 static int rect_packs(int tiles_x, int tiles_y) { return (tiles_x <= 255 && tiles_y <= 255) ? 1 : 0; }   // see OrderRect
 
 int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int tiles_y, const GeomState& geom, const ImageState& img,
-                BinningState* out_binning, int prefiltered, int debug, hipStream_t stream) {
+                BinningState* out_binning, int prefiltered, int debug, hipStream_t stream, bool blend_masks) {
 	Readback* rb = readback_slot();
 	if (!rb) { set_error("pinned word / event for the num_rendered readback could not be created"); return GSR_E_HIP; }
 	int* host = rb->word;
@@ -649,10 +649,10 @@ int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int ti
 	const int bit = (int)higher_msb(tiles);
 	const size_t sort_bytes = R > 0 ? sort_temp_bytes((size_t)R, bit) : 0;
 	size_t total = 0;
-	carve_binning(nullptr, (size_t)R, (size_t)tiles, sort_bytes, &total);
+	carve_binning(nullptr, (size_t)R, (size_t)tiles, sort_bytes, &total, blend_masks);
 	void* buf = alloc(alloc_user, GSR_BUF_BINNING, total);
 	if (!buf && total > 0) { set_error("binning buffer allocation of %zu bytes failed", total); return GSR_E_ALLOC; }
-	BinningState b = carve_binning(buf, (size_t)R, (size_t)tiles, sort_bytes, nullptr);
+	BinningState b = carve_binning(buf, (size_t)R, (size_t)tiles, sort_bytes, nullptr, blend_masks);
 	*out_binning = b;
 
 	if (R == 0) GSR_HIP_CHECK(hipMemsetAsync(img.ranges, 0, (size_t)tiles * sizeof(uint2), stream));   // otherwise emit_tiles_kernel clears them

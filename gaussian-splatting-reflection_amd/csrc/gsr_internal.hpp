@@ -118,7 +118,7 @@ struct BinningState {
 
 GeomState carve_geom(void* buf, size_t P, int rec_f4, int aux_floats, int acc_floats, size_t scan_temp_bytes, size_t* total);
 ImageState carve_image(void* buf, size_t HW, size_t tiles, int planes_T, int planes_n, size_t* total);
-BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_temp_bytes, size_t* total);
+BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_temp_bytes, size_t* total, bool blend_masks = true);
 
 int option_cull();   // 1 (default): per-wave bounding-box culling in the tile kernels; 0: evaluate every list entry
 int option_dev();    // development ablation bits (0 in production): 1 = skip the gradient atomics of the surfel backward
@@ -129,9 +129,10 @@ uint32_t higher_msb(uint32_t n);
 
 // Binning pipeline shared by both variants (reference: DSR/DGR rasterizer_impl.cu:282-325):
 // inclusive scan of tiles_touched -> num_rendered (pinned 4-byte readback) -> binning buffer via alloc
-// -> key/value emission -> radix sort -> tile ranges.  Returns num_rendered or <0.
+// -> key/value emission -> radix sort -> tile ranges.  Returns num_rendered or <0.  blend_masks = false (a forward without backward):
+// no blend mask is reserved or cleared (mask_stride 0, blend_mask NULL); sort and ranges are the same.
 int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int tiles_y, const GeomState& geom,
-                const ImageState& img, BinningState* out_binning, int prefiltered, int debug, hipStream_t stream);
+                const ImageState& img, BinningState* out_binning, int prefiltered, int debug, hipStream_t stream, bool blend_masks = true);
 
 // Texel-gradient tail of the deferred-reflection backward (sort of the per-pixel footprint records by texel, run combine, unpack:
 // gsr_cubemap.hip) around the pixel kernel of gsr_deferred_reflection_backward*.  See refl_tail_begin in gsr_cubemap.hip.

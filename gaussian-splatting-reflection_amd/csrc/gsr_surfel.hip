@@ -6,6 +6,7 @@
 // Render record (80 bytes, five float4 per Gaussian, written by preprocess, gathered by the tile kernels), in even-aligned
 // pairs for packed fp32 math:  {x, y | Tu.x, Tv.x} {Tu.y, Tv.y | Tu.z, Tv.z} {Tw.x, Tw.y | Tw.z, opacity} {n.x, n.y | n.z, refl}
 // {r, g | b, mask}   (Tu, Tv, Tw = rows of the 3x3 homography "transMat").
+#include <type_traits>
 #include "gsr_internal.hpp"
 #include "gsr_sort.hpp"
 #include "gsr_math.hpp"
@@ -144,6 +145,9 @@ __device__ __forceinline__ void surfel_cull_record(const M3& T, float cx, float 
 // kernel: 0.175 -> 0.249 / 0.321 ms at C3, the registers it gives up cost more than the waves it gains.)
 // One Gaussian of the pass; returns false where the reference's kernel returns early.  The render record (5 float4) and the
 // cull record (2 float4) are handed back in `o` instead of being stored: the wave stores them together (see the kernel).
+// TRAIN = false (inference forward, gsr_surfel_forward_eval): what only the backward reads — the zero-fill of gaussian_weights and
+// the SH clamp flags — is not written; the records come out the same.
+template <bool TRAIN>
 __device__ __forceinline__ bool
 surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
                       const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
@@ -152,7 +156,7 @@ surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, co
                       int prefiltered, float* __restrict__ gaussian_weights, float4* o) {
 #pragma clang fp contract(off)
 	radii[idx] = 0;
-	gaussian_weights[idx] = 0.f;   // the tile kernel merges per-wave maxima into it with atomicMax
+	if constexpr (TRAIN) gaussian_weights[idx] = 0.f;   // the tile kernel merges per-wave maxima into it with atomicMax
 	g.tiles_touched[idx] = 0;
 	reinterpret_cast<uint2*>(g.rect)[idx] = make_uint2(0u, 0u);   // empty tile rectangle: emit_tiles_kernel takes the instance count from its area
 	g.depths[idx] = __int_as_float(0x7f7fffff);   // culled: sorts behind every visible Gaussian in the depth pre-sort
@@ -205,7 +209,7 @@ surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, co
 		ShRow s;
 		load_sh(shs, idx, M, (D + 1) * (D + 1), s);
 		const F3 c = sh_eval(D, s, dx / len, dy / len, dz / len);
-		g.clamped[idx] = (uint8_t)((c.x < 0 ? 1 : 0) | (c.y < 0 ? 2 : 0) | (c.z < 0 ? 4 : 0));
+		if constexpr (TRAIN) g.clamped[idx] = (uint8_t)((c.x < 0 ? 1 : 0) | (c.y < 0 ? 2 : 0) | (c.z < 0 ? 4 : 0));
 		cr = fmaxf(c.x, 0.0f); cg = fmaxf(c.y, 0.0f); cb = fmaxf(c.z, 0.0f);
 	} else {
 		cr = colors_precomp[3 * idx]; cg = colors_precomp[3 * idx + 1]; cb = colors_precomp[3 * idx + 2];
@@ -242,6 +246,7 @@ struct CubemapInterleave {
 	float4* rgba;
 	uint32_t ntex, LL;
 };
+template <bool TRAIN>
 __global__ void __launch_bounds__(256)
 surfel_preprocess_kernel(int P, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
                          const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
@@ -266,7 +271,7 @@ surfel_preprocess_kernel(int P, int D, int M, const float* __restrict__ means, c
 	for (int k = 0; k < S_OUT_F4; k++) o[k] = make_float4(0.f, 0.f, 0.f, 0.f);
 	bool live = false;
 	if (idx < P)
-		live = surfel_preprocess_one(idx, D, M, means, scales, scale_modifier, rotations, opacities, shs, transMat_precomp, colors_precomp, refl,
+		live = surfel_preprocess_one<TRAIN>(idx, D, M, means, scales, scale_modifier, rotations, opacities, shs, transMat_precomp, colors_precomp, refl,
 		                             env_scope_mask, cam, radii, g, gx, gy, prefiltered, gaussian_weights, o);
 	if (__ballot(live) == 0ull) return;      // (wave-uniform) nothing of this wave is ever read
 	const int g0 = idx - lane;               // first Gaussian of the wave
@@ -339,6 +344,9 @@ struct SurfelFwdPix {
 
 // One (wave, surfel) pair of the forward.  `done` = lanes whose pixel has retired (or lies outside the image); returns the
 // lanes that blended (ok) and updates `done`.  wq receives the blend weight (0 where the pair did not contribute).
+// TRAIN = false (inference forward): only T, colour, normal and reflection strength are accumulated — in the same expressions
+// and order, so they come out bit-identical — and contributor, med_live, wq and grazed are neither read nor written.
+template <bool TRAIN>
 __device__ __forceinline__ lmask surfel_fwd_pair(const SurfelRec& R, const v2f pix, uint32_t contributor, bool med_live, SurfelFwdPix& st,
                                                  lmask& done, float& wq, bool& grazed) {
 	float sx, sy, rho3d, depth, alpha, rho2d;
@@ -360,7 +368,7 @@ __device__ __forceinline__ lmask surfel_fwd_pair(const SurfelRec& R, const v2f p
 			sx = ppx * inv; sy = ppy * inv;
 			rho3d = sx * sx + sy * sy;
 		} else {                                      // some lane's ray grazes the splat plane: the reference's select form
-			grazed = true;                            // (the backward uses another threshold there: it must look at this pair itself)
+			if constexpr (TRAIN) grazed = true;       // (the backward uses another threshold there: it must look at this pair itself)
 			const float inv = div_nr(1.0f, selm(unstable, 1.0f, pz));
 			sx = selm(unstable, 0.f, ppx * inv); sy = selm(unstable, 0.f, ppy * inv);
 			rho3d = selm(unstable, 1e8f, sx * sx + sy * sy);
@@ -380,29 +388,33 @@ __device__ __forceinline__ lmask surfel_fwd_pair(const SurfelRec& R, const v2f p
 	const lmask sat = LMASK(test_T < 0.0001f) & live;   // this pixel is saturated: the pair is dropped and the pixel retires
 	const lmask ok = live & ~sat;
 	done |= sat;
-	wq = 0.f;
+	if constexpr (TRAIN) wq = 0.f;
 	if (ok != 0ull) {
 		const float w = selm0(ok, alpha * st.T);
-		const float dep = selm(ok, depth, 1.0f);
-		const float A = 1 - st.T;
-		const float m = S_FAR / (S_FAR - S_NEAR) * (1 - S_NEAR * __builtin_amdgcn_rcpf(dep));
 		const v2f w2 = mk2(w, w);
-		st.distortion += (m * m * A + st.M2 - 2 * m * st.DM.y) * w;
-		st.M2 += m * (m * w);
-		st.DM = __builtin_elementwise_fma(mk2(dep, m), w2, st.DM);        // depth sum, M1
-		if (med_live) {                                                  // median depth: last pair seen while T > 0.5
-			const lmask med = ok & LMASK(st.T > 0.5f);
-			st.median_depth = selm(med, dep, st.median_depth);
-			st.median_contributor = selm(med, (float)contributor, st.median_contributor);
+		if constexpr (TRAIN) {
+			const float dep = selm(ok, depth, 1.0f);
+			const float A = 1 - st.T;
+			const float m = S_FAR / (S_FAR - S_NEAR) * (1 - S_NEAR * __builtin_amdgcn_rcpf(dep));
+			st.distortion += (m * m * A + st.M2 - 2 * m * st.DM.y) * w;
+			st.M2 += m * (m * w);
+			st.DM = __builtin_elementwise_fma(mk2(dep, m), w2, st.DM);        // depth sum, M1
+			if (med_live) {                                                  // median depth: last pair seen while T > 0.5
+				const lmask med = ok & LMASK(st.T > 0.5f);
+				st.median_depth = selm(med, dep, st.median_depth);
+				st.median_contributor = selm(med, (float)contributor, st.median_contributor);
+			}
 		}
 		st.Nxy = __builtin_elementwise_fma(R.nxy(), w2, st.Nxy);
 		st.NzR = __builtin_elementwise_fma(mk2(R.nz(), R.refl()), w2, st.NzR);
 		st.Crg = __builtin_elementwise_fma(R.rg(), w2, st.Crg);
 		st.C2 = fmaf(R.b(), w, st.C2);
-		st.maskacc = fmaf(R.mask(), w, st.maskacc);   // > 0 iff a contributor inside the env scope blended (w > 0 for every ok pair)
+		if constexpr (TRAIN) st.maskacc = fmaf(R.mask(), w, st.maskacc);   // > 0 iff a contributor inside the env scope blended (w > 0 for every ok pair)
 		st.T = selm(ok, test_T, st.T);
-		st.last_contributor = selmu(ok, contributor, st.last_contributor);
-		wq = w;
+		if constexpr (TRAIN) {
+			st.last_contributor = selmu(ok, contributor, st.last_contributor);
+			wq = w;
+		}
 	}
 	return ok;
 }
@@ -424,13 +436,30 @@ struct SurfelReflFwd {
 	float* out_nworld;
 	uint32_t* sort_keys;
 };
-template <bool REFL>
+// Last argument of the inference instance (TRAIN = false, gsr_surfel_forward_eval), which writes alpha = 1 - T (plane 1 of out_others in
+// training) and the blended view-space normal (planes 2..4; out_normal NULL: not stored) to planes of their own.  The training instances keep
+// their argument list as it was.
+struct SurfelEvalFwd {
+	SurfelReflFwd refl;   // (sort_keys NULL)
+	float* out_alpha;
+	float* out_normal;
+};
+__device__ __forceinline__ const SurfelReflFwd& refl_args(const SurfelReflFwd& a) { return a; }
+__device__ __forceinline__ const SurfelReflFwd& refl_args(const SurfelEvalFwd& a) { return a.refl; }
+// TRAIN = false compiles out everything only the backward reads: the depth / distortion / median / env-scope accumulators, the contributor
+// numbers, the gaussian_weights row maxima and atomics, the grazing bookkeeping and blend masks, and the stores of final_T, n_contrib,
+// out_others planes 0 and 5..7 and the reflection sort keys.  What is left — vote, compaction, the blending of colour, T, normal and reflection
+// strength in the same expressions and order, the same early exit, the reflection epilogue — gives bit-identical colour, alpha, normal and
+// reflection planes (each pixel's accumulation runs sequentially over the tile's list in both instances).
+template <bool REFL, bool TRAIN>
 __global__ void __launch_bounds__(64) GSR_FWD_ATTR
 surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ point_list, int W, int H, int tiles_x, int ntiles,
                               const float4* __restrict__ rec, const float4* __restrict__ bbox, int cull, const float* __restrict__ bg,
                               float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
                               float* __restrict__ out_others, float* __restrict__ out_refl, float* __restrict__ gaussian_weights,
-                              unsigned long long* __restrict__ blend_mask, size_t mask_stride, SurfelReflFwd rf) {
+                              unsigned long long* __restrict__ blend_mask, size_t mask_stride,
+                              std::conditional_t<TRAIN, SurfelReflFwd, SurfelEvalFwd> args) {
+	const SurfelReflFwd& rf = refl_args(args);
 	const uint32_t slot = xcd_slot(blockIdx.x);   // dispatch slot -> (tile, quadrant), longest lists first
 	if (slot >= (uint32_t)ntiles * 4u) return;
 	const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_order[slot >> 2]), quad = slot & 3u;   // (readfirstlane: the compiler cannot see that the loaded tile id is wave-uniform)
@@ -447,8 +476,8 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 	const float qx0 = (float)bx0, qy0 = (float)by0, qx1 = qx0 + 7.0f, qy1 = qy0 + 7.0f;
 
 	__shared__ uint32_t s_hid[S_WBATCH];
-	__shared__ uint32_t s_hc[S_WBATCH];
-	__shared__ float4 s_wmax[S_WBATCH];            // [hit][16-lane row = 4x4 sub-block]: row maxima of the blend weight
+	__shared__ uint32_t s_hc[TRAIN ? S_WBATCH : 1];
+	__shared__ float4 s_wmax[TRAIN ? S_WBATCH : 1];   // [hit][16-lane row = 4x4 sub-block]: row maxima of the blend weight
 
 	lmask done = ~LMASK(px < W) | ~LMASK(py < H);  // lanes outside the image never blend
 	SurfelFwdPix st;
@@ -477,15 +506,15 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 		const unsigned long long mm = __ballot(hit);
 		const int nh = __popcll(mm);
 		if (nh == 0) continue;
-		s_wmax[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+		if constexpr (TRAIN) s_wmax[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
 		const int kown = __popcll(mm & ((1ull << lane) - 1ull));   // this lane's entry is hit number kown (if it is a hit)
 		if (hit) {
 			s_hid[kown] = id;
-			s_hc[kown] = (uint32_t)(base + lane + 1);  // the pair's contributor number (1-based position in the tile's list)
+			if constexpr (TRAIN) s_hc[kown] = (uint32_t)(base + lane + 1);  // the pair's contributor number (1-based position in the tile's list)
 		}
 		__syncthreads();
 		const uint32_t hid = lane < nh ? s_hid[lane] : 0u;
-		const uint32_t hc = lane < nh ? s_hc[lane] : 0u;
+		const uint32_t hc = TRAIN && lane < nh ? s_hc[lane] : 0u;
 		// ---- 2. blend.  Two SGPR record buffers ping-pong (as in the backward): the s_load of the next record is issued
 		// right after the arithmetic of the current one has started; with a single rotating buffer the compiler copies the 20
 		// SGPRs twice per pair.  Four pairs per trip: their blend weights share one packed row-max reduction.
@@ -503,37 +532,40 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 			{
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k);
 				if (k + 1 < nh) B = fetch(k + 1);
-				any |= surfel_fwd_pair(A, pix, c, med_live, st, done, w0, grazed);
+				any |= surfel_fwd_pair<TRAIN>(A, pix, c, med_live, st, done, w0, grazed);
 				stop = done == ~0ull || k + 1 >= nh;
 			}
 			if (!stop) {
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k + 1);
 				if (k + 2 < nh) A = fetch(k + 2);
-				any |= surfel_fwd_pair(B, pix, c, med_live, st, done, w1, grazed);
+				any |= surfel_fwd_pair<TRAIN>(B, pix, c, med_live, st, done, w1, grazed);
 				stop = done == ~0ull || k + 2 >= nh;
 			}
 			if (!stop) {
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k + 2);
 				if (k + 3 < nh) B = fetch(k + 3);
-				any |= surfel_fwd_pair(A, pix, c, med_live, st, done, w2, grazed);
+				any |= surfel_fwd_pair<TRAIN>(A, pix, c, med_live, st, done, w2, grazed);
 				stop = done == ~0ull || k + 3 >= nh;
 			}
 			if (!stop) {
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k + 3);
 				if (k + 4 < nh) A = fetch(k + 4);
-				any |= surfel_fwd_pair(B, pix, c, med_live, st, done, w3, grazed);
+				any |= surfel_fwd_pair<TRAIN>(B, pix, c, med_live, st, done, w3, grazed);
 				stop = done == ~0ull;
 			}
-			if (grazed) force |= 0xFull << k;    // (the whole group of four: which of them grazed is not worth tracking)
-			if (any != 0ull) {
-				// gaussian_weights (forward.cu:458-459): row maxima of the four weights; the rows are merged in step 3
-				const float z = row_max4(w0, w1, w2, w3);
-				reinterpret_cast<float*>(s_wmax)[(k * 16 + wmax_off) >> 2] = z;   // the four lanes of a quad store the same value
-				med_live = med_live && LMASK(st.T > 0.5f) != 0ull;
+			if constexpr (TRAIN) {
+				if (grazed) force |= 0xFull << k;    // (the whole group of four: which of them grazed is not worth tracking)
+				if (any != 0ull) {
+					// gaussian_weights (forward.cu:458-459): row maxima of the four weights; the rows are merged in step 3
+					const float z = row_max4(w0, w1, w2, w3);
+					reinterpret_cast<float*>(s_wmax)[(k * 16 + wmax_off) >> 2] = z;   // the four lanes of a quad store the same value
+					med_live = med_live && LMASK(st.T > 0.5f) != 0ull;
+				}
 			}
 			if (stop) break;
 		}
 		__syncthreads();
+		if constexpr (!TRAIN) continue;   // (the barrier above orders this batch's reads of s_hid before the next batch's writes)
 		// ---- 3. per entry (each lane looks at ITS entry of the batch again): merge the four row maxima of its blend weight.
 		// w > 0 always, so the IEEE bit pattern orders like a signed int; the reference's check-then-atomicExch is racy,
 		// this is the true maximum.  The entries that blended anywhere in a 4x4 sub-block (its row maximum is > 0) form that
@@ -559,13 +591,15 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 		const size_t HW = (size_t)H * W;
 		const size_t p = (size_t)W * py + px;
 		const float T = st.T;
-		final_T[p] = T;
-		final_T[HW + p] = st.DM.y;
-		final_T[2 * HW + p] = st.M2;
-		n_contrib[p] = st.last_contributor;
-		// the reference converts the float -1 of "no median" with cvt.rzi.u32.f32, which saturates to 0; in C++ that
-		// conversion is undefined (and clang does exploit it), so the clamp is explicit
-		n_contrib[HW + p] = (uint32_t)fmaxf(st.median_contributor, 0.0f);
+		if constexpr (TRAIN) {
+			final_T[p] = T;
+			final_T[HW + p] = st.DM.y;
+			final_T[2 * HW + p] = st.M2;
+			n_contrib[p] = st.last_contributor;
+			// the reference converts the float -1 of "no median" with cvt.rzi.u32.f32, which saturates to 0; in C++ that
+			// conversion is undefined (and clang does exploit it), so the clamp is explicit
+			n_contrib[HW + p] = (uint32_t)fmaxf(st.median_contributor, 0.0f);
+		}
 		const float c0 = st.Crg.x + T * bg[0], c1 = st.Crg.y + T * bg[1], c2 = st.C2 + T * bg[2];
 		out_color[p] = c0;
 		out_color[HW + p] = c1;
@@ -574,7 +608,9 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 		if (REFL) {
 			ReflFwdOut ro;
 			refl_forward_pixel<true>(rf.cam, rf.cubemap, rf.rgba, rf.fail_value, rf.L, st.Nxy.x, st.Nxy.y, st.NzR.x, px, py, st.NzR.y, c0, c1, c2, rf.no_key, ro);
-			if (rf.sort_keys) rf.sort_keys[p] = ro.key;
+			if constexpr (TRAIN) {
+				if (rf.sort_keys) rf.sort_keys[p] = ro.key;
+			}
 #pragma unroll
 			for (int ch = 0; ch < 3; ch++) {
 				rf.out_final[ch * HW + p] = ro.final_c[ch];
@@ -584,14 +620,23 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 			rf.out_nworld[HW + p] = ro.ny;
 			rf.out_nworld[2 * HW + p] = ro.nz;
 		}
-		out_others[0 * HW + p] = st.DM.x;
-		out_others[1 * HW + p] = 1 - T;
-		out_others[2 * HW + p] = st.Nxy.x;
-		out_others[3 * HW + p] = st.Nxy.y;
-		out_others[4 * HW + p] = st.NzR.x;
-		out_others[5 * HW + p] = st.median_depth;
-		out_others[6 * HW + p] = st.distortion;
-		out_others[7 * HW + p] = st.maskacc > 0.f ? 1.0f : 0.f;
+		if constexpr (TRAIN) {
+			out_others[0 * HW + p] = st.DM.x;
+			out_others[1 * HW + p] = 1 - T;
+			out_others[2 * HW + p] = st.Nxy.x;
+			out_others[3 * HW + p] = st.Nxy.y;
+			out_others[4 * HW + p] = st.NzR.x;
+			out_others[5 * HW + p] = st.median_depth;
+			out_others[6 * HW + p] = st.distortion;
+			out_others[7 * HW + p] = st.maskacc > 0.f ? 1.0f : 0.f;
+		} else {
+			args.out_alpha[p] = 1 - T;
+			if (args.out_normal) {
+				args.out_normal[p] = st.Nxy.x;
+				args.out_normal[HW + p] = st.Nxy.y;
+				args.out_normal[2 * HW + p] = st.NzR.x;
+			}
+		}
 	}
 }
 
@@ -1223,7 +1268,7 @@ extern "C" int gsr_surfel_forward_refl(gsr_alloc_fn alloc, void* alloc_user, int
 		if ((size_t)6 * refl->L * refl->L >= 0xFFFFFFFFull) { set_error("gsr_surfel_forward_refl: cubemap too large"); return GSR_E_INVALID; }
 		ci = CubemapInterleave{refl->cubemap, reinterpret_cast<float4*>(refl->cubemap_rgba), 6u * refl->L * refl->L, refl->L * refl->L};
 	}
-{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
+{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<true><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
 	                                                              transMat_precomp, colors_precomp, refl_strengths, env_scope_mask, cam, radii, geom,
 	                                                              tiles_x, tiles_y, prefiltered, gaussian_weights, ci); }
 	GSR_LAUNCH_CHECK(debug, stream);
@@ -1237,11 +1282,11 @@ extern "C" int gsr_surfel_forward_refl(gsr_alloc_fn alloc, void* alloc_user, int
 	if (refl) {
 		const SurfelReflFwd rf{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
 		                       refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->sort_keys};
-		surfel_render_fwd_wave_kernel<true><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
+		surfel_render_fwd_wave_kernel<true, true><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
 		                                                               option_cull(), background, img.final_T, img.n_contrib, out_color, out_others,
 		                                                               out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, rf);
 	} else {
-		surfel_render_fwd_wave_kernel<false><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
+		surfel_render_fwd_wave_kernel<false, true><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
 		                                                                option_cull(), background, img.final_T, img.n_contrib, out_color, out_others,
 		                                                                out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, SurfelReflFwd{});
 	} }
@@ -1262,6 +1307,101 @@ extern "C" int gsr_surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, i
 	return gsr_surfel_forward_refl(alloc, alloc_user, P, D, M, background, width, height, means3D, env_scope_mask, shs, colors_precomp, refl_strengths, opacities,
 	                               scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
 	                               out_others, out_refl_strength_map, radii, gaussian_weights, nullptr, debug, stream_);
+}
+
+extern "C" int gsr_surfel_forward_eval(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,
+                                       const float* means3D, const float* shs, const float* colors_precomp, const float* refl_strengths,
+                                       const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                                       const float* transMat_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                                       float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_alpha,
+                                       float* out_normal_view, float* out_refl_strength_map, int* radii, const gsr_refl_forward* refl,
+                                       int debug, void* stream_) {
+	hipStream_t stream = (hipStream_t)stream_;
+	// every check comes before the first device call
+	if (!alloc || P < 0 || width <= 0 || height <= 0 || !background || !out_color || !out_alpha || !out_refl_strength_map) {
+		set_error("gsr_surfel_forward_eval: invalid argument (alloc, P >= 0, width, height, background, out_color, out_alpha, out_refl_strength_map)");
+		return GSR_E_INVALID;
+	}
+	if (!out_normal_view && !refl) { set_error("gsr_surfel_forward_eval: out_normal_view may be NULL only with refl"); return GSR_E_INVALID; }
+	if (refl && (refl->sort_keys || refl->scratch)) {
+		set_error("gsr_surfel_forward_eval: refl->sort_keys and refl->scratch must be NULL (the eval forward has no backward)");
+		return GSR_E_INVALID;
+	}
+	if (refl && (!refl->cam || !refl->cubemap || !refl->fail_value || refl->L == 0 || !refl->cubemap_rgba || ((uintptr_t)refl->cubemap_rgba & 15) != 0 ||
+	             !refl->out_final || !refl->out_refl_color || !refl->out_normal_world)) {
+		set_error("gsr_surfel_forward_eval: incomplete reflection descriptor (cam, cubemap, fail_value, L, 16-byte aligned cubemap_rgba and the three outputs are required)");
+		return GSR_E_INVALID;
+	}
+	if (refl && (size_t)6 * refl->L * refl->L >= 0xFFFFFFFFull) { set_error("gsr_surfel_forward_eval: cubemap too large"); return GSR_E_INVALID; }
+	if (P > 0) {
+		if (!means3D || !opacities || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii || (!shs && !colors_precomp) ||
+		    ((!scales || !rotations) && !transMat_precomp)) {
+			set_error("gsr_surfel_forward_eval: missing required input pointer");
+			return GSR_E_INVALID;
+		}
+		if (D < 0 || D > 3 || (shs && (D + 1) * (D + 1) > M)) { set_error("gsr_surfel_forward_eval: SH degree %d not supported with M=%d", D, M); return GSR_E_INVALID; }
+		if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(shs, "shs (rows of a multiple of 16 bytes)");
+	}
+	const size_t HW = (size_t)width * height;
+	if (P == 0) {
+		float* normal = out_normal_view;
+		if (!normal) {   // the stand-alone pixel pass below reads the normal planes
+			normal = static_cast<float*>(alloc(alloc_user, GSR_BUF_IMAGE, HW * 3 * 4));
+			if (!normal) { set_error("workspace allocation failed (%zu bytes)", HW * 3 * 4); return GSR_E_ALLOC; }
+		}
+		GSR_HIP_CHECK(hipMemsetAsync(out_color, 0, HW * 3 * 4, stream));
+		GSR_HIP_CHECK(hipMemsetAsync(out_alpha, 0, HW * 4, stream));
+		GSR_HIP_CHECK(hipMemsetAsync(normal, 0, HW * 3 * 4, stream));
+		GSR_HIP_CHECK(hipMemsetAsync(out_refl_strength_map, 0, HW * 4, stream));
+		if (refl)    // an empty scene through the stand-alone pixel pass, as gsr_surfel_forward_refl does (no keys)
+			return gsr_deferred_reflection_forward_keys(normal, out_color, out_refl_strength_map, refl->cam, refl->cubemap, refl->fail_value, refl->L,
+			                                            width, height, refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->cubemap_rgba,
+			                                            nullptr, stream_) < 0 ? GSR_E_HIP : 0;
+		return 0;
+	}
+	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
+	const int ntiles = tiles_x * tiles_y;
+
+	// workspace: no backward accumulator, no final_T / n_contrib planes, no blend masks
+	size_t geom_bytes = 0, img_bytes = 0;
+	const size_t scan_bytes = scan_temp_bytes(P);
+	carve_geom(nullptr, P, S_REC_F4, 0, 0, scan_bytes, &geom_bytes);
+	carve_image(nullptr, HW, ntiles, 0, 0, &img_bytes);
+	void* gbuf = alloc(alloc_user, GSR_BUF_GEOM, geom_bytes);
+	void* ibuf = alloc(alloc_user, GSR_BUF_IMAGE, img_bytes);
+	if (!gbuf || !ibuf) { set_error("workspace allocation failed (%zu / %zu bytes)", geom_bytes, img_bytes); return GSR_E_ALLOC; }
+	GeomState geom = carve_geom(gbuf, P, S_REC_F4, 0, 0, scan_bytes, nullptr);
+	ImageState img = carve_image(ibuf, HW, ntiles, 0, 0, nullptr);
+
+	if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));
+	const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
+	CubemapInterleave ci{nullptr, nullptr, 0u, 1u};
+	if (refl) ci = CubemapInterleave{refl->cubemap, reinterpret_cast<float4*>(refl->cubemap_rgba), 6u * refl->L * refl->L, refl->L * refl->L};
+{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<false><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
+	                                                                     transMat_precomp, colors_precomp, refl_strengths, nullptr, cam, radii, geom,
+	                                                                     tiles_x, tiles_y, prefiltered, nullptr, ci); }
+	GSR_LAUNCH_CHECK(debug, stream);
+
+	BinningState bin;
+	const int R = run_binning(alloc, alloc_user, P, tiles_x, tiles_y, geom, img, &bin, prefiltered, debug, stream, false);
+	if (R < 0) return R;
+
+{ StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
+	const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
+	SurfelEvalFwd ev{SurfelReflFwd{}, out_alpha, out_normal_view};
+	if (refl) {
+		ev.refl = SurfelReflFwd{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
+		                        refl->out_final, refl->out_refl_color, refl->out_normal_world, nullptr};
+		surfel_render_fwd_wave_kernel<true, false><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec,
+		                                                                      geom.bbox, option_cull(), background, nullptr, nullptr, out_color, nullptr,
+		                                                                      out_refl_strength_map, nullptr, nullptr, 0, ev);
+	} else {
+		surfel_render_fwd_wave_kernel<false, false><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec,
+		                                                                       geom.bbox, option_cull(), background, nullptr, nullptr, out_color, nullptr,
+		                                                                       out_refl_strength_map, nullptr, nullptr, 0, ev);
+	} }
+	GSR_LAUNCH_CHECK(debug, stream);
+	return R;
 }
 
 extern "C" int gsr_surfel_backward_ex(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,

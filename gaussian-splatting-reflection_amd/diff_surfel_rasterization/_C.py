@@ -89,6 +89,58 @@ def rasterize_gaussians(background, means3D, env_scope_mask, colors, refl_streng
     return (rendered, out_color, out_others, radii, geomBuffer, binningBuffer, imgBuffer, out_refl, gaussian_weights) + extra
 
 
+def rasterize_gaussians_eval(background, means3D, colors, refl_strengths, opacity, scales, rotations, scale_modifier, transMat_precomp,
+                             viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug, *,
+                             refl=None):
+    """Extension (ABI 102): the inference-only forward, gsr_surfel_forward_eval — no backward can follow it.  Arguments as
+    rasterize_gaussians without env_scope_mask; `refl`: None, or a dict with `cam`, `cubemap` [6,3,L,L] and `fail_value` [3] (no keys).
+    Returns (num_rendered, color[3,H,W], alpha[1,H,W], normal_view[3,H,W] | None, refl_strength_map[1,H,W], radii[P] int32), and with
+    `refl` also (final[3,H,W], refl_color[3,H,W], normal_world[3,H,W]); normal_view is None then (the epilogue consumes it).  Every
+    plane is bit-identical to the corresponding output of rasterize_gaussians (alpha = allmap[1:2], normal_view = allmap[2:5])."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    for name, t in (("background", background), ("means3D", means3D), ("colors", colors), ("refl_strengths", refl_strengths),
+                    ("opacity", opacity), ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
+                    ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh), ("campos", campos)):
+        require_cuda(t, name)
+    P, H, W = means3D.size(0), int(image_height), int(image_width)
+    dev = means3D.device
+    fopts = dict(dtype=torch.float32, device=dev)
+    out_color = torch.empty((NUM_CHANNELS, H, W), **fopts)
+    out_alpha = torch.empty((1, H, W), **fopts)
+    out_normal = torch.empty((3, H, W), **fopts) if refl is None else None
+    out_refl = torch.empty((1, H, W), **fopts)
+    radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    ws = _gsr.Workspace(dev)
+    M = sh.size(1) if sh.numel() != 0 else 0
+    keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh"), f32c(colors, "colors"),
+            f32c(refl_strengths, "refl_strengths"), f32c(opacity, "opacity"), f32c(scales, "scales"), f32c(rotations, "rotations"),
+            f32c(transMat_precomp, "transMat_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"),
+            f32c(campos, "campos")]
+    bg, m3, shc, col, rfl, opa, sca, rot, tmp, vm, pm, cp = keep
+    desc, extra = None, ()
+    if refl is not None:
+        cm, fv, cam = f32c(refl["cubemap"], "cubemap"), f32c(refl["fail_value"], "fail_value"), f32c(refl["cam"], "cam")
+        if cm.dim() != 4 or cm.shape[0] != 6 or cm.shape[1] != 3 or cm.shape[2] != cm.shape[3]:
+            raise RuntimeError("rasterize + reflect: the cubemap must be (6, 3, L, L)")
+        L = int(cm.shape[2])
+        final, refl_color, normal_world = (torch.empty((3, H, W), **fopts) for _ in range(3))
+        rgba = torch.empty(6 * L * L * 4, **fopts)
+        desc = _gsr.ReflForward(ptr(cam), ptr(cm), ptr(fv), L, ptr(rgba), ptr(final), ptr(refl_color), ptr(normal_world), None, None, 0, 0)
+        keep += [cm, fv, cam, rgba]
+        extra = (final, refl_color, normal_world)
+    with torch.cuda.device(dev):
+        rendered = check(lib.gsr_surfel_forward_eval(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(shc), ptr(col), ptr(rfl),
+                                                     ptr(opa), ptr(sca), float(scale_modifier), ptr(rot), ptr(tmp), ptr(vm), ptr(pm), ptr(cp),
+                                                     float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), ptr(out_color), ptr(out_alpha),
+                                                     ptr(out_normal), ptr(out_refl), ptr(radii),
+                                                     ctypes.byref(desc) if desc is not None else None, int(bool(debug)), stream_ptr(dev)),
+                         "gsr_surfel_forward_eval")
+    if ws.error is not None:
+        raise ws.error
+    return (rendered, out_color, out_alpha, out_normal, out_refl, radii) + extra
+
+
 def rasterize_gaussians_backward(background, means3D, radii, colors, refl_strengths, scales, rotations, scale_modifier, transMat_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_others, dL_dout_refl_strength_map, sh,
                                  degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *, grad_sink=None, accumulate=False, unused=(),

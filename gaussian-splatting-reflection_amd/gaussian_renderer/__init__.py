@@ -323,6 +323,39 @@ def rasterize_reflect(rasterizer, env_map, world_view_transform, HWK, R, T, mean
                                    rasterizer.raster_settings, rasterizer._grad_sink, rsink)
 
 
+def rasterize_eval(rasterizer, means3D, opacities, shs=None, colors_precomp=None, refl_strengths=None, scales=None, rotations=None,
+                   cov3D_precomp=None, env_map=None, world_view_transform=None, HWK=None, R=None, T=None):
+    """Extension: inference-only forward of the surfel rasterizer (gsr_surfel_forward_eval), for a render that no backward follows.  It skips
+    everything only a backward reads (depth, distortion, median and env-scope planes, gaussian_weights, contributor counts, blend masks) and
+    returns the planes render_fast() shows, bit-identical to those of `rasterizer(...)` / rasterize_reflect():
+      {"render", "rend_alpha" [1,H,W], "rend_normal", "refl_strength_map" [1,H,W]}, and with env_map (camera arguments as rasterize_reflect)
+      "render" = final image of the fused reflection epilogue, "rend_normal" = world-space shading normal, "refl_color_map", "base_color_map";
+      without env_map "render" = base colour and "rend_normal" = the blended view-space normal (allmap[2:5]).
+    `rasterizer`: a diff_surfel_rasterization.GaussianRasterizer; its settings apply.  There is no backward: with grad mode on and an input
+    that requires grad this raises RuntimeError."""
+    inputs = (means3D, opacities, shs, colors_precomp, refl_strengths, scales, rotations, cov3D_precomp)
+    if env_map is not None:
+        inputs += (env_map.params['Cubemap_texture'], env_map.params['Cubemap_failv'])
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in inputs):
+        raise RuntimeError("rasterize_eval has no backward; use rasterize_reflect / GaussianRasterizer")
+    t = rasterizer._collect(means3D, None, opacities, shs=shs, colors_precomp=colors_precomp, refl_strengths=refl_strengths, scales=scales,
+                            rotations=rotations, cov3D_precomp=cov3D_precomp, env_scope_mask=None)
+    s = rasterizer.raster_settings
+    refl = None
+    if env_map is not None:
+        refl = dict(cam=_cam_block(world_view_transform, HWK, R, T), cubemap=env_map.params['Cubemap_texture'].detach(),
+                    fail_value=env_map.params['Cubemap_failv'].detach())
+    ret = _dsr._C.rasterize_gaussians_eval(s.bg, t["means3D"], t["colors_precomp"], t["refl_strengths"], t["opacities"], t["scales"],
+                                           t["rotations"], s.scale_modifier, t["cov3Ds_precomp"], s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
+                                           s.image_height, s.image_width, t["sh"], s.sh_degree, s.campos, s.prefiltered, s.debug, refl=refl)
+    _, color, alpha, normal_view, refl_map, _ = ret[:6]
+    if refl is None:
+        return {"render": color, "rend_alpha": alpha, "rend_normal": normal_view, "refl_strength_map": refl_map}
+    final, refl_color, normal_world = ret[6:]
+    return {"render": final, "rend_alpha": alpha, "rend_normal": normal_world, "refl_strength_map": refl_map, "refl_color_map": refl_color,
+            "base_color_map": color}
+
+
 class _ShadingNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, normal_view, cam):
@@ -480,8 +513,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
 
 def render_fast(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, initial_stage=False):
     """Inference path (the reference's render_fast, used by its eval_fps.py / render.py): all-true env-scope mask, no depth
-    or normal-consistency outputs."""
+    or normal-consistency outputs.  Under torch.no_grad() it runs the inference-only forward (rasterize_eval: same values, none of
+    the work only a backward reads); with grad mode on, the training forward, so that the result stays differentiable."""
     xyz = pc.get_xyz
+    if not torch.is_grad_enabled():
+        return _render_fast_eval(viewpoint_camera, pc, bg_color, scaling_modifier, initial_stage)
     means2D = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
     rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, bg_color, scaling_modifier))
     v = viewpoint_camera
@@ -502,6 +538,26 @@ def render_fast(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, init
                                                                v.world_view_transform, v.HWK, v.R, v.T)
     return {"render": final_image, "rend_alpha": allmap[1:2], "rend_normal": rend_normal, "refl_strength_map": refl_strength_map,
             "refl_color_map": refl_color, "base_color_map": base_color}
+
+
+def _render_fast_eval(viewpoint_camera, pc, bg_color, scaling_modifier, initial_stage):
+    rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, bg_color, scaling_modifier))
+    v = viewpoint_camera
+    fused = FUSED_REFLECTION and not initial_stage
+    out = rasterize_eval(rasterizer, pc.get_xyz, pc.get_opacity, shs=pc.get_features, refl_strengths=pc.get_refl, scales=pc.get_scaling,
+                         rotations=pc.get_rotation, env_map=pc.get_envmap if fused else None, world_view_transform=v.world_view_transform,
+                         HWK=v.HWK, R=v.R, T=v.T)
+    if fused:
+        return out
+    normal_view = out["rend_normal"]
+    if initial_stage:
+        out["rend_normal"] = shading_normal(normal_view, v.world_view_transform, v.HWK, v.R, v.T)
+        return out
+    base_color = out["render"]
+    final_image, refl_color, rend_normal = deferred_reflection(normal_view, base_color, out["refl_strength_map"], pc.get_envmap,
+                                                               v.world_view_transform, v.HWK, v.R, v.T)
+    out.update({"render": final_image, "rend_normal": rend_normal, "refl_color_map": refl_color, "base_color_map": base_color})
+    return out
 
 
 def _panorama_dirs(H, W, device):

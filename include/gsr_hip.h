@@ -54,8 +54,9 @@ const char* gsr_last_error(void);
  * arguments.  Rule: an exported entry point NEVER changes its signature; extensions get new symbols (…_accum, …_ex, …_keys, …_refl).
  *   100  rounds 1-3.  Round 3 broke the rule once: gsr_deferred_reflection_forward_ex / _backward_ex gained a sort_keys argument in place.
  *   101  round 4: those two are back to their round-2 signatures (no sort_keys) and the forms with keys are the new symbols
- *        gsr_deferred_reflection_forward_keys / _backward_keys; new: gsr_gauss_backward_accum, gsr_surfel_forward_refl. */
-#define GSR_ABI_VERSION 101
+ *        gsr_deferred_reflection_forward_keys / _backward_keys; new: gsr_gauss_backward_accum, gsr_surfel_forward_refl.
+ *   102  new: gsr_surfel_forward_eval (inference-only surfel forward).  No existing signature changed. */
+#define GSR_ABI_VERSION 102
 int gsr_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -162,6 +163,22 @@ int gsr_surfel_forward_refl(gsr_alloc_fn alloc, void* alloc_user, int P, int D, 
                        float tan_fovy, int prefiltered, float* out_color, float* out_others,
                        float* out_refl_strength_map, int* radii, float* gaussian_weights, const gsr_refl_forward* refl,
                        int debug, void* stream);
+/* Extension (ABI 102): inference-only form of gsr_surfel_forward_refl, for a forward that no backward follows.  It computes and writes only
+ * what a renderer shows: none of the depth, distortion, median and env-scope planes, gaussian_weights, SH clamp flags, final_T / n_contrib or
+ * blend masks that only the backward reads.  Every plane it writes is bit-identical to the corresponding output of gsr_surfel_forward_refl
+ * for the same inputs, and num_rendered and radii are the same.
+ *   out_color [3,H,W]; out_alpha [H,W] = 1 - T (out_others plane 1); out_normal_view [3,H,W] = blended view-space normal (out_others planes
+ *   2..4), may be NULL only when refl != NULL; out_refl_strength_map [H,W]; radii int32[P].  All are fully written.
+ *   refl: NULL, or the descriptor of gsr_surfel_forward_refl with the same meaning, except that sort_keys and scratch must be NULL / 0
+ *   (there is no backward to hand them to; GSR_E_INVALID otherwise).
+ * Workspace: the same three gsr_alloc_fn buffers, smaller.  Every argument is checked before the first device call.  Returns num_rendered. */
+int gsr_surfel_forward_eval(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,
+                            const float* means3D, const float* shs, const float* colors_precomp, const float* refl_strengths,
+                            const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                            const float* transMat_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                            float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_alpha,
+                            float* out_normal_view, float* out_refl_strength_map, int* radii, const gsr_refl_forward* refl,
+                            int debug, void* stream);
 /* ---------------------------------------------------------------------------------------------
  * Variant G — 3D Gaussians with EWA projection, anti-aliasing and inverse depth.  Replaces
  * CudaRasterizer::Rasterizer::forward (DGR cuda_rasterizer/rasterizer.h:24-57, rasterizer_impl.cu:198-349).

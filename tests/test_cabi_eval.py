@@ -1,0 +1,134 @@
+"""The inference-only surfel forward's C entry (gsr_surfel_forward_eval, ABI 102) on a machine without a GPU: declared, exported and
+bound with the header's argument list, and every refusal happens before the first device call.  Also: the build digest covers every
+local header the sources include, so that an edit to any of them rebuilds the library."""
+import ctypes
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gaussian-splatting-reflection_amd", "csrc")
+HEADER = os.path.join(ROOT, "include", "gsr_hip.h")
+GSR_E_INVALID = -1
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def test_eval_entry_is_declared_exported_and_bound(hip_lib_built):
+    import _gsr
+    m = re.search(r"int\s+gsr_surfel_forward_eval\s*\(([^;]*?)\)\s*;", _header(), flags=re.S)
+    assert m, "gsr_surfel_forward_eval is not declared in gsr_hip.h"
+    assert hasattr(ctypes.CDLL(_gsr.LIB_PATH), "gsr_surfel_forward_eval")
+    assert "gsr_surfel_forward_eval" in _gsr.EXPORTED
+    P, F, I = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
+    want = []
+    for arg in (a.strip() for a in m.group(1).split(",")):
+        if arg.startswith("gsr_alloc_fn"):
+            want.append(_gsr.ALLOC_FN)
+        elif arg.startswith("const gsr_refl_forward*"):
+            want.append(ctypes.POINTER(_gsr.ReflForward))
+        elif "*" in arg:
+            want.append(P)
+        elif arg.startswith("float"):
+            want.append(F)
+        else:
+            assert arg.startswith("int"), arg
+            want.append(I)
+    assert len(want) == 31
+    assert list(_gsr.lib.gsr_surfel_forward_eval.argtypes) == want
+
+
+def test_abi_version_is_102(hip_lib_built):
+    import _gsr
+    hdr = open(HEADER).read()
+    assert int(re.search(r"#define GSR_ABI_VERSION (\d+)", hdr).group(1)) == 102
+    assert _gsr.GSR_ABI_VERSION == 102
+    assert _gsr.lib.gsr_version() == 102
+
+
+class _Call:
+    """A call of gsr_surfel_forward_eval with well-formed (never dereferenced) pointers; `kw` overrides one argument.  The alloc
+    callback records whether the library got as far as asking for workspace."""
+
+    def __init__(self):
+        import _gsr
+        self.gsr = _gsr
+        self.allocs = []
+        self.cb = _gsr.ALLOC_FN(lambda user, which, nbytes: self.allocs.append(which) or 0)
+        self.fake = 0x7f0000000000        # 256-byte aligned, never touched: every call below must fail validation first
+
+    def __call__(self, **kw):
+        f = self.fake
+        a = dict(alloc=self.cb, user=None, P=100, D=3, M=16, bg=f, W=64, H=48, means=f, shs=f, colors=None, refl_s=f, opac=f, scales=f,
+                 mod=1.0, rot=f, tmat=None, view=f, proj=f, campos=f, tx=0.5, ty=0.5, prefiltered=0, color=f, alpha=f, normal=f, refl_map=f,
+                 radii=f, refl=None, debug=0, stream=None)
+        a.update(kw)
+        rc = self.gsr.lib.gsr_surfel_forward_eval(*a.values())
+        return rc, self.gsr.lib.gsr_last_error().decode()
+
+
+def _refl_desc(_gsr, **kw):
+    f = 0x7f0000000000
+    d = dict(cam=f, cubemap=f, fail_value=f, L=16, cubemap_rgba=f, out_final=f, out_refl_color=f, out_normal_world=f, sort_keys=None,
+             scratch=None, scratch_floats=0, async_sort=0)
+    d.update(kw)
+    return ctypes.byref(_gsr.ReflForward(*d.values()))
+
+
+@pytest.mark.parametrize("case, expect", [
+    ("alloc", "invalid argument"),
+    ("out_color", "invalid argument"),
+    ("normal_without_refl", "out_normal_view"),
+    ("refl_sort_keys", "sort_keys"),
+    ("refl_scratch", "scratch"),
+    ("refl_incomplete", "reflection descriptor"),
+    ("means", "missing required input"),
+    ("sh_degree", "SH degree"),
+    ("shs_misaligned", "16-byte aligned"),
+])
+def test_eval_entry_refuses_bad_arguments_before_any_device_call(hip_lib_built, case, expect):
+    import _gsr
+    call = _Call()
+    f = call.fake
+    kw = {"alloc": dict(alloc=_gsr.ALLOC_FN()),        # (a NULL function pointer)
+          "out_color": dict(color=None),
+          "normal_without_refl": dict(normal=None),
+          "refl_sort_keys": dict(normal=None, refl=_refl_desc(_gsr, sort_keys=f)),
+          "refl_scratch": dict(refl=_refl_desc(_gsr, scratch=f, scratch_floats=1024)),
+          "refl_incomplete": dict(refl=_refl_desc(_gsr, out_final=None)),
+          "means": dict(means=None),
+          "sh_degree": dict(D=4),
+          "shs_misaligned": dict(shs=f + 4)}[case]
+    rc, msg = call(**kw)
+    assert rc == GSR_E_INVALID, (case, rc, msg)
+    assert expect in msg, (case, msg)
+    assert "gsr_surfel_forward_eval" in msg or case == "shs_misaligned", msg
+    assert call.allocs == [], "the entry asked for workspace before refusing"
+
+
+def _includes_reached(sources):
+    seen, todo = set(), list(sources)
+    while todo:
+        rel = todo.pop()
+        text = open(os.path.join(CSRC, rel)).read()
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, flags=re.M):
+            r = os.path.normpath(os.path.join(os.path.dirname(rel), inc))
+            if r not in seen:
+                assert os.path.exists(os.path.join(CSRC, r)), f"{rel} includes missing {inc}"
+                seen.add(r)
+                todo.append(r)
+    return seen
+
+
+def test_build_digest_covers_every_local_include():
+    import sys
+    sys.path.insert(0, CSRC)
+    import build
+    reached = _includes_reached(build.SOURCES)
+    assert "gsr_refl.hpp" in reached and os.path.normpath("../../include/gsr_hip.h") in reached
+    inputs = {os.path.normpath(p) for p in build.digest_inputs()}
+    missing = sorted(reached - inputs)
+    assert not missing, f"headers outside the build digest: {missing}"
