@@ -174,7 +174,6 @@ static size_t depth_sort_bytes(size_t P) {
 	                                            (unsigned long long*)nullptr, P, 0, 31, 0, false);
 	return std::max(c, d);
 }
-size_t scan_temp_bytes(size_t P) { return scan_part_bytes(P) + depth_sort_bytes(P); }
 size_t sort_temp_bytes(size_t R, int end_bit) {
 	size_t bytes = 0, pub = 0;
 	if (R <= SORT_MAX_ITEMS) {
@@ -193,7 +192,8 @@ size_t sort_temp_bytes(size_t R, int end_bit) {
 	return std::max(bytes, pub);
 }
 
-GeomState carve_geom(void* buf, size_t P, int rec_f4, int aux_floats, int acc_floats, size_t scan_bytes, size_t* total) {
+GeomState carve_geom(void* buf, size_t P, const WorkspaceLayout& layout, size_t* total) {
+	const size_t scan_bytes = scan_part_bytes(P), sort_bytes = depth_sort_bytes(P);
 	Carver c(buf);
 	GeomState g;
 	g.depths = c.take<float>(P);
@@ -201,32 +201,44 @@ GeomState carve_geom(void* buf, size_t P, int rec_f4, int aux_floats, int acc_fl
 	g.tiles_touched = c.take<uint32_t>(P);
 	g.point_offsets = c.take<uint32_t>(P);
 	g.clamped = c.take<uint8_t>(P);
-	g.rec = c.take<float4>(P * rec_f4);
+	g.rec = c.take<float4>(P * layout.rec_f4);
 	g.bbox = c.take<float4>(2 * P);
-	g.aux = c.take<float>(P * aux_floats);
-	g.acc = c.take<float>(P * acc_floats);
+	g.aux = c.take<float>(P * layout.aux_floats);
+	g.acc = c.take<float>(P * layout.acc_floats);
 	g.flags = c.take<int>(4);
 	g.depth_sorted = c.take<uint32_t>(P);
 	g.order = c.take<unsigned long long>(P);
 	g.emit_state_bytes = ((((P + 255) / 256 + 1) * sizeof(unsigned long long)) + 15) & ~(size_t)15;   // (enough for any EMIT_BLOCK >= 256)
 	g.emit_state = c.take<unsigned long long>(g.emit_state_bytes / sizeof(unsigned long long));
-	g.scan_temp = c.take<char>(scan_bytes);
-	g.scan_temp_bytes = scan_bytes;
-	g.depth_sort_temp = g.scan_temp ? static_cast<char*>(g.scan_temp) + scan_part_bytes(P) : nullptr;
-	g.depth_sort_bytes = depth_sort_bytes(P);
+	g.scan_temp = c.take<char>(scan_bytes + sort_bytes);
+	g.scan_temp_bytes = scan_bytes + sort_bytes;
+	g.depth_sort_temp = g.scan_temp ? static_cast<char*>(g.scan_temp) + scan_bytes : nullptr;
+	g.depth_sort_bytes = sort_bytes;
 	g.depth_sort_clear = P <= SORT_MAX_ITEMS ? onesweep_cleared_bytes<DEPTH_SORT_SHAPE>(P, 0u, DEPTH_KEY_BITS) : 0;
 	if (total) *total = c.size();
 	return g;
 }
-ImageState carve_image(void* buf, size_t HW, size_t tiles, int planes_T, int planes_n, size_t* total) {
+ImageState carve_image(void* buf, size_t HW, size_t tiles, const WorkspaceLayout& layout, size_t* total) {
 	Carver c(buf);
 	ImageState s;
 	s.ranges = c.take<uint2>(tiles);
-	s.final_T = c.take<float>(HW * planes_T);
-	s.n_contrib = c.take<uint32_t>(HW * planes_n);
+	s.final_T = c.take<float>(HW * layout.planes_T);
+	s.n_contrib = c.take<uint32_t>(HW * layout.planes_n);
 	s.tile_order = c.take<uint32_t>(tiles);
 	if (total) *total = c.size();
 	return s;
+}
+int forward_workspace(gsr_alloc_fn alloc, void* alloc_user, const WorkspaceLayout& layout, size_t P, size_t HW, size_t tiles, GeomState* geom,
+                      ImageState* img) {
+	size_t geom_bytes = 0, img_bytes = 0;
+	carve_geom(nullptr, P, layout, &geom_bytes);
+	carve_image(nullptr, HW, tiles, layout, &img_bytes);
+	void* gbuf = alloc(alloc_user, GSR_BUF_GEOM, geom_bytes);
+	void* ibuf = alloc(alloc_user, GSR_BUF_IMAGE, img_bytes);
+	if (!gbuf || !ibuf) { set_error("workspace allocation failed (%zu / %zu bytes)", geom_bytes, img_bytes); return GSR_E_ALLOC; }
+	*geom = carve_geom(gbuf, P, layout, nullptr);
+	*img = carve_image(ibuf, HW, tiles, layout, nullptr);
+	return 0;
 }
 BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_bytes, size_t* total, bool blend_masks) {
 	Carver c(buf);
@@ -795,10 +807,10 @@ extern "C" int gsr_debug_fetch(int variant, const char* name, int P, int R, int 
 	hipStream_t stream = (hipStream_t)stream_;
 	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
 	const size_t HW = (size_t)width * height, tiles = (size_t)tiles_x * tiles_y;
-	const int rec_f4 = variant == 0 ? 5 : 4;
-	const int stride = rec_f4 * 4;
-	GeomState g = carve_geom((void*)geom_buffer, P, rec_f4, 0, variant == 0 ? 20 : 16, scan_temp_bytes(P), nullptr);
-	ImageState im = carve_image((void*)image_buffer, HW, tiles, variant == 0 ? 3 : 1, variant == 0 ? 2 : 1, nullptr);
+	const WorkspaceLayout& layout = variant == 0 ? SURFEL_LAYOUT : GAUSS_LAYOUT;
+	const int stride = layout.rec_f4 * 4;
+	GeomState g = carve_geom((void*)geom_buffer, P, layout, nullptr);
+	ImageState im = carve_image((void*)image_buffer, HW, tiles, layout, nullptr);
 	BinningState b = carve_binning((void*)binning_buffer, R, tiles, 0, nullptr);
 	auto d2d = [&](const void* src, size_t bytes) -> int {
 		if (bytes == 0) return 0;
@@ -854,8 +866,8 @@ extern "C" int gsr_debug_fetch(int variant, const char* name, int P, int R, int 
 		return 0;
 	}
 	if (n == "ranges") return d2d(im.ranges, tiles * 8);
-	if (n == "final_T") return d2d(im.final_T, HW * 4 * (variant == 0 ? 3 : 1));
-	if (n == "n_contrib") return d2d(im.n_contrib, HW * 4 * (variant == 0 ? 2 : 1));
+	if (n == "final_T") return d2d(im.final_T, HW * 4 * layout.planes_T);
+	if (n == "n_contrib") return d2d(im.n_contrib, HW * 4 * layout.planes_n);
 	set_error("gsr_debug_fetch: unknown array '%s'", name);
 	return GSR_E_INVALID;
 }

@@ -14,8 +14,6 @@
 
 namespace gsr {
 
-#define G_REC_F4 4
-#define G_ACC_F 16
 // accumulator slots (floats) of the backward tile kernel / per-Gaussian backward
 #define GA_COLOR 0
 #define GA_NORMAL 3
@@ -772,20 +770,11 @@ extern "C" int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, in
 		set_error("gsr_gauss_forward: missing required input pointer");
 		return GSR_E_INVALID;
 	}
-	if (D < 0 || D > 3 || (shs && (D + 1) * (D + 1) > M)) { set_error("gsr_gauss_forward: SH degree %d not supported with M=%d", D, M); return GSR_E_INVALID; }
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(shs, "shs (rows of a multiple of 16 bytes)");
+	if (const int rc = check_sh_input("gsr_gauss_forward", D, M, shs); rc < 0) return rc;
 	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
 	const int ntiles = tiles_x * tiles_y;
-
-	size_t geom_bytes = 0, img_bytes = 0;
-	const size_t scan_bytes = scan_temp_bytes(P);
-	carve_geom(nullptr, P, G_REC_F4, 0, G_ACC_F, scan_bytes, &geom_bytes);
-	carve_image(nullptr, HW, ntiles, 1, 1, &img_bytes);
-	void* gbuf = alloc(alloc_user, GSR_BUF_GEOM, geom_bytes);
-	void* ibuf = alloc(alloc_user, GSR_BUF_IMAGE, img_bytes);
-	if (!gbuf || !ibuf) { set_error("workspace allocation failed (%zu / %zu bytes)", geom_bytes, img_bytes); return GSR_E_ALLOC; }
-	GeomState geom = carve_geom(gbuf, P, G_REC_F4, 0, G_ACC_F, scan_bytes, nullptr);
-	ImageState img = carve_image(ibuf, HW, ntiles, 1, 1, nullptr);
+	GeomState geom; ImageState img;
+	if (const int rc = forward_workspace(alloc, alloc_user, GAUSS_LAYOUT, P, HW, ntiles, &geom, &img); rc < 0) return rc;
 
 	if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));   // the flag is only written and read then
 	const GaussCam cam = make_cam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
@@ -840,11 +829,11 @@ extern "C" int gsr_gauss_backward_accum(int P, int D, int M, int R, const float*
 	const size_t HW = (size_t)width * height;
 	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
 	const int ntiles = tiles_x * tiles_y;
-	GeomState geom = carve_geom(geom_buffer, P, G_REC_F4, 0, G_ACC_F, scan_temp_bytes(P), nullptr);
-	ImageState img = carve_image(image_buffer, HW, ntiles, 1, 1, nullptr);
+	GeomState geom = carve_geom(geom_buffer, P, GAUSS_LAYOUT, nullptr);
+	ImageState img = carve_image(image_buffer, HW, ntiles, GAUSS_LAYOUT, nullptr);
 	BinningState bin = carve_binning(binning_buffer, R, ntiles, 0, nullptr);
 
-	GSR_HIP_CHECK(hipMemsetAsync(geom.acc, 0, (size_t)P * G_ACC_F * sizeof(float), stream));
+	GSR_HIP_CHECK(hipMemsetAsync(geom.acc, 0, (size_t)P * GAUSS_LAYOUT.acc_floats * sizeof(float), stream));
 	if (R > 0) {
 		const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
 		{

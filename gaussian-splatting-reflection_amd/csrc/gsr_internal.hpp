@@ -116,13 +116,42 @@ struct BinningState {
 	size_t sort_temp_bytes;
 };
 
-GeomState carve_geom(void* buf, size_t P, int rec_f4, int aux_floats, int acc_floats, size_t scan_temp_bytes, size_t* total);
-ImageState carve_image(void* buf, size_t HW, size_t tiles, int planes_T, int planes_n, size_t* total);
+// What a variant keeps in the geometry and image buffers.  The forward carves its buffers with it and the backward and gsr_debug_fetch
+// carve the same buffers again with it: one description, so that they read at the offsets the forward wrote at.
+// (the kernels size their records and accumulator slabs with these)
+#define S_REC_F4 5
+#define S_ACC_F 20
+#define G_REC_F4 4
+#define G_ACC_F 16
+struct WorkspaceLayout {
+	int rec_f4, aux_floats, acc_floats;   // per Gaussian: float4 of the render record, floats of GeomState::aux and of the backward accumulator
+	int planes_T, planes_n;               // per pixel: final_T and n_contrib planes
+	// for a forward that no backward follows: no accumulator, no final_T / n_contrib planes
+	constexpr WorkspaceLayout inference() const { return {rec_f4, aux_floats, 0, 0, 0}; }
+};
+constexpr WorkspaceLayout SURFEL_LAYOUT{S_REC_F4, 0, S_ACC_F, 3, 2};
+constexpr WorkspaceLayout GAUSS_LAYOUT{G_REC_F4, 0, G_ACC_F, 1, 1};
+
+GeomState carve_geom(void* buf, size_t P, const WorkspaceLayout& layout, size_t* total);
+ImageState carve_image(void* buf, size_t HW, size_t tiles, const WorkspaceLayout& layout, size_t* total);
 BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_temp_bytes, size_t* total, bool blend_masks = true);
+// The geometry and image buffers of a forward: sized, requested through `alloc` and carved.  0 or GSR_E_ALLOC.
+int forward_workspace(gsr_alloc_fn alloc, void* alloc_user, const WorkspaceLayout& layout, size_t P, size_t HW, size_t tiles, GeomState* geom,
+                      ImageState* img);
+
+// The check of the SH input every forward makes: degree 0..3 with (D+1)^2 <= M coefficients per row, and rows of a multiple of 16 bytes
+// 16-byte aligned (their float4 loads).  `entry` names the caller in the message.
+static inline int check_sh_input(const char* entry, int D, int M, const float* shs) {
+	if (D < 0 || D > 3 || (shs && (D + 1) * (D + 1) > M)) { set_error("%s: SH degree %d not supported with M=%d", entry, D, M); return GSR_E_INVALID; }
+	if (shs && ((M * 3) & 3) == 0 && misaligned16(shs)) {
+		set_error("%s: shs (rows of a multiple of 16 bytes) must be 16-byte aligned (float4 accesses); got %p", entry, (const void*)shs);
+		return GSR_E_INVALID;
+	}
+	return 0;
+}
 
 int option_cull();   // 1 (default): per-wave bounding-box culling in the tile kernels; 0: evaluate every list entry
 int option_dev();    // development ablation bits (0 in production): 1 = skip the gradient atomics of the surfel backward
-size_t scan_temp_bytes(size_t P);
 size_t sort_temp_bytes(size_t R, int end_bit);
 int run_tile_order(const ImageState& img, size_t tiles, hipStream_t stream);
 uint32_t higher_msb(uint32_t n);

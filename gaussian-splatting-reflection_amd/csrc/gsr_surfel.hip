@@ -14,8 +14,6 @@
 
 namespace gsr {
 
-#define S_REC_F4 5
-#define S_ACC_F 20
 #define SA_COLOR 0
 #define SA_REFL 3
 #define SA_NORMAL 4
@@ -1213,6 +1211,103 @@ static SurfelCam make_scam(const float* view, const float* proj, const float* ca
 	return c;
 }
 
+// The checks both surfel forwards make, before their first allocation or device call.  `entry` names the caller in the message.
+static int check_refl_descriptor(const char* entry, const gsr_refl_forward* refl) {
+	if (!refl) return 0;
+	if (!refl->cam || !refl->cubemap || !refl->fail_value || refl->L == 0 || !refl->cubemap_rgba || ((uintptr_t)refl->cubemap_rgba & 15) != 0 ||
+	    !refl->out_final || !refl->out_refl_color || !refl->out_normal_world) {
+		set_error("%s: incomplete reflection descriptor (cam, cubemap, fail_value, L, 16-byte aligned cubemap_rgba and the three outputs are required)", entry);
+		return GSR_E_INVALID;
+	}
+	if ((size_t)6 * refl->L * refl->L >= 0xFFFFFFFFull) { set_error("%s: cubemap too large", entry); return GSR_E_INVALID; }
+	return 0;
+}
+static int check_surfel_inputs(const char* entry, int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                               const float* refl_strengths, const float* opacities, const float* scales, const float* rotations,
+                               const float* transMat_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int* radii) {
+	if (P == 0) return 0;    // an empty scene reads none of them
+	if (!means3D || !opacities || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii || (!shs && !colors_precomp) ||
+	    ((!scales || !rotations) && !transMat_precomp)) {
+		set_error("%s: missing required input pointer", entry);
+		return GSR_E_INVALID;
+	}
+	return check_sh_input(entry, D, M, shs);
+}
+
+// The key sort of the reflection backward that the training forward starts when the descriptor hands it sort_keys and scratch; 0 otherwise.
+static int early_key_sort(const gsr_refl_forward* refl, int width, int height, hipStream_t stream) {
+	if (!refl || !refl->sort_keys || !refl->scratch) return 0;
+	return refl_sort_keys_early(refl->L, width, height, refl->scratch, refl->scratch_floats, refl->sort_keys, refl->async_sort, stream);
+}
+
+// Both surfel forwards after their checks.  TRAIN: gsr_surfel_forward_refl, which writes out_others, gaussian_weights and everything the
+// backward reads; otherwise gsr_surfel_forward_eval, which writes out_alpha and out_normal_view (NULL with refl: not stored) instead and
+// takes NULL for env_scope_mask, out_others and gaussian_weights.
+template <bool TRAIN>
+static int surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,
+                          const float* means3D, const uint8_t* env_scope_mask, const float* shs, const float* colors_precomp,
+                          const float* refl_strengths, const float* opacities, const float* scales, float scale_modifier,
+                          const float* rotations, const float* transMat_precomp, const float* viewmatrix, const float* projmatrix,
+                          const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_others,
+                          float* out_alpha, float* out_normal_view, float* out_refl_strength_map, int* radii, float* gaussian_weights,
+                          const gsr_refl_forward* refl, int debug, hipStream_t stream) {
+	const size_t HW = (size_t)width * height;
+	if (P == 0) {
+		// zero planes, and with refl the stand-alone pixel pass over them: the same arithmetic on an empty scene
+		float* normal = TRAIN ? out_others + 2 * HW : out_normal_view;
+		if (!normal) {   // (the pixel pass reads the normal planes)
+			normal = static_cast<float*>(alloc(alloc_user, GSR_BUF_IMAGE, HW * 3 * 4));
+			if (!normal) { set_error("workspace allocation failed (%zu bytes)", HW * 3 * 4); return GSR_E_ALLOC; }
+		}
+		GSR_HIP_CHECK(hipMemsetAsync(out_color, 0, HW * 3 * 4, stream));
+		if (TRAIN) {
+			GSR_HIP_CHECK(hipMemsetAsync(out_others, 0, HW * 8 * 4, stream));
+		} else {
+			GSR_HIP_CHECK(hipMemsetAsync(out_alpha, 0, HW * 4, stream));
+			GSR_HIP_CHECK(hipMemsetAsync(normal, 0, HW * 3 * 4, stream));
+		}
+		GSR_HIP_CHECK(hipMemsetAsync(out_refl_strength_map, 0, HW * 4, stream));
+		if (refl)
+			return gsr_deferred_reflection_forward_keys(normal, out_color, out_refl_strength_map, refl->cam, refl->cubemap, refl->fail_value, refl->L,
+			                                            width, height, refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->cubemap_rgba,
+			                                            refl->sort_keys, stream) < 0 ? GSR_E_HIP : 0;
+		return 0;
+	}
+	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
+	const int ntiles = tiles_x * tiles_y;
+	GeomState geom; ImageState img;
+	if (const int rc = forward_workspace(alloc, alloc_user, TRAIN ? SURFEL_LAYOUT : SURFEL_LAYOUT.inference(), P, HW, ntiles, &geom, &img); rc < 0) return rc;
+
+	if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));   // the flag is only written and read then
+	const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
+	CubemapInterleave ci{nullptr, nullptr, 0u, 1u};
+	SurfelReflFwd rf{};
+	if (refl) {
+		ci = CubemapInterleave{refl->cubemap, reinterpret_cast<float4*>(refl->cubemap_rgba), 6u * refl->L * refl->L, refl->L * refl->L};
+		rf = SurfelReflFwd{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
+		                   refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->sort_keys};
+	}
+{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<TRAIN><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
+	                                                                     transMat_precomp, colors_precomp, refl_strengths, env_scope_mask, cam, radii, geom,
+	                                                                     tiles_x, tiles_y, prefiltered, gaussian_weights, ci); }
+	GSR_LAUNCH_CHECK(debug, stream);
+
+	BinningState bin;
+	const int R = run_binning(alloc, alloc_user, P, tiles_x, tiles_y, geom, img, &bin, prefiltered, debug, stream, TRAIN);
+	if (R < 0) return R;
+
+{ StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
+	const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
+	const auto args = [&] { if constexpr (TRAIN) return rf; else return SurfelEvalFwd{rf, out_alpha, out_normal_view}; }();
+	auto render = refl ? surfel_render_fwd_wave_kernel<true, TRAIN> : surfel_render_fwd_wave_kernel<false, TRAIN>;
+	render<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(),
+	                                  background, TRAIN ? img.final_T : nullptr, TRAIN ? img.n_contrib : nullptr, out_color, out_others,
+	                                  out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, args); }
+	GSR_LAUNCH_CHECK(debug, stream);
+	const int rc = TRAIN ? early_key_sort(refl, width, height, stream) : 0;
+	return rc < 0 ? rc : R;
+}
+
 extern "C" int gsr_surfel_forward_refl(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,
                                   const float* means3D, const uint8_t* env_scope_mask, const float* shs, const float* colors_precomp,
                                   const float* refl_strengths, const float* opacities, const float* scales, float scale_modifier,
@@ -1220,82 +1315,18 @@ extern "C" int gsr_surfel_forward_refl(gsr_alloc_fn alloc, void* alloc_user, int
                                   const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_others,
                                   float* out_refl_strength_map, int* radii, float* gaussian_weights, const gsr_refl_forward* refl, int debug,
                                   void* stream_) {
-	hipStream_t stream = (hipStream_t)stream_;
 	if (!alloc || P < 0 || width <= 0 || height <= 0 || !background || !out_color || !out_others || !out_refl_strength_map) {
 		set_error("gsr_surfel_forward: invalid argument");
 		return GSR_E_INVALID;
 	}
-	if (refl && (!refl->cam || !refl->cubemap || !refl->fail_value || refl->L == 0 || !refl->cubemap_rgba || ((uintptr_t)refl->cubemap_rgba & 15) != 0 ||
-	             !refl->out_final || !refl->out_refl_color || !refl->out_normal_world)) {
-		set_error("gsr_surfel_forward_refl: incomplete reflection descriptor (cam, cubemap, fail_value, L, 16-byte aligned cubemap_rgba and the three outputs are required)");
-		return GSR_E_INVALID;
-	}
-	const size_t HW = (size_t)width * height;
-	if (P == 0) {
-		GSR_HIP_CHECK(hipMemsetAsync(out_color, 0, HW * 3 * 4, stream));
-		GSR_HIP_CHECK(hipMemsetAsync(out_others, 0, HW * 8 * 4, stream));
-		GSR_HIP_CHECK(hipMemsetAsync(out_refl_strength_map, 0, HW * 4, stream));
-		if (refl)    // an empty scene through the stand-alone pixel pass: the same arithmetic on zero planes
-			return gsr_deferred_reflection_forward_keys(out_others + 2 * HW, out_color, out_refl_strength_map, refl->cam, refl->cubemap, refl->fail_value, refl->L,
-			                                            width, height, refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->cubemap_rgba,
-			                                            refl->sort_keys, stream_) < 0 ? GSR_E_HIP : 0;
-		return 0;
-	}
-	if (!means3D || !opacities || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii || !gaussian_weights ||
-	    (!shs && !colors_precomp) || ((!scales || !rotations) && !transMat_precomp)) {
-		set_error("gsr_surfel_forward: missing required input pointer");
-		return GSR_E_INVALID;
-	}
-	if (D < 0 || D > 3 || (shs && (D + 1) * (D + 1) > M)) { set_error("gsr_surfel_forward: SH degree %d not supported with M=%d", D, M); return GSR_E_INVALID; }
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(shs, "shs (rows of a multiple of 16 bytes)");
-	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
-	const int ntiles = tiles_x * tiles_y;
-
-	size_t geom_bytes = 0, img_bytes = 0;
-	const size_t scan_bytes = scan_temp_bytes(P);
-	carve_geom(nullptr, P, S_REC_F4, 0, S_ACC_F, scan_bytes, &geom_bytes);
-	carve_image(nullptr, HW, ntiles, 3, 2, &img_bytes);
-	void* gbuf = alloc(alloc_user, GSR_BUF_GEOM, geom_bytes);
-	void* ibuf = alloc(alloc_user, GSR_BUF_IMAGE, img_bytes);
-	if (!gbuf || !ibuf) { set_error("workspace allocation failed (%zu / %zu bytes)", geom_bytes, img_bytes); return GSR_E_ALLOC; }
-	GeomState geom = carve_geom(gbuf, P, S_REC_F4, 0, S_ACC_F, scan_bytes, nullptr);
-	ImageState img = carve_image(ibuf, HW, ntiles, 3, 2, nullptr);
-
-	if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));   // the flag is only written and read then
-	const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
-	CubemapInterleave ci{nullptr, nullptr, 0u, 1u};
-	if (refl) {
-		if ((size_t)6 * refl->L * refl->L >= 0xFFFFFFFFull) { set_error("gsr_surfel_forward_refl: cubemap too large"); return GSR_E_INVALID; }
-		ci = CubemapInterleave{refl->cubemap, reinterpret_cast<float4*>(refl->cubemap_rgba), 6u * refl->L * refl->L, refl->L * refl->L};
-	}
-{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<true><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
-	                                                              transMat_precomp, colors_precomp, refl_strengths, env_scope_mask, cam, radii, geom,
-	                                                              tiles_x, tiles_y, prefiltered, gaussian_weights, ci); }
-	GSR_LAUNCH_CHECK(debug, stream);
-
-	BinningState bin;
-	const int R = run_binning(alloc, alloc_user, P, tiles_x, tiles_y, geom, img, &bin, prefiltered, debug, stream);
-	if (R < 0) return R;
-
-{ StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
-	const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
-	if (refl) {
-		const SurfelReflFwd rf{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
-		                       refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->sort_keys};
-		surfel_render_fwd_wave_kernel<true, true><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
-		                                                               option_cull(), background, img.final_T, img.n_contrib, out_color, out_others,
-		                                                               out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, rf);
-	} else {
-		surfel_render_fwd_wave_kernel<false, true><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
-		                                                                option_cull(), background, img.final_T, img.n_contrib, out_color, out_others,
-		                                                                out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, SurfelReflFwd{});
-	} }
-	GSR_LAUNCH_CHECK(debug, stream);
-	if (refl && refl->sort_keys && refl->scratch) {
-		const int rc = refl_sort_keys_early(refl->L, width, height, refl->scratch, refl->scratch_floats, refl->sort_keys, refl->async_sort, stream);
-		if (rc < 0) return rc;
-	}
-	return R;
+	if (P > 0 && !gaussian_weights) { set_error("gsr_surfel_forward: missing required input pointer"); return GSR_E_INVALID; }
+	if (const int rc = check_refl_descriptor("gsr_surfel_forward_refl", refl); rc < 0) return rc;
+	if (const int rc = check_surfel_inputs("gsr_surfel_forward", P, D, M, means3D, shs, colors_precomp, refl_strengths, opacities, scales, rotations,
+	                                       transMat_precomp, viewmatrix, projmatrix, cam_pos, radii); rc < 0) return rc;
+	return surfel_forward<true>(alloc, alloc_user, P, D, M, background, width, height, means3D, env_scope_mask, shs, colors_precomp, refl_strengths,
+	                            opacities, scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+	                            prefiltered, out_color, out_others, nullptr, nullptr, out_refl_strength_map, radii, gaussian_weights, refl, debug,
+	                            (hipStream_t)stream_);
 }
 
 extern "C" int gsr_surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,
@@ -1316,8 +1347,6 @@ extern "C" int gsr_surfel_forward_eval(gsr_alloc_fn alloc, void* alloc_user, int
                                        float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_alpha,
                                        float* out_normal_view, float* out_refl_strength_map, int* radii, const gsr_refl_forward* refl,
                                        int debug, void* stream_) {
-	hipStream_t stream = (hipStream_t)stream_;
-	// every check comes before the first device call
 	if (!alloc || P < 0 || width <= 0 || height <= 0 || !background || !out_color || !out_alpha || !out_refl_strength_map) {
 		set_error("gsr_surfel_forward_eval: invalid argument (alloc, P >= 0, width, height, background, out_color, out_alpha, out_refl_strength_map)");
 		return GSR_E_INVALID;
@@ -1327,81 +1356,12 @@ extern "C" int gsr_surfel_forward_eval(gsr_alloc_fn alloc, void* alloc_user, int
 		set_error("gsr_surfel_forward_eval: refl->sort_keys and refl->scratch must be NULL (the eval forward has no backward)");
 		return GSR_E_INVALID;
 	}
-	if (refl && (!refl->cam || !refl->cubemap || !refl->fail_value || refl->L == 0 || !refl->cubemap_rgba || ((uintptr_t)refl->cubemap_rgba & 15) != 0 ||
-	             !refl->out_final || !refl->out_refl_color || !refl->out_normal_world)) {
-		set_error("gsr_surfel_forward_eval: incomplete reflection descriptor (cam, cubemap, fail_value, L, 16-byte aligned cubemap_rgba and the three outputs are required)");
-		return GSR_E_INVALID;
-	}
-	if (refl && (size_t)6 * refl->L * refl->L >= 0xFFFFFFFFull) { set_error("gsr_surfel_forward_eval: cubemap too large"); return GSR_E_INVALID; }
-	if (P > 0) {
-		if (!means3D || !opacities || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii || (!shs && !colors_precomp) ||
-		    ((!scales || !rotations) && !transMat_precomp)) {
-			set_error("gsr_surfel_forward_eval: missing required input pointer");
-			return GSR_E_INVALID;
-		}
-		if (D < 0 || D > 3 || (shs && (D + 1) * (D + 1) > M)) { set_error("gsr_surfel_forward_eval: SH degree %d not supported with M=%d", D, M); return GSR_E_INVALID; }
-		if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(shs, "shs (rows of a multiple of 16 bytes)");
-	}
-	const size_t HW = (size_t)width * height;
-	if (P == 0) {
-		float* normal = out_normal_view;
-		if (!normal) {   // the stand-alone pixel pass below reads the normal planes
-			normal = static_cast<float*>(alloc(alloc_user, GSR_BUF_IMAGE, HW * 3 * 4));
-			if (!normal) { set_error("workspace allocation failed (%zu bytes)", HW * 3 * 4); return GSR_E_ALLOC; }
-		}
-		GSR_HIP_CHECK(hipMemsetAsync(out_color, 0, HW * 3 * 4, stream));
-		GSR_HIP_CHECK(hipMemsetAsync(out_alpha, 0, HW * 4, stream));
-		GSR_HIP_CHECK(hipMemsetAsync(normal, 0, HW * 3 * 4, stream));
-		GSR_HIP_CHECK(hipMemsetAsync(out_refl_strength_map, 0, HW * 4, stream));
-		if (refl)    // an empty scene through the stand-alone pixel pass, as gsr_surfel_forward_refl does (no keys)
-			return gsr_deferred_reflection_forward_keys(normal, out_color, out_refl_strength_map, refl->cam, refl->cubemap, refl->fail_value, refl->L,
-			                                            width, height, refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->cubemap_rgba,
-			                                            nullptr, stream_) < 0 ? GSR_E_HIP : 0;
-		return 0;
-	}
-	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
-	const int ntiles = tiles_x * tiles_y;
-
-	// workspace: no backward accumulator, no final_T / n_contrib planes, no blend masks
-	size_t geom_bytes = 0, img_bytes = 0;
-	const size_t scan_bytes = scan_temp_bytes(P);
-	carve_geom(nullptr, P, S_REC_F4, 0, 0, scan_bytes, &geom_bytes);
-	carve_image(nullptr, HW, ntiles, 0, 0, &img_bytes);
-	void* gbuf = alloc(alloc_user, GSR_BUF_GEOM, geom_bytes);
-	void* ibuf = alloc(alloc_user, GSR_BUF_IMAGE, img_bytes);
-	if (!gbuf || !ibuf) { set_error("workspace allocation failed (%zu / %zu bytes)", geom_bytes, img_bytes); return GSR_E_ALLOC; }
-	GeomState geom = carve_geom(gbuf, P, S_REC_F4, 0, 0, scan_bytes, nullptr);
-	ImageState img = carve_image(ibuf, HW, ntiles, 0, 0, nullptr);
-
-	if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));
-	const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
-	CubemapInterleave ci{nullptr, nullptr, 0u, 1u};
-	if (refl) ci = CubemapInterleave{refl->cubemap, reinterpret_cast<float4*>(refl->cubemap_rgba), 6u * refl->L * refl->L, refl->L * refl->L};
-{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<false><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
-	                                                                     transMat_precomp, colors_precomp, refl_strengths, nullptr, cam, radii, geom,
-	                                                                     tiles_x, tiles_y, prefiltered, nullptr, ci); }
-	GSR_LAUNCH_CHECK(debug, stream);
-
-	BinningState bin;
-	const int R = run_binning(alloc, alloc_user, P, tiles_x, tiles_y, geom, img, &bin, prefiltered, debug, stream, false);
-	if (R < 0) return R;
-
-{ StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
-	const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
-	SurfelEvalFwd ev{SurfelReflFwd{}, out_alpha, out_normal_view};
-	if (refl) {
-		ev.refl = SurfelReflFwd{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
-		                        refl->out_final, refl->out_refl_color, refl->out_normal_world, nullptr};
-		surfel_render_fwd_wave_kernel<true, false><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec,
-		                                                                      geom.bbox, option_cull(), background, nullptr, nullptr, out_color, nullptr,
-		                                                                      out_refl_strength_map, nullptr, nullptr, 0, ev);
-	} else {
-		surfel_render_fwd_wave_kernel<false, false><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec,
-		                                                                       geom.bbox, option_cull(), background, nullptr, nullptr, out_color, nullptr,
-		                                                                       out_refl_strength_map, nullptr, nullptr, 0, ev);
-	} }
-	GSR_LAUNCH_CHECK(debug, stream);
-	return R;
+	if (const int rc = check_refl_descriptor("gsr_surfel_forward_eval", refl); rc < 0) return rc;
+	if (const int rc = check_surfel_inputs("gsr_surfel_forward_eval", P, D, M, means3D, shs, colors_precomp, refl_strengths, opacities, scales, rotations,
+	                                       transMat_precomp, viewmatrix, projmatrix, cam_pos, radii); rc < 0) return rc;
+	return surfel_forward<false>(alloc, alloc_user, P, D, M, background, width, height, means3D, nullptr, shs, colors_precomp, refl_strengths, opacities,
+	                             scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
+	                             out_color, nullptr, out_alpha, out_normal_view, out_refl_strength_map, radii, nullptr, refl, debug, (hipStream_t)stream_);
 }
 
 extern "C" int gsr_surfel_backward_ex(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
@@ -1428,11 +1388,11 @@ extern "C" int gsr_surfel_backward_ex(int P, int D, int M, int R, const float* b
 	const size_t HW = (size_t)width * height;
 	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
 	const int ntiles = tiles_x * tiles_y;
-	GeomState geom = carve_geom(geom_buffer, P, S_REC_F4, 0, S_ACC_F, scan_temp_bytes(P), nullptr);
-	ImageState img = carve_image(image_buffer, HW, ntiles, 3, 2, nullptr);
+	GeomState geom = carve_geom(geom_buffer, P, SURFEL_LAYOUT, nullptr);
+	ImageState img = carve_image(image_buffer, HW, ntiles, SURFEL_LAYOUT, nullptr);
 	BinningState bin = carve_binning(binning_buffer, R, ntiles, 0, nullptr);
 
-	GSR_HIP_CHECK(hipMemsetAsync(geom.acc, 0, (size_t)P * S_ACC_F * sizeof(float), stream));
+	GSR_HIP_CHECK(hipMemsetAsync(geom.acc, 0, (size_t)P * SURFEL_LAYOUT.acc_floats * sizeof(float), stream));
 	if (R > 0) {
 		// a key sort of the reflection backward on the library's side stream must have reached its last pass before this kernel takes
 		// every wave slot of the chip (side_gate_wait, gsr_cubemap.hip); nothing pending: no wait

@@ -19,6 +19,46 @@ NUM_CHANNELS = 3
 SINKABLE = frozenset(("means3D", "shs", "opacities", "scales", "rotations", "refl_strengths"))   # gradients a grad_sink may take
 
 
+def _forward_inputs(background, means3D, colors, refl_strengths, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix, sh,
+                    campos):
+    """The input checks of both forwards; returns the contiguous float32 inputs in the order of the C entries (background, means3D, sh,
+    colors, refl_strengths, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix, campos) and M."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    for name, t in (("background", background), ("means3D", means3D), ("colors", colors), ("refl_strengths", refl_strengths),
+                    ("opacity", opacity), ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
+                    ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh), ("campos", campos)):
+        require_cuda(t, name)
+    keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh"), f32c(colors, "colors"),
+            f32c(refl_strengths, "refl_strengths"), f32c(opacity, "opacity"), f32c(scales, "scales"), f32c(rotations, "rotations"),
+            f32c(transMat_precomp, "transMat_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"),
+            f32c(campos, "campos")]
+    return keep, (sh.size(1) if sh.numel() != 0 else 0)
+
+
+def _refl_forward(refl, H, W, dev, keys):
+    """The reflection descriptor argument of a `refl` dict: (ctypes argument, tensors it points into, (final, refl_color, normal_world,
+    cubemap_rgba, sort_keys | None, scratch | None)); (None, [], ()) for refl None.  The caller holds the tensors until the call returns.
+    keys: honour refl["keys"] and refl["early_sort"]."""
+    if refl is None:
+        return None, [], ()
+    fopts = dict(dtype=torch.float32, device=dev)
+    cm, fv, cam = f32c(refl["cubemap"], "cubemap"), f32c(refl["fail_value"], "fail_value"), f32c(refl["cam"], "cam")
+    if cm.dim() != 4 or cm.shape[0] != 6 or cm.shape[1] != 3 or cm.shape[2] != cm.shape[3]:
+        raise RuntimeError("rasterize + reflect: the cubemap must be (6, 3, L, L)")
+    L = int(cm.shape[2])
+    final, refl_color, normal_world = (torch.empty((3, H, W), **fopts) for _ in range(3))
+    rgba = torch.empty(6 * L * L * 4, **fopts)
+    sort_keys = torch.empty(H * W, dtype=torch.int32, device=dev) if keys and refl.get("keys") else None
+    # early_sort: the forward also sorts the keys (on the side stream) into the scratch the reflection backward will use
+    scratch = None
+    if sort_keys is not None and refl.get("early_sort"):
+        scratch = torch.empty(int(lib.gsr_deferred_reflection_scratch_floats(L, W, H, 1)), **fopts)
+    desc = _gsr.ReflForward(ptr(cam), ptr(cm), ptr(fv), L, ptr(rgba), ptr(final), ptr(refl_color), ptr(normal_world), ptr(sort_keys), ptr(scratch),
+                            scratch.numel() if scratch is not None else 0, 1 if scratch is not None else 0)
+    return ctypes.byref(desc), [cm, fv, cam, rgba], (final, refl_color, normal_world, rgba, sort_keys, scratch)
+
+
 def rasterize_gaussians(background, means3D, env_scope_mask, colors, refl_strengths, opacity, scales, rotations, scale_modifier,
                         transMat_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                         prefiltered, debug, *, refl=None):
@@ -33,12 +73,14 @@ def rasterize_gaussians(background, means3D, env_scope_mask, colors, refl_streng
                                                       float(scale_modifier), transMat_precomp, viewmatrix, projmatrix, float(tan_fovx),
                                                       float(tan_fovy), int(image_height), int(image_width), sh, int(degree), campos,
                                                       bool(prefiltered), bool(debug))
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    for name, t in (("background", background), ("means3D", means3D), ("colors", colors), ("refl_strengths", refl_strengths),
-                    ("opacity", opacity), ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
-                    ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh), ("campos", campos)):
-        require_cuda(t, name)
+    keep, M = _forward_inputs(background, means3D, colors, refl_strengths, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix,
+                              sh, campos)
+    bg, m3, shc, col, rfl, opa, sca, rot, tmp, vm, pm, cp = keep
+    mask = env_scope_mask
+    if mask is not None and mask.numel() != 0:
+        if mask.dtype != torch.bool:
+            raise RuntimeError(f"expected scalar type Bool but found {mask.dtype} for env_scope_mask")
+        mask = mask.contiguous()
     P, H, W = means3D.size(0), int(image_height), int(image_width)
     dev = means3D.device
     fopts = dict(dtype=torch.float32, device=dev)
@@ -48,40 +90,13 @@ def rasterize_gaussians(background, means3D, env_scope_mask, colors, refl_streng
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     gaussian_weights = torch.empty((P,), **fopts)
     ws = _gsr.Workspace(dev)
-    M = sh.size(1) if sh.numel() != 0 else 0
-    mask = env_scope_mask
-    if mask is not None and mask.numel() != 0:
-        if mask.dtype != torch.bool:
-            raise RuntimeError(f"expected scalar type Bool but found {mask.dtype} for env_scope_mask")
-        mask = mask.contiguous()
-    keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh"), f32c(colors, "colors"),
-            f32c(refl_strengths, "refl_strengths"), f32c(opacity, "opacity"), f32c(scales, "scales"), f32c(rotations, "rotations"),
-            f32c(transMat_precomp, "transMat_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"),
-            f32c(campos, "campos")]
-    bg, m3, shc, col, rfl, opa, sca, rot, tmp, vm, pm, cp = keep
-    desc, extra = None, ()
-    if refl is not None:
-        cm, fv, cam = f32c(refl["cubemap"], "cubemap"), f32c(refl["fail_value"], "fail_value"), f32c(refl["cam"], "cam")
-        if cm.dim() != 4 or cm.shape[0] != 6 or cm.shape[1] != 3 or cm.shape[2] != cm.shape[3]:
-            raise RuntimeError("rasterize + reflect: the cubemap must be (6, 3, L, L)")
-        L = int(cm.shape[2])
-        final, refl_color, normal_world = (torch.empty((3, H, W), **fopts) for _ in range(3))
-        rgba = torch.empty(6 * L * L * 4, **fopts)
-        keys = torch.empty(H * W, dtype=torch.int32, device=dev) if refl.get("keys") else None
-        # early_sort: the forward also sorts the keys (on the side stream) into the scratch the reflection backward will use
-        scratch = None
-        if keys is not None and refl.get("early_sort"):
-            scratch = torch.empty(int(lib.gsr_deferred_reflection_scratch_floats(L, W, H, 1)), **fopts)
-        desc = _gsr.ReflForward(ptr(cam), ptr(cm), ptr(fv), L, ptr(rgba), ptr(final), ptr(refl_color), ptr(normal_world), ptr(keys), ptr(scratch),
-                                scratch.numel() if scratch is not None else 0, 1 if scratch is not None else 0)
-        keep += [cm, fv, cam]
-        extra = (final, refl_color, normal_world, rgba, keys, scratch)
+    desc, refl_keep, extra = _refl_forward(refl, H, W, dev, keys=True)
     with torch.cuda.device(dev):
         rendered = check(lib.gsr_surfel_forward_refl(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(mask), ptr(shc), ptr(col),
                                                      ptr(rfl), ptr(opa), ptr(sca), float(scale_modifier), ptr(rot), ptr(tmp), ptr(vm), ptr(pm),
                                                      ptr(cp), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), ptr(out_color),
-                                                     ptr(out_others), ptr(out_refl), ptr(radii), ptr(gaussian_weights),
-                                                     ctypes.byref(desc) if desc is not None else None, int(bool(debug)), stream_ptr(dev)),
+                                                     ptr(out_others), ptr(out_refl), ptr(radii), ptr(gaussian_weights), desc, int(bool(debug)),
+                                                     stream_ptr(dev)),
                          "gsr_surfel_forward")
     if ws.error is not None:
         raise ws.error
@@ -97,12 +112,9 @@ def rasterize_gaussians_eval(background, means3D, colors, refl_strengths, opacit
     Returns (num_rendered, color[3,H,W], alpha[1,H,W], normal_view[3,H,W] | None, refl_strength_map[1,H,W], radii[P] int32), and with
     `refl` also (final[3,H,W], refl_color[3,H,W], normal_world[3,H,W]); normal_view is None then (the epilogue consumes it).  Every
     plane is bit-identical to the corresponding output of rasterize_gaussians (alpha = allmap[1:2], normal_view = allmap[2:5])."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    for name, t in (("background", background), ("means3D", means3D), ("colors", colors), ("refl_strengths", refl_strengths),
-                    ("opacity", opacity), ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
-                    ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh), ("campos", campos)):
-        require_cuda(t, name)
+    keep, M = _forward_inputs(background, means3D, colors, refl_strengths, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix,
+                              sh, campos)
+    bg, m3, shc, col, rfl, opa, sca, rot, tmp, vm, pm, cp = keep
     P, H, W = means3D.size(0), int(image_height), int(image_width)
     dev = means3D.device
     fopts = dict(dtype=torch.float32, device=dev)
@@ -112,33 +124,16 @@ def rasterize_gaussians_eval(background, means3D, colors, refl_strengths, opacit
     out_refl = torch.empty((1, H, W), **fopts)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     ws = _gsr.Workspace(dev)
-    M = sh.size(1) if sh.numel() != 0 else 0
-    keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh"), f32c(colors, "colors"),
-            f32c(refl_strengths, "refl_strengths"), f32c(opacity, "opacity"), f32c(scales, "scales"), f32c(rotations, "rotations"),
-            f32c(transMat_precomp, "transMat_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"),
-            f32c(campos, "campos")]
-    bg, m3, shc, col, rfl, opa, sca, rot, tmp, vm, pm, cp = keep
-    desc, extra = None, ()
-    if refl is not None:
-        cm, fv, cam = f32c(refl["cubemap"], "cubemap"), f32c(refl["fail_value"], "fail_value"), f32c(refl["cam"], "cam")
-        if cm.dim() != 4 or cm.shape[0] != 6 or cm.shape[1] != 3 or cm.shape[2] != cm.shape[3]:
-            raise RuntimeError("rasterize + reflect: the cubemap must be (6, 3, L, L)")
-        L = int(cm.shape[2])
-        final, refl_color, normal_world = (torch.empty((3, H, W), **fopts) for _ in range(3))
-        rgba = torch.empty(6 * L * L * 4, **fopts)
-        desc = _gsr.ReflForward(ptr(cam), ptr(cm), ptr(fv), L, ptr(rgba), ptr(final), ptr(refl_color), ptr(normal_world), None, None, 0, 0)
-        keep += [cm, fv, cam, rgba]
-        extra = (final, refl_color, normal_world)
+    desc, refl_keep, refl_out = _refl_forward(refl, H, W, dev, keys=False)
     with torch.cuda.device(dev):
         rendered = check(lib.gsr_surfel_forward_eval(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(shc), ptr(col), ptr(rfl),
                                                      ptr(opa), ptr(sca), float(scale_modifier), ptr(rot), ptr(tmp), ptr(vm), ptr(pm), ptr(cp),
                                                      float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), ptr(out_color), ptr(out_alpha),
-                                                     ptr(out_normal), ptr(out_refl), ptr(radii),
-                                                     ctypes.byref(desc) if desc is not None else None, int(bool(debug)), stream_ptr(dev)),
+                                                     ptr(out_normal), ptr(out_refl), ptr(radii), desc, int(bool(debug)), stream_ptr(dev)),
                          "gsr_surfel_forward_eval")
     if ws.error is not None:
         raise ws.error
-    return (rendered, out_color, out_alpha, out_normal, out_refl, radii) + extra
+    return (rendered, out_color, out_alpha, out_normal, out_refl, radii) + refl_out[:3]
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, refl_strengths, scales, rotations, scale_modifier, transMat_precomp,

@@ -531,13 +531,7 @@ def render_fast(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, init
     base_color, _, allmap, refl_strength_map, _ = rasterizer(
         means3D=xyz, means2D=means2D, shs=pc.get_features, colors_precomp=None, refl_strengths=pc.get_refl, opacities=pc.get_opacity,
         scales=pc.get_scaling, rotations=pc.get_rotation, cov3D_precomp=None, env_scope_mask=torch.ones_like(xyz).bool())
-    if initial_stage:
-        return {"render": base_color, "rend_alpha": allmap[1:2], "refl_strength_map": refl_strength_map,
-                "rend_normal": shading_normal(allmap[2:5], v.world_view_transform, v.HWK, v.R, v.T)}
-    final_image, refl_color, rend_normal = deferred_reflection(allmap[2:5], base_color, refl_strength_map, pc.get_envmap,
-                                                               v.world_view_transform, v.HWK, v.R, v.T)
-    return {"render": final_image, "rend_alpha": allmap[1:2], "rend_normal": rend_normal, "refl_strength_map": refl_strength_map,
-            "refl_color_map": refl_color, "base_color_map": base_color}
+    return _render_fast_tail(v, pc, base_color, allmap[1:2], allmap[2:5], refl_strength_map, initial_stage)
 
 
 def _render_fast_eval(viewpoint_camera, pc, bg_color, scaling_modifier, initial_stage):
@@ -549,15 +543,19 @@ def _render_fast_eval(viewpoint_camera, pc, bg_color, scaling_modifier, initial_
                          HWK=v.HWK, R=v.R, T=v.T)
     if fused:
         return out
-    normal_view = out["rend_normal"]
+    return _render_fast_tail(v, pc, out["render"], out["rend_alpha"], out["rend_normal"], out["refl_strength_map"], initial_stage)
+
+
+def _render_fast_tail(v, pc, base_color, alpha, normal_view, refl_strength_map, initial_stage):
+    """render_fast() after a forward without the fused reflection epilogue: the shading normal (initial_stage) or the deferred reflection
+    from the rasterizer's base colour, alpha, view-space normal and reflection strength planes."""
     if initial_stage:
-        out["rend_normal"] = shading_normal(normal_view, v.world_view_transform, v.HWK, v.R, v.T)
-        return out
-    base_color = out["render"]
-    final_image, refl_color, rend_normal = deferred_reflection(normal_view, base_color, out["refl_strength_map"], pc.get_envmap,
+        return {"render": base_color, "rend_alpha": alpha, "refl_strength_map": refl_strength_map,
+                "rend_normal": shading_normal(normal_view, v.world_view_transform, v.HWK, v.R, v.T)}
+    final_image, refl_color, rend_normal = deferred_reflection(normal_view, base_color, refl_strength_map, pc.get_envmap,
                                                                v.world_view_transform, v.HWK, v.R, v.T)
-    out.update({"render": final_image, "rend_normal": rend_normal, "refl_color_map": refl_color, "base_color_map": base_color})
-    return out
+    return {"render": final_image, "rend_alpha": alpha, "rend_normal": rend_normal, "refl_strength_map": refl_strength_map,
+            "refl_color_map": refl_color, "base_color_map": base_color}
 
 
 def _panorama_dirs(H, W, device):
