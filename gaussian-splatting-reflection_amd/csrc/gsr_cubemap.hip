@@ -586,13 +586,7 @@ struct ReflScratch {
 // Sort of (texel id, pixel) through gsr_sort.hpp (one clear per sort).  17-bit texel ids at L = 128, 19-bit at L = 256: two
 // passes with 9- or 10-bit digits instead of three with 8.  Workgroup shape measured at n = 2 M pairs (whole backward, ms):
 // 256x12 0.361, 512x12 0.320, 1024x4 0.313, 1024x6 0.306, 1024x8 0.297, 1024x12 0.309, 1024x16 0.314.
-// `small` (the tail on the side stream, beside the tile backward): 256-thread workgroups with 8-bit digits.  The tile backward keeps
-// every CU at 16 single-wave workgroups and 152 of its 160 KB of LDS; a 1024-thread pass (39 KB of LDS, 16 waves) can only start on a
-// CU that has drained, i.e. when the tile backward is over, while a 256-thread one (one wave per SIMD, ~13 KB) slips in whenever one
-// of those workgroups retires.  Slower on an empty chip (one more pass, 4x the look-back chain), but hidden.
-#ifndef REFL_SMALL_SORT
-#define REFL_SMALL_SORT 1
-#endif
+// `small`: 256-thread workgroups with 8-bit digits (for the choice see gsr_deferred_reflection_backward_keys).
 // Shape of the 9-bit sort (L = 128).  Round 4: 512 x 16 instead of 1024 x 8 — the same 8192 pairs per workgroup, but a workgroup that finds
 // room beside the backward's pixel kernel (see ENTRIES_BS); alone on the chip the two shapes are within 2 us of each other.
 #ifndef REFL_SORT_BS
@@ -657,45 +651,88 @@ extern "C" size_t gsr_deferred_reflection_scratch_floats(uint32_t L, int width, 
 // they are enqueued on a library-owned stream that forks from the caller's stream after the pixel kernel and run
 // beside the (VALU-bound) tile backward; gsr_side_join() makes a stream wait for them.  One side stream per device, so
 // successive tails (a batch of views accumulating into one gradient) stay ordered among themselves.
-// Priority of the side stream.  Highest: the tail's small workgroups go first whenever a slot frees up, its look-back chains move
-// and it is over early (measured, interleaved runs of the C3 step: highest 1.917-1.922 ms; default 1.905-1.920 ms in two runs of four but
-// 2.44 / 2.55 ms in the other two — default-priority streams share the runtime's pool of hardware queues and the step then
-// depends on which queue the side stream happened to get; lowest 1.98 ms: the tail only runs once the tile backward has drained).
-#ifndef GSR_SIDE_PRIO
-#define GSR_SIDE_PRIO 1     // 0: default priority; 1: highest; -1: lowest
-#endif
 namespace {
 struct SideStream {
 	hipStream_t stream = nullptr;
-	hipEvent_t fork = nullptr, fork2 = nullptr, done = nullptr, sorted = nullptr, gate = nullptr;
-	bool recorded = false;      // `done` has been recorded at least once (an event that was never recorded must not be waited on)
-	bool sorted_recorded = false;
+	hipEvent_t fork = nullptr, fork2 = nullptr, done = nullptr, gate = nullptr;
+	bool recorded = false;      // `done` — recorded behind every early sort and every tail — has been recorded at least once (an event that was never recorded must not be waited on)
 	bool gate_pending = false;  // `gate` = "the last pass of the key sort is next on the side stream": the rasterizer's tile backward waits for it ONCE
 };
 std::mutex g_side_mu;
 SideStream g_side[64];
-SideStream* side_stream() {   // (g_side_mu held)
+// The current device's side stream (g_side_mu held), created on first use when `create`; NULL if there is none.  Created at the highest
+// priority: the tail's small workgroups go first whenever a slot frees up, its look-back chains move and it is over early (measured,
+// interleaved runs of the C3 step: highest 1.917-1.922 ms; default 1.905-1.920 ms in two runs of four but 2.44 / 2.55 ms in the other two
+// — default-priority streams share the runtime's pool of hardware queues and the step then depends on which queue the side stream
+// happened to get; lowest 1.98 ms: the tail only runs once the tile backward has drained).
+SideStream* side_stream(bool create) {
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
 	SideStream& s = g_side[dev];
-	if (!s.stream) {
-#if GSR_SIDE_PRIO
+	if (!s.stream && create) {
 		int least = 0, greatest = 0;
 		(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-		if (hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, GSR_SIDE_PRIO > 0 ? greatest : least) != hipSuccess) { s.stream = nullptr; return nullptr; }
-#else
-		if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) { s.stream = nullptr; return nullptr; }
-#endif
+		if (hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, greatest) != hipSuccess) { s.stream = nullptr; return nullptr; }
 		if (hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s.fork2, hipEventDisableTiming) != hipSuccess ||
-		    hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s.sorted, hipEventDisableTiming) != hipSuccess ||
-		    hipEventCreateWithFlags(&s.gate, hipEventDisableTiming) != hipSuccess) {
+		    hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s.gate, hipEventDisableTiming) != hipSuccess) {
 			(void)hipStreamDestroy(s.stream);
 			s.stream = nullptr;
-			return nullptr;
 		}
 	}
-	return &s;
+	return s.stream ? &s : nullptr;
 }
+
+// The scratch of the sorted-footprint backward, carved, and the stream its sort / combine / unpack go to: the caller's, or with
+// use_side_stream() the side stream, which stays locked for as long as the ReflTail lives.  Used by the backward and by the early sort.
+struct ReflTail {
+	ReflScratch rs;
+	float* staging = nullptr;     // [6][L][L][4] channel-interleaved texel gradients (rim pixels add here directly; the combine adds the rest)
+	float* fail_acc = nullptr;    // 4 floats behind it: gradient of the fail value
+	ReflFootprint* footprints = nullptr;   // one 32-byte record per pixel
+	uint32_t *keys_in = nullptr, *keys_out = nullptr, *pix_out = nullptr;
+	void* sort_temp = nullptr;
+	hipStream_t stream, tail;
+	SideStream* side = nullptr;
+	std::unique_lock<std::mutex> lock;
+
+	ReflTail(uint32_t L, int width, int height, hipStream_t s) : rs(refl_scratch(L, width, height)), stream(s), tail(s) {}
+	// false: `scratch` does not hold the sorted path (32-byte aligned, gsr_deferred_reflection_scratch_floats(L, W, H, 1) floats)
+	bool carve(float* scratch, size_t scratch_floats) {
+		staging = scratch;
+		fail_acc = scratch + rs.ntex * 4;
+		if (scratch_floats < rs.total_floats || rs.n >= ((size_t)1 << 30) || rs.ntex >= 0xFFFFFFFFull || ((uintptr_t)scratch & 31) != 0) return false;
+		footprints = reinterpret_cast<ReflFootprint*>(scratch + (rs.ntex + 1) * 4 + 4);   // 32-byte aligned as long as scratch is
+		keys_in = reinterpret_cast<uint32_t*>(footprints + rs.n);
+		keys_out = keys_in + rs.n;
+		pix_out = keys_out + rs.n;
+		sort_temp = reinterpret_cast<void*>(((uintptr_t)(pix_out + rs.n) + 255) & ~(uintptr_t)255);
+		return true;
+	}
+	void lock_side() { lock = std::unique_lock<std::mutex>(g_side_mu); }
+	void use_side_stream() {
+		lock_side();
+		side = side_stream(true);
+		if (side) tail = side->stream;
+	}
+	size_t sort_cleared_bytes(bool small) const { return refl_sort_cleared_bytes(rs.key_bits, rs.n, small); }
+	// the side stream waits for what `stream` has enqueued so far
+	hipError_t fork(hipEvent_t ev) {
+		hipError_t e = hipEventRecord(ev, stream);
+		return e == hipSuccess ? hipStreamWaitEvent(side->stream, ev, 0) : e;
+	}
+	// gated: on the side stream, arm the gate (see side_gate_wait)
+	hipError_t sort(const uint32_t* keys, bool small, bool gated) {
+		size_t sb = rs.sort_bytes;
+		hipError_t e = refl_sort(sort_temp, sb, rs.key_bits, keys, keys_out, pix_out, rs.n, tail, true, small, gated && side ? side->gate : nullptr);
+		if (e == hipSuccess && gated && side) side->gate_pending = true;
+		return e;
+	}
+	hipError_t mark_done() {
+		hipError_t e = hipEventRecord(side->done, side->stream);
+		if (e == hipSuccess) side->recorded = true;
+		return e;
+	}
+};
 }  // namespace
 
 // The gate of the key sort (see SideStream::gate_pending): called by the rasterizer backward right before its tile kernel.  A sort pass of
@@ -706,173 +743,49 @@ SideStream* side_stream() {   // (g_side_mu held)
 namespace gsr {
 int side_gate_wait(hipStream_t stream) {
 	std::lock_guard<std::mutex> lk(g_side_mu);
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-	SideStream& s = g_side[dev];
-	if (s.stream && s.gate_pending) {
-		s.gate_pending = false;
-		GSR_HIP_CHECK(hipStreamWaitEvent(stream, s.gate, 0));
+	SideStream* s = side_stream(false);
+	if (s && s->gate_pending) {
+		s->gate_pending = false;
+		GSR_HIP_CHECK(hipStreamWaitEvent(stream, s->gate, 0));
 	}
-	return 0;
-}
-}  // namespace gsr
-
-extern "C" int gsr_side_join(void* stream_) {
-	std::lock_guard<std::mutex> lk(g_side_mu);
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-	SideStream& s = g_side[dev];
-	// Every joining stream waits on the LAST recorded `done` (not cleared by the first waiter: an all-reduce stream and then an
-	// optimizer stream may both consume the sink); waiting on an event that has already completed costs nothing on the device.
-	if (s.stream && s.recorded) GSR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream_, s.done, 0));
 	return 0;
 }
 
-namespace gsr {
-// ---- host side of the texel-gradient tail, shared by gsr_deferred_reflection_backward* and the fused surfel backward
-// (gsr_surfel_backward_refl, gsr_surfel.hip), whose tile kernel runs the pixel part as its prologue.  Order of use:
-//   refl_tail_begin   carve the scratch, pick the stream of the tail (locks the side stream when async)
-//   [the caller zeroes clear[0..1] on `stream` — refl_tail_clear() does it with two fills — before anything else]
-//   refl_tail_sort    with forward keys: fork the side stream and start the sort (it depends on nothing the pixel code computes)
-//   [the caller's pixel code on `stream`: records, rim atomics into `staging`, fail-value sums into `fail_acc`]
-//   refl_tail_finish  join the pixel code, (sort,) run combine, unpack, `done` event
-int refl_tail_begin(ReflTail& t, uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async_tail,
-                    int accumulate, float* g_cubemap, float* g_fail, hipStream_t stream) {
-	const ReflScratch rs = refl_scratch(L, width, height);
-	if (scratch_floats < rs.total_floats || rs.n >= ((size_t)1 << 30) || rs.ntex >= 0xFFFFFFFFull || ((uintptr_t)scratch & 31) != 0) {
-		set_error("reflection backward (sorted footprints): scratch of %zu floats, 32-byte aligned, needed (gsr_deferred_reflection_scratch_floats(L, W, H, 1))",
-		          rs.total_floats);
-		return GSR_E_INVALID;
-	}
-	t.L = L; t.n = rs.n; t.ntex = rs.ntex; t.key_bits = rs.key_bits; t.sort_bytes = rs.sort_bytes;
-	t.staging = scratch;
-	t.fail_acc = scratch + rs.ntex * 4;   // [texel staging ntex*4][fail-value gradient 4]
-	ReflFootprint* fp = reinterpret_cast<ReflFootprint*>(scratch + (rs.ntex + 1) * 4 + 4);   // 32-byte aligned as long as scratch is
-	t.footprints = fp;
-	t.keys_in = reinterpret_cast<uint32_t*>(fp + rs.n);
-	t.keys_out = t.keys_in + rs.n;
-	t.pix_out = t.keys_out + rs.n;
-	t.sort_temp = reinterpret_cast<void*>(((uintptr_t)(t.pix_out + rs.n) + 255) & ~(uintptr_t)255);
-	t.sort_keys = sort_keys;
-	// sort_keys: the forward already wrote the keys, so the sort depends on nothing the backward computes: with async_tail it forks
-	// BEFORE the pixel code and runs beside it and only the combine waits for the records.  Without keys the sort follows the pixel code and,
-	// on the side stream, has to share the chip with the tile backward: the small shape then (see refl_sort).
-	t.small_sort = async_tail && !sort_keys && REFL_SMALL_SORT;
-	t.clear_ptr[0] = scratch; t.clear_bytes[0] = (rs.ntex + 1) * 4 * sizeof(float);
-	t.clear_ptr[1] = t.sort_temp; t.clear_bytes[1] = refl_sort_cleared_bytes(rs.key_bits, rs.n, t.small_sort);
-	t.stream = stream; t.tail = stream; t.side = nullptr; t.locked = false;
-	t.g_cubemap = g_cubemap; t.g_fail = g_fail; t.accumulate = accumulate;
-	if (async_tail) {
-		g_side_mu.lock();
-		t.locked = true;
-		SideStream* side = side_stream();
-		if (side) { t.side = side; t.tail = side->stream; }
-	}
-	return 0;
-}
-void refl_tail_abort(ReflTail& t) {
-	if (t.locked) { g_side_mu.unlock(); t.locked = false; }
-}
-int refl_tail_clear(ReflTail& t) {
-	hipError_t e = hipMemsetAsync(t.clear_ptr[0], 0, t.clear_bytes[0], t.stream);
-	if (e == hipSuccess) e = hipMemsetAsync(t.clear_ptr[1], 0, t.clear_bytes[1], t.stream);
-	if (e != hipSuccess) { refl_tail_abort(t); set_error("reflection backward: clearing the scratch failed: %s", hipGetErrorString(e)); return GSR_E_HIP; }
-	return 0;
-}
-#define REFL_TAIL_CHECK(expr)                                                                                     \
-	do {                                                                                                          \
-		hipError_t _e = (expr);                                                                                   \
-		if (_e != hipSuccess) {                                                                                   \
-			refl_tail_abort(t);                                                                                   \
-			gsr::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);            \
-			return GSR_E_HIP;                                                                                     \
-		}                                                                                                         \
-	} while (0)
-// With forward keys: fork the side stream and start the sort (between the clears and the pixel code).
-int refl_tail_sort(ReflTail& t) {
-	if (!t.sort_keys) return 0;
-	SideStream* side = static_cast<SideStream*>(t.side);
-	if (side) {
-		REFL_TAIL_CHECK(hipEventRecord(side->fork, t.stream));
-		REFL_TAIL_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
-	}
-	size_t sb = t.sort_bytes;
-	StageTimer tt(GSR_STAGE_REFL_BWD_TAIL, t.tail);     // timed on the stream it runs on: with async_tail NOT inside GSR_STAGE_REFL_BWD's events
-	REFL_TAIL_CHECK(refl_sort(t.sort_temp, sb, t.key_bits, t.sort_keys, t.keys_out, t.pix_out, t.n, t.tail, true, false, side ? side->gate : nullptr));
-	if (side) side->gate_pending = true;
-	return 0;
-}
 // The sort of the footprint keys, EARLY: called by a forward that has just written the keys (gsr_surfel_forward_refl) with the scratch the
 // backward will use.  async: on the side stream, forked behind the kernel that wrote the keys — it then runs beside whatever the caller
 // enqueues next (the loss; the fills and the pixel kernel of the backward) while the chip still has room: a 1024-thread sort workgroup
 // cannot start on a CU the tile backward has filled (round 3), and since round 4 the backward's pixel kernel is short enough that a sort
 // forked in the backward no longer finished before that kernel took the chip (its second pass then waited 0.8 ms and the run combine ran
 // after the tile backward, beside — and at the expense of — the per-Gaussian backward).  The backward is told with keys_sorted = 1.
-int refl_sort_keys_early(uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async, hipStream_t stream) {
-	ReflTail t;
-	int rc = refl_tail_begin(t, L, width, height, scratch, scratch_floats, sort_keys, async, 0, nullptr, nullptr, stream);
-	if (rc < 0) return rc;
-	SideStream* side = static_cast<SideStream*>(t.side);
-	if (side) {
-		REFL_TAIL_CHECK(hipEventRecord(side->fork, t.stream));
-		REFL_TAIL_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
+// gated: arm the gate; not when no tile backward will consume it (nothing rendered), which would leave it for an unrelated one.
+int refl_sort_keys_early(uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async, bool gated,
+                         hipStream_t stream) {
+	ReflTail t(L, width, height, stream);
+	if (!t.carve(scratch, scratch_floats)) {
+		set_error("reflection backward (sorted footprints): scratch of %zu floats, 32-byte aligned, needed (gsr_deferred_reflection_scratch_floats(L, W, H, 1))",
+		          t.rs.total_floats);
+		return GSR_E_INVALID;
 	}
+	if (async) t.use_side_stream();
+	if (t.side) GSR_HIP_CHECK(t.fork(t.side->fork));
 	{
 		StageTimer tt(GSR_STAGE_REFL_BWD_TAIL, t.tail);
-		REFL_TAIL_CHECK(hipMemsetAsync(t.clear_ptr[1], 0, t.clear_bytes[1], t.tail));
-		size_t sb = t.sort_bytes;
-		REFL_TAIL_CHECK(refl_sort(t.sort_temp, sb, t.key_bits, t.sort_keys, t.keys_out, t.pix_out, t.n, t.tail, true, false, side ? side->gate : nullptr));
+		GSR_HIP_CHECK(hipMemsetAsync(t.sort_temp, 0, t.sort_cleared_bytes(false), t.tail));
+		GSR_HIP_CHECK(t.sort(sort_keys, false, gated));
 	}
-	if (side) {
-		side->gate_pending = true;
-		REFL_TAIL_CHECK(hipEventRecord(side->sorted, side->stream));
-		side->sorted_recorded = true;
-	}
-	refl_tail_abort(t);
+	if (t.side) GSR_HIP_CHECK(t.mark_done());
 	return 0;
 }
-// keys_sorted: the backward's counterpart — the stream its tail runs on is ordered behind the early sort (a no-op when that is the side
-// stream itself: the combine is enqueued there behind the sort anyway)
-int refl_tail_join_early_sort(ReflTail& t) {
-	std::unique_lock<std::mutex> lk(g_side_mu, std::defer_lock);
-	if (!t.locked) lk.lock();
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-	SideStream& s = g_side[dev];
-	if (s.stream && s.sorted_recorded && t.tail != s.stream) REFL_TAIL_CHECK(hipStreamWaitEvent(t.tail, s.sorted, 0));
-	return 0;
-}
-
-int refl_tail_finish(ReflTail& t) {
-	SideStream* side = static_cast<SideStream*>(t.side);
-	if (side) {     // the combine needs the records (and, without forward keys, the sort needs the keys) the pixel code just wrote
-		hipEvent_t ev = t.sort_keys ? side->fork2 : side->fork;
-		REFL_TAIL_CHECK(hipEventRecord(ev, t.stream));
-		REFL_TAIL_CHECK(hipStreamWaitEvent(side->stream, ev, 0));
-	}
-	{
-		StageTimer tt(GSR_STAGE_REFL_BWD_TAIL, t.tail);
-		const size_t per_wg = (size_t)256 * REFL_CHUNK;
-		const unsigned cgrid = (unsigned)((t.n + per_wg - 1) / per_wg);
-		const ReflFootprint* fp = static_cast<const ReflFootprint*>(t.footprints);
-		if (!t.sort_keys) {
-			size_t sb = t.sort_bytes;
-			REFL_TAIL_CHECK(refl_sort(t.sort_temp, sb, t.key_bits, t.keys_in, t.keys_out, t.pix_out, t.n, t.tail, true, t.small_sort));
-		}
-		refl_run_combine_kernel<<<cgrid, 256, 0, t.tail>>>(t.keys_out, t.pix_out, fp, t.n, t.L, (uint32_t)t.ntex, t.staging);
-		auto unpack = t.accumulate ? unpack_cubemap_grad_kernel<true> : unpack_cubemap_grad_kernel<false>;
-		unpack<<<(unsigned)((t.ntex + 255) / 256), 256, 0, t.tail>>>((const float4*)t.staging, t.g_cubemap, t.g_fail, (int)t.L);
-	}
-	if (side) {
-		REFL_TAIL_CHECK(hipEventRecord(side->done, side->stream));
-		side->recorded = true;
-	}
-	REFL_TAIL_CHECK(hipGetLastError());
-	refl_tail_abort(t);      // (releases the side-stream lock)
-	return 0;
-}
-
 }  // namespace gsr
+
+extern "C" int gsr_side_join(void* stream_) {
+	std::lock_guard<std::mutex> lk(g_side_mu);
+	// Every joining stream waits on the LAST recorded `done` (not cleared by the first waiter: an all-reduce stream and then an
+	// optimizer stream may both consume the sink); waiting on an event that has already completed costs nothing on the device.
+	const SideStream* s = side_stream(false);
+	if (s && s->recorded) GSR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream_, s->done, 0));
+	return 0;
+}
 
 extern "C" int gsr_deferred_reflection_backward_keys(const float* normal_view, const float* base_color, const float* refl_strength, const float* cam,
                                                    const float* cubemap, const float* fail_value, uint32_t L, int width, int height,
@@ -887,58 +800,80 @@ extern "C" int gsr_deferred_reflection_backward_keys(const float* normal_view, c
 		return GSR_E_INVALID;
 	}
 	const size_t HW = (size_t)width * height;
-	const ReflScratch rs = refl_scratch(L, width, height);
-	const size_t ntex = rs.ntex;
+	ReflTail t(L, width, height, stream);
+	const size_t ntex = t.rs.ntex;
 	if (scratch_floats < (ntex + 1) * 4) { set_error("gsr_deferred_reflection_backward: scratch smaller than (6*L*L+1)*4 floats"); return GSR_E_INVALID; }
-	const bool binned = scratch_floats >= rs.total_floats && rs.n < ((size_t)1 << 30) && rs.ntex < 0xFFFFFFFFull && ((uintptr_t)scratch & 31) == 0;
+	const bool binned = t.carve(scratch, scratch_floats);
 	if (keys_sorted && !binned) { set_error("gsr_deferred_reflection_backward: keys_sorted needs the scratch the forward sorted into"); return GSR_E_INVALID; }
+	auto unpack = accumulate ? unpack_cubemap_grad_kernel<true> : unpack_cubemap_grad_kernel<false>;
+	// the staging buffer and the fail-value gradient are zeroed first on every path
+	GSR_HIP_CHECK(hipMemsetAsync(scratch, 0, (ntex + 1) * 4 * sizeof(float), stream));
 	if (!binned) {
 		// texel gradients by float atomics straight from the pixel kernel (memory-side, ~2.5 requests per pixel)
-		float* fail_acc = scratch + ntex * 4;   // [texel staging ntex*4][fail-value gradient 4]
-		GSR_HIP_CHECK(hipMemsetAsync(scratch, 0, (ntex + 1) * 4 * sizeof(float), stream));
 		{
 			StageTimer st_(GSR_STAGE_REFL_BWD, stream);
 			const unsigned grid = (unsigned)((HW * 4 + 255) / 256);
 			deferred_refl_bwd_kernel<<<grid, 256, 0, stream>>>(normal_view, base_color, refl_strength, cam, cubemap, fail_value, (int)L, width, height, g_final,
-			                                                  g_refl_color, g_normal_world, g_normal_view, g_base, g_strength, scratch, fail_acc);
+			                                                  g_refl_color, g_normal_world, g_normal_view, g_base, g_strength, t.staging, t.fail_acc);
 		}
-		auto unpack = accumulate ? unpack_cubemap_grad_kernel<true> : unpack_cubemap_grad_kernel<false>;
-		unpack<<<(unsigned)((ntex + 255) / 256), 256, 0, stream>>>((const float4*)scratch, g_cubemap, g_fail, (int)L);
+		unpack<<<(unsigned)((ntex + 255) / 256), 256, 0, stream>>>((const float4*)t.staging, g_cubemap, g_fail, (int)L);
 		GSR_LAUNCH_CHECK(0, stream);
 		return 0;
 	}
 	// sorted footprints: the pixel kernel stores one footprint record per pixel and its texel id as a sort key; a radix sort of
 	// (texel id, pixel) makes equal texels adjacent; refl_run_combine_kernel gathers the records in that order, sums runs in
 	// registers and a workgroup's texel range in LDS.
-	ReflTail t;
-	int rc = refl_tail_begin(t, L, width, height, scratch, scratch_floats, sort_keys, async_tail, accumulate, g_cubemap, g_fail, stream);
-	if (rc < 0) return rc;
-	// the staging buffer is zeroed here; the sort's look-back state by the pixel kernel (no forward keys: the sort follows it) or by a fill
-	// in front of the sort (forward keys); keys_sorted: the forward call has sorted (or is still sorting, on the side stream) into this
-	// scratch: only the staging buffer is touched
-	if (sort_keys && !keys_sorted) rc = refl_tail_clear(t);
-	else if (hipMemsetAsync(t.clear_ptr[0], 0, t.clear_bytes[0], stream) != hipSuccess) { refl_tail_abort(t); set_error("hipMemsetAsync failed"); return GSR_E_HIP; }
-	if (rc < 0) return rc;
-	rc = keys_sorted ? refl_tail_join_early_sort(t) : refl_tail_sort(t);
-	if (rc < 0) return rc;
+	// sort_keys: the forward already wrote the keys, so the sort depends on nothing the backward computes: with async_tail it forks
+	// BEFORE the pixel code and runs beside it and only the combine waits for the records.  Without keys the sort follows the pixel code and,
+	// on the side stream, has to share the chip with the tile backward: the small shape then.  The tile backward keeps every CU at 16
+	// single-wave workgroups and 152 of its 160 KB of LDS; a 1024-thread pass (39 KB of LDS, 16 waves) can only start on a CU that has
+	// drained, i.e. when the tile backward is over, while a 256-thread one (one wave per SIMD, ~13 KB) slips in whenever one of those
+	// workgroups retires.  Slower on an empty chip (one more pass, 4x the look-back chain), but hidden.
+	const bool small_sort = async_tail && !sort_keys;
+	const size_t sort_cleared = t.sort_cleared_bytes(small_sort);
+	if (async_tail) t.use_side_stream();
+	else if (keys_sorted) t.lock_side();   // (to read the side stream's state)
+	if (keys_sorted) {
+		// the forward has sorted (or is still sorting, on the side stream) into this scratch: the stream of the tail is ordered behind
+		// it (nothing to do when that is the side stream itself: the combine is enqueued there behind the sort anyway)
+		const SideStream* s = side_stream(false);
+		if (s && s->recorded && t.tail != s->stream) GSR_HIP_CHECK(hipStreamWaitEvent(t.tail, s->done, 0));
+	} else if (sort_keys) {
+		// the sort's look-back state is zeroed by a fill in front of the sort (without forward keys: by the pixel kernel, which the sort follows)
+		GSR_HIP_CHECK(hipMemsetAsync(t.sort_temp, 0, sort_cleared, stream));
+		if (t.side) GSR_HIP_CHECK(t.fork(t.side->fork));
+		StageTimer tt(GSR_STAGE_REFL_BWD_TAIL, t.tail);     // timed on the stream it runs on: with async_tail NOT inside GSR_STAGE_REFL_BWD's events
+		GSR_HIP_CHECK(t.sort(sort_keys, false, true));
+	}
 	{
 		StageTimer st_(GSR_STAGE_REFL_BWD, stream);      // the pixel kernel; the texel-gradient tail is GSR_STAGE_REFL_BWD_TAIL
 		const unsigned egrid = (unsigned)((HW + ENTRIES_BS - 1) / ENTRIES_BS);
-		ReflFootprint* fp = static_cast<ReflFootprint*>(t.footprints);
 		if (cubemap_rgba && ((uintptr_t)cubemap_rgba & 15) == 0)     // the texel-interleaved copy the forward made (same cubemap)
 			deferred_refl_bwd_entries_kernel<true><<<egrid, ENTRIES_BS, 0, stream>>>(normal_view, base_color, refl_strength, cam, cubemap,
 			                                                                 reinterpret_cast<const float4*>(cubemap_rgba), fail_value, (int)L, width, height, g_final,
-			                                                                 g_refl_color, g_normal_world, g_normal_view, g_base, g_strength, t.fail_acc, t.staging, fp,
-			                                                                 t.keys_in, sort_keys, (uint32_t)ntex, sort_keys ? nullptr : t.sort_temp,
-			                                                                 sort_keys ? 0 : t.clear_bytes[1]);
+			                                                                 g_refl_color, g_normal_world, g_normal_view, g_base, g_strength, t.fail_acc, t.staging,
+			                                                                 t.footprints, t.keys_in, sort_keys, (uint32_t)ntex, sort_keys ? nullptr : t.sort_temp,
+			                                                                 sort_keys ? 0 : sort_cleared);
 		else
 			deferred_refl_bwd_entries_kernel<false><<<egrid, ENTRIES_BS, 0, stream>>>(normal_view, base_color, refl_strength, cam, cubemap, nullptr, fail_value, (int)L, width,
 			                                                                  height, g_final, g_refl_color, g_normal_world, g_normal_view, g_base, g_strength, t.fail_acc,
-			                                                                  t.staging, fp, t.keys_in, sort_keys, (uint32_t)ntex, sort_keys ? nullptr : t.sort_temp,
-			                                                                  sort_keys ? 0 : t.clear_bytes[1]);
+			                                                                  t.staging, t.footprints, t.keys_in, sort_keys, (uint32_t)ntex, sort_keys ? nullptr : t.sort_temp,
+			                                                                  sort_keys ? 0 : sort_cleared);
 	}
-	// the per-pixel gradients are complete here; what follows only produces dL_dcubemap / dL_dfail
-	return refl_tail_finish(t);
+	// the per-pixel gradients are complete here; what follows only produces dL_dcubemap / dL_dfail.  The combine needs the records (and,
+	// without forward keys, the sort needs the keys) the pixel code just wrote.
+	if (t.side) GSR_HIP_CHECK(t.fork(sort_keys ? t.side->fork2 : t.side->fork));
+	{
+		StageTimer tt(GSR_STAGE_REFL_BWD_TAIL, t.tail);
+		const size_t per_wg = (size_t)256 * REFL_CHUNK;
+		const unsigned cgrid = (unsigned)((t.rs.n + per_wg - 1) / per_wg);
+		if (!sort_keys) GSR_HIP_CHECK(t.sort(t.keys_in, small_sort, false));
+		refl_run_combine_kernel<<<cgrid, 256, 0, t.tail>>>(t.keys_out, t.pix_out, t.footprints, t.rs.n, L, (uint32_t)ntex, t.staging);
+		unpack<<<(unsigned)((ntex + 255) / 256), 256, 0, t.tail>>>((const float4*)t.staging, g_cubemap, g_fail, (int)L);
+	}
+	if (t.side) GSR_HIP_CHECK(t.mark_done());
+	GSR_HIP_CHECK(hipGetLastError());
+	return 0;
 }
 
 /* the round-2 signature of gsr_deferred_reflection_backward_ex (no forward keys): kept so that a caller built against the earlier header

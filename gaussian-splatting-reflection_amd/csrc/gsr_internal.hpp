@@ -163,34 +163,12 @@ uint32_t higher_msb(uint32_t n);
 int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int tiles_y, const GeomState& geom,
                 const ImageState& img, BinningState* out_binning, int prefiltered, int debug, hipStream_t stream, bool blend_masks = true);
 
-// Texel-gradient tail of the deferred-reflection backward (sort of the per-pixel footprint records by texel, run combine, unpack:
-// gsr_cubemap.hip) around the pixel kernel of gsr_deferred_reflection_backward*.  See refl_tail_begin in gsr_cubemap.hip.
-struct ReflTail {
-	float* staging;          // [6][L][L][4] channel-interleaved texel gradients (rim pixels add here directly; the combine adds the rest)
-	float* fail_acc;         // 4 floats behind it: gradient of the fail value
-	void* footprints;        // ReflFootprint[n], one 32-byte record per pixel
-	uint32_t *keys_in, *keys_out, *pix_out;
-	void* sort_temp;
-	void* clear_ptr[2];      // what must be zero before the pixel code runs: [0] staging + fail_acc, [1] the sort's look-back state
-	size_t clear_bytes[2];
-	size_t n, ntex, sort_bytes;
-	int key_bits;
-	uint32_t L;
-	const uint32_t* sort_keys;   // keys written by the forward, or NULL (then the pixel code writes keys_in)
-	bool small_sort, locked;
-	hipStream_t stream, tail;
-	void* side;
-	float *g_cubemap, *g_fail;
-	int accumulate;
-};
-int refl_tail_begin(ReflTail& t, uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async_tail,
-                    int accumulate, float* g_cubemap, float* g_fail, hipStream_t stream);
-int refl_tail_clear(ReflTail& t);
-int refl_tail_sort(ReflTail& t);
-int refl_tail_finish(ReflTail& t);
-void refl_tail_abort(ReflTail& t);
+// The reflection backward's side stream (gsr_cubemap.hip): the rasterizer backward holds its tile kernel back until the key sort's last pass is
+// next there; the training forward sorts the backward's footprint keys early (with async, on the side stream; `gated`: arm that gate —
+// only when a tile backward will follow, i.e. the forward rendered something).
 int side_gate_wait(hipStream_t stream);
-int refl_sort_keys_early(uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async, hipStream_t stream);
+int refl_sort_keys_early(uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async, bool gated,
+                         hipStream_t stream);
 
 }  // namespace gsr
 

@@ -1235,9 +1235,10 @@ static int check_surfel_inputs(const char* entry, int P, int D, int M, const flo
 }
 
 // The key sort of the reflection backward that the training forward starts when the descriptor hands it sort_keys and scratch; 0 otherwise.
-static int early_key_sort(const gsr_refl_forward* refl, int width, int height, hipStream_t stream) {
+// R = num_rendered: the tile backward that consumes the sort's gate runs only when R > 0.
+static int early_key_sort(const gsr_refl_forward* refl, int width, int height, int R, hipStream_t stream) {
 	if (!refl || !refl->sort_keys || !refl->scratch) return 0;
-	return refl_sort_keys_early(refl->L, width, height, refl->scratch, refl->scratch_floats, refl->sort_keys, refl->async_sort, stream);
+	return refl_sort_keys_early(refl->L, width, height, refl->scratch, refl->scratch_floats, refl->sort_keys, refl->async_sort, R > 0, stream);
 }
 
 // Both surfel forwards after their checks.  TRAIN: gsr_surfel_forward_refl, which writes out_others, gaussian_weights and everything the
@@ -1252,6 +1253,7 @@ static int surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, in
                           float* out_alpha, float* out_normal_view, float* out_refl_strength_map, int* radii, float* gaussian_weights,
                           const gsr_refl_forward* refl, int debug, hipStream_t stream) {
 	const size_t HW = (size_t)width * height;
+	int R = 0;   // num_rendered
 	if (P == 0) {
 		// zero planes, and with refl the stand-alone pixel pass over them: the same arithmetic on an empty scene
 		float* normal = TRAIN ? out_others + 2 * HW : out_normal_view;
@@ -1267,45 +1269,46 @@ static int surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, in
 			GSR_HIP_CHECK(hipMemsetAsync(normal, 0, HW * 3 * 4, stream));
 		}
 		GSR_HIP_CHECK(hipMemsetAsync(out_refl_strength_map, 0, HW * 4, stream));
-		if (refl)
-			return gsr_deferred_reflection_forward_keys(normal, out_color, out_refl_strength_map, refl->cam, refl->cubemap, refl->fail_value, refl->L,
-			                                            width, height, refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->cubemap_rgba,
-			                                            refl->sort_keys, stream) < 0 ? GSR_E_HIP : 0;
-		return 0;
+		if (refl && gsr_deferred_reflection_forward_keys(normal, out_color, out_refl_strength_map, refl->cam, refl->cubemap, refl->fail_value, refl->L,
+		                                                 width, height, refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->cubemap_rgba,
+		                                                 refl->sort_keys, stream) < 0)
+			return GSR_E_HIP;
+	} else {
+		const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
+		const int ntiles = tiles_x * tiles_y;
+		GeomState geom; ImageState img;
+		if (const int rc = forward_workspace(alloc, alloc_user, TRAIN ? SURFEL_LAYOUT : SURFEL_LAYOUT.inference(), P, HW, ntiles, &geom, &img); rc < 0) return rc;
+
+		if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));   // the flag is only written and read then
+		const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
+		CubemapInterleave ci{nullptr, nullptr, 0u, 1u};
+		SurfelReflFwd rf{};
+		if (refl) {
+			ci = CubemapInterleave{refl->cubemap, reinterpret_cast<float4*>(refl->cubemap_rgba), 6u * refl->L * refl->L, refl->L * refl->L};
+			rf = SurfelReflFwd{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
+			                   refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->sort_keys};
+		}
+	{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<TRAIN><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
+		                                                                     transMat_precomp, colors_precomp, refl_strengths, env_scope_mask, cam, radii, geom,
+		                                                                     tiles_x, tiles_y, prefiltered, gaussian_weights, ci); }
+		GSR_LAUNCH_CHECK(debug, stream);
+
+		BinningState bin;
+		R = run_binning(alloc, alloc_user, P, tiles_x, tiles_y, geom, img, &bin, prefiltered, debug, stream, TRAIN);
+		if (R < 0) return R;
+
+	{ StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
+		const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
+		const auto args = [&] { if constexpr (TRAIN) return rf; else return SurfelEvalFwd{rf, out_alpha, out_normal_view}; }();
+		auto render = refl ? surfel_render_fwd_wave_kernel<true, TRAIN> : surfel_render_fwd_wave_kernel<false, TRAIN>;
+		render<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(),
+		                                  background, TRAIN ? img.final_T : nullptr, TRAIN ? img.n_contrib : nullptr, out_color, out_others,
+		                                  out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, args); }
+		GSR_LAUNCH_CHECK(debug, stream);
 	}
-	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
-	const int ntiles = tiles_x * tiles_y;
-	GeomState geom; ImageState img;
-	if (const int rc = forward_workspace(alloc, alloc_user, TRAIN ? SURFEL_LAYOUT : SURFEL_LAYOUT.inference(), P, HW, ntiles, &geom, &img); rc < 0) return rc;
-
-	if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));   // the flag is only written and read then
-	const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
-	CubemapInterleave ci{nullptr, nullptr, 0u, 1u};
-	SurfelReflFwd rf{};
-	if (refl) {
-		ci = CubemapInterleave{refl->cubemap, reinterpret_cast<float4*>(refl->cubemap_rgba), 6u * refl->L * refl->L, refl->L * refl->L};
-		rf = SurfelReflFwd{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
-		                   refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->sort_keys};
-	}
-{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<TRAIN><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
-	                                                                     transMat_precomp, colors_precomp, refl_strengths, env_scope_mask, cam, radii, geom,
-	                                                                     tiles_x, tiles_y, prefiltered, gaussian_weights, ci); }
-	GSR_LAUNCH_CHECK(debug, stream);
-
-	BinningState bin;
-	const int R = run_binning(alloc, alloc_user, P, tiles_x, tiles_y, geom, img, &bin, prefiltered, debug, stream, TRAIN);
-	if (R < 0) return R;
-
-{ StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
-	const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
-	const auto args = [&] { if constexpr (TRAIN) return rf; else return SurfelEvalFwd{rf, out_alpha, out_normal_view}; }();
-	auto render = refl ? surfel_render_fwd_wave_kernel<true, TRAIN> : surfel_render_fwd_wave_kernel<false, TRAIN>;
-	render<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(),
-	                                  background, TRAIN ? img.final_T : nullptr, TRAIN ? img.n_contrib : nullptr, out_color, out_others,
-	                                  out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, args); }
-	GSR_LAUNCH_CHECK(debug, stream);
-	const int rc = TRAIN ? early_key_sort(refl, width, height, stream) : 0;
-	return rc < 0 ? rc : R;
+	// one exit for both paths: with scratch the training forward also sorts the keys it wrote, whatever P (include/gsr_hip.h)
+	if (const int rc = TRAIN ? early_key_sort(refl, width, height, R, stream) : 0; rc < 0) return rc;
+	return R;
 }
 
 extern "C" int gsr_surfel_forward_refl(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,

@@ -19,6 +19,13 @@ NUM_CHANNELS = 3
 SINKABLE = frozenset(("means3D", "shs", "opacities", "scales", "rotations", "refl_strengths"))   # gradients a grad_sink may take
 
 
+def _sh_coeffs(sh):
+    """M, the SH coefficients per Gaussian: an omitted input is a 1-D empty placeholder, an empty scene's shs are (0, M, 3).  (The compiled
+    binding, gsr_torch_binding.cpp, takes M = 0 for any empty sh; the two differ only at P = 0, where the library reads nothing and
+    autograd drops the empty gradient, and gradient sinks always take this binding.)"""
+    return sh.size(1) if sh.dim() > 1 else 0
+
+
 def _forward_inputs(background, means3D, colors, refl_strengths, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix, sh,
                     campos):
     """The input checks of both forwards; returns the contiguous float32 inputs in the order of the C entries (background, means3D, sh,
@@ -33,7 +40,7 @@ def _forward_inputs(background, means3D, colors, refl_strengths, opacity, scales
             f32c(refl_strengths, "refl_strengths"), f32c(opacity, "opacity"), f32c(scales, "scales"), f32c(rotations, "rotations"),
             f32c(transMat_precomp, "transMat_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"),
             f32c(campos, "campos")]
-    return keep, (sh.size(1) if sh.numel() != 0 else 0)
+    return keep, _sh_coeffs(sh)
 
 
 def _refl_forward(refl, H, W, dev, keys):
@@ -151,7 +158,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, refl_streng
     `extra_normal_grad` (keyword-only extension): float32 (3,H,W), a second upstream gradient of planes 2..4 of the `others`
     output (the blended view-space normal) that the tile kernel adds to dL_dout_others[2:5] while loading it
     (gsr_surfel_backward_ex) — what the output tap `normal_view` of GaussianRasterizer receives."""
-    M = sh.size(1) if sh.numel() != 0 else 0
+    M = _sh_coeffs(sh)
     if grad_sink:
         unknown = set(grad_sink) - SINKABLE
         if unknown:
@@ -160,7 +167,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, refl_streng
         # the kernel has ONE accumulate switch for all six parameter gradients: fresh (uninitialised) tensors cannot be added to
         raise ValueError("accumulate=True needs a sink for every parameter gradient: " + ", ".join(sorted(SINKABLE)))
     unused = frozenset(unused)
-    if unused - {"colors", "transMat"} or ("colors" in unused and sh.numel() == 0) or ("transMat" in unused and scales.numel() == 0):
+    if unused - {"colors", "transMat"} or ("colors" in unused and _sh_coeffs(sh) == 0) or ("transMat" in unused and scales.dim() < 2):
         raise ValueError("unused: 'colors' needs shs as the colour input, 'transMat' needs scales / rotations; got %r" % (sorted(unused),))
     if extra_normal_grad is not None:
         hw = tuple(dL_dout_color.shape[1:])

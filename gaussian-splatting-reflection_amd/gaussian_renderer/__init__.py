@@ -131,39 +131,51 @@ class _DeferredReflection(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_final, g_refl_color, g_normal_world):
-        nv, bc, rs, cm, fv, cam, rgba = ctx.saved_tensors
-        H, W = nv.shape[1], nv.shape[2]
-        g_final = torch.zeros_like(bc) if g_final is None else g_final.float().contiguous()
-        g_refl_color = None if g_refl_color is None else g_refl_color.float().contiguous()
-        g_normal_world = None if g_normal_world is None else g_normal_world.float().contiguous()
-        g_nv, g_base, g_s = torch.empty_like(nv), torch.empty_like(bc), torch.empty_like(rs)
-        # the library writes (or, accumulate mode, adds to) every element of both gradients.  With a sink they go straight
-        # into caller-owned tensors and autograd gets None: no allocation, no `grad += new` pass
-        sink = ctx.sink.tensors if ctx.sink is not None else {}
-        accumulate = ctx.sink is not None and ctx.sink.accumulate
-        g_cm, g_fail = sink.get("cubemap"), sink.get("fail")
-        sunk_cm, sunk_fail = g_cm is not None, g_fail is not None
-        if accumulate and not (sunk_cm and sunk_fail):
-            raise ValueError("reflection grad sink: accumulate=True needs both 'cubemap' and 'fail' tensors")
-        for t, like, name in ((g_cm, cm, "cubemap"), (g_fail, fv, "fail")):
-            if t is not None and (tuple(t.shape) != tuple(like.shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != like.device):
-                raise ValueError(f"reflection grad sink '{name}': expected contiguous float32 {tuple(like.shape)} on {like.device}")
-        g_cm = torch.empty_like(cm) if g_cm is None else g_cm
-        g_fail = torch.empty_like(fv) if g_fail is None else g_fail
-        n_scratch = int(lib.gsr_deferred_reflection_scratch_floats(int(cm.shape[2]), W, H, 1 if REFLECTION_BACKWARD_BINNED else 0))
-        scratch = torch.empty(n_scratch, dtype=torch.float32, device=cm.device)
-        async_tail = ctx.sink is not None and ctx.sink.async_tail
-        if async_tail and not (sunk_cm and sunk_fail):
-            raise ValueError("reflection grad sink: async_tail=True needs both 'cubemap' and 'fail' tensors")
-        with torch.cuda.device(nv.device):
-            check(lib.gsr_deferred_reflection_backward_keys(ptr(nv), ptr(bc), ptr(rs), ptr(cam), ptr(cm), ptr(fv), cm.shape[2], W, H,
-                                                          ptr(g_final), ptr(g_refl_color), ptr(g_normal_world), ptr(g_nv), ptr(g_base),
-                                                          ptr(g_s), ptr(g_cm), ptr(g_fail), ptr(scratch), n_scratch, int(accumulate),
-                                                          int(async_tail), ptr(rgba), ptr(ctx.sort_keys), 0, stream_ptr(nv.device)),
-                  "gsr_deferred_reflection_backward")
-        if async_tail:
-            _gsr.side_hold(scratch, g_cm, g_fail, ctx.sort_keys)     # read / written on the side stream until side_join()
-        return g_nv, g_base, g_s, (None if sunk_cm else g_cm), (None if sunk_fail else g_fail), None, None
+        return _reflection_backward(ctx.saved_tensors, (g_final, g_refl_color, g_normal_world), ctx.sink, ctx.sort_keys) + (None, None)
+
+
+def _reflection_backward(saved, grads, sink, sort_keys, scratch=None):
+    """The deferred reflection's backward, for both autograd nodes.  saved: (normal_view, base_color, refl_strength, cubemap, fail_value,
+    cam, cubemap_rgba); grads: the upstream (g_final, g_refl_color, g_normal_world), None where nobody differentiates; sink: the GradSink
+    or None; sort_keys: the forward's keys or None; scratch: None, or the scratch the forward has already sorted the keys into
+    (keys_sorted).  Returns (g_normal_view, g_base, g_strength, g_cubemap | None, g_fail | None): None where the gradient went into the
+    sink.  The library writes (or, accumulate mode, adds to) every element of the cubemap and fail-value gradients; with a sink they go
+    straight into caller-owned tensors and autograd gets None: no allocation, no `grad += new` pass."""
+    nv, bc, rs, cm, fv, cam, rgba = saved
+    cont = lambda g: None if g is None else g.float().contiguous()
+    g_final, g_refl_color, g_normal_world = grads
+    g_final = torch.zeros_like(bc) if g_final is None else cont(g_final)
+    g_refl_color, g_normal_world = cont(g_refl_color), cont(g_normal_world)
+    H, W = nv.shape[1], nv.shape[2]
+    tensors = sink.tensors if sink is not None else {}
+    accumulate = sink is not None and sink.accumulate
+    async_tail = sink is not None and sink.async_tail
+    g_cm, g_fail = tensors.get("cubemap"), tensors.get("fail")
+    sunk_cm, sunk_fail = g_cm is not None, g_fail is not None
+    need_both = "=True needs both 'cubemap' and 'fail' tensors (accumulate / async_tail need both 'cubemap' and 'fail' tensors)"
+    if accumulate and not (sunk_cm and sunk_fail):
+        raise ValueError("reflection grad sink: accumulate" + need_both)
+    for t, like, name in ((g_cm, cm, "cubemap"), (g_fail, fv, "fail")):
+        if t is not None and (tuple(t.shape) != tuple(like.shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != like.device):
+            raise ValueError(f"reflection grad sink '{name}': expected contiguous float32 {tuple(like.shape)} on {like.device}")
+    if async_tail and not (sunk_cm and sunk_fail):
+        raise ValueError("reflection grad sink: async_tail" + need_both)
+    g_cm = torch.empty_like(cm) if g_cm is None else g_cm
+    g_fail = torch.empty_like(fv) if g_fail is None else g_fail
+    keys_sorted = scratch is not None
+    if not keys_sorted:
+        scratch = torch.empty(int(lib.gsr_deferred_reflection_scratch_floats(int(cm.shape[2]), W, H, 1 if REFLECTION_BACKWARD_BINNED else 0)),
+                              dtype=torch.float32, device=cm.device)
+    g_nv, g_base, g_s = torch.empty_like(nv), torch.empty_like(bc), torch.empty_like(rs)
+    with torch.cuda.device(nv.device):
+        check(lib.gsr_deferred_reflection_backward_keys(ptr(nv), ptr(bc), ptr(rs), ptr(cam), ptr(cm), ptr(fv), cm.shape[2], W, H,
+                                                        ptr(g_final), ptr(g_refl_color), ptr(g_normal_world), ptr(g_nv), ptr(g_base),
+                                                        ptr(g_s), ptr(g_cm), ptr(g_fail), ptr(scratch), int(scratch.numel()), int(accumulate),
+                                                        int(async_tail), ptr(rgba), ptr(sort_keys), int(keys_sorted), stream_ptr(nv.device)),
+              "gsr_deferred_reflection_backward")
+    if async_tail:
+        _gsr.side_hold(scratch, g_cm, g_fail, sort_keys)     # read / written on the side stream until side_join()
+    return g_nv, g_base, g_s, (None if sunk_cm else g_cm), (None if sunk_fail else g_fail)
 
 
 def deferred_reflection(normal_view, base_color, refl_strength_map, env_map, world_view_transform, HWK, R, T, grad_sink=None,
@@ -241,39 +253,9 @@ class _RasterizeReflect(torch.autograd.Function):
         radii, geom, binning, img, color, others, refl_map, cm, fv, cam, rgba = kept[ns:]
         settings = ctx.raster_settings
         cont = lambda g: None if g is None else g.float().contiguous()
-        H, W = color.shape[1], color.shape[2]
-        dev = color.device
-        # ---- 1. reflection backward (pixel kernel on this stream, texel-gradient tail beside what follows)
-        g_final = torch.zeros_like(color) if g_final is None else cont(g_final)
-        g_refl_color, g_normal_world = cont(g_refl_color), cont(g_normal_world)
-        rs = ctx.refl_sink.tensors if ctx.refl_sink is not None else {}
-        acc_refl = ctx.refl_sink is not None and ctx.refl_sink.accumulate
-        async_tail = ctx.refl_sink is not None and ctx.refl_sink.async_tail
-        g_cm, g_fail = rs.get("cubemap"), rs.get("fail")
-        sunk_cm, sunk_fail = g_cm is not None, g_fail is not None
-        if (acc_refl or async_tail) and not (sunk_cm and sunk_fail):
-            raise ValueError("reflection grad sink: accumulate / async_tail need both 'cubemap' and 'fail' tensors")
-        for tt, like, name in ((g_cm, cm, "cubemap"), (g_fail, fv, "fail")):
-            if tt is not None and (tuple(tt.shape) != tuple(like.shape) or tt.dtype != torch.float32 or not tt.is_contiguous() or tt.device != like.device):
-                raise ValueError(f"reflection grad sink '{name}': expected contiguous float32 {tuple(like.shape)} on {like.device}")
-        g_cm = torch.empty_like(cm) if g_cm is None else g_cm
-        g_fail = torch.empty_like(fv) if g_fail is None else g_fail
-        keys_sorted = ctx.scratch is not None
-        if keys_sorted:
-            scratch, n_scratch = ctx.scratch, int(ctx.scratch.numel())
-        else:
-            n_scratch = int(lib.gsr_deferred_reflection_scratch_floats(int(cm.shape[2]), W, H, 1 if REFLECTION_BACKWARD_BINNED else 0))
-            scratch = torch.empty(n_scratch, dtype=torch.float32, device=dev)
-        g_nv, g_base, g_s = torch.empty((3, H, W), dtype=torch.float32, device=dev), torch.empty_like(color), torch.empty_like(refl_map)
-        nv = others[2:5]                          # (contiguous: planes 2..4 of the [8,H,W] output)
-        with torch.cuda.device(dev):
-            check(lib.gsr_deferred_reflection_backward_keys(ptr(nv), ptr(color), ptr(refl_map), ptr(cam), ptr(cm), ptr(fv), cm.shape[2], W, H,
-                                                            ptr(g_final), ptr(g_refl_color), ptr(g_normal_world), ptr(g_nv), ptr(g_base), ptr(g_s),
-                                                            ptr(g_cm), ptr(g_fail), ptr(scratch), n_scratch, int(acc_refl), int(async_tail),
-                                                            ptr(rgba), ptr(ctx.sort_keys), int(keys_sorted), stream_ptr(dev)),
-                  "gsr_deferred_reflection_backward")
-        if async_tail:
-            _gsr.side_hold(scratch, g_cm, g_fail, ctx.sort_keys)     # read / written on the side stream until side_join()
+        # ---- 1. reflection backward (pixel kernel on this stream, texel-gradient tail beside what follows); others[2:5] is contiguous
+        g_nv, g_base, g_s, g_cm, g_fail = _reflection_backward((others[2:5], color, refl_map, cm, fv, cam, rgba), (g_final, g_refl_color, g_normal_world),
+                                                               ctx.refl_sink, ctx.sort_keys, ctx.scratch)
         # ---- 2. rasterizer backward: what reached its colour / reflection-strength outputs through the final image, plus the direct gradients
         # of those outputs (rare: nothing in the reference's losses reads them); the normal gradient travels as the tap's pointer
         g_color, g_refl_map, g_others = cont(g_color), cont(g_refl_map), cont(g_others)
@@ -302,7 +284,7 @@ class _RasterizeReflect(torch.autograd.Function):
             elif name in v.optional_grads and (saved.get(name) is None or saved[name].numel() == 0):
                 grad = None
             out.append(grad)
-        return tuple(out) + ((None if sunk_cm else g_cm), (None if sunk_fail else g_fail), None, None, None, None)
+        return tuple(out) + (g_cm, g_fail, None, None, None, None)
 
 
 def rasterize_reflect(rasterizer, env_map, world_view_transform, HWK, R, T, means3D, means2D, opacities, shs=None, colors_precomp=None,

@@ -311,6 +311,8 @@ int gsr_deferred_reflection_backward_keys(const float* normal_view, const float*
                                         float* g_cubemap, float* g_fail, float* scratch, size_t scratch_floats,
                                         int accumulate, int async_tail, const float* cubemap_rgba, const uint32_t* sort_keys,
                                         int keys_sorted, void* stream);
+/* gsr_side_join(s): stream s waits for all side-stream work enqueued so far on the current device — every asynchronous tail and every
+ * early key sort a gsr_surfel_forward_refl started with async_sort (also one whose backward never ran). */
 int gsr_side_join(void* stream);
 /* Extension: cubemap_rgba (NULL, or 6*L*L*4 floats, 16-byte aligned) receives a texel-interleaved copy [6][L][L][r,g,b,0] of
  * the cubemap, made by the call, from which the pixel kernel gathers each bilinear corner with one 16-byte load instead of

@@ -1,8 +1,9 @@
-"""The fused rasterize + reflect path (round 4): gaussian_renderer.rasterize_reflect / gsr_surfel_forward_refl / gsr_surfel_backward_refl
-run the deferred-reflection pixel code (gaussian_renderer/__init__.py:22-35,143-199 of the reference) inside the rasterizer's tile
-kernels.  It must give what the two-node path — GaussianRasterizer, then deferred_reflection(), each checked against the oracle and the
-float64 chain elsewhere — gives: the rasterizer's own outputs bit for bit (the same kernel code produced them), the reflection outputs and
-every gradient to rounding (the arithmetic is the same text compiled into another kernel; atomics land in another order)."""
+"""The fused rasterize + reflect path (round 4): gaussian_renderer.rasterize_reflect / gsr_surfel_forward_refl run the deferred-reflection
+pixel code (gaussian_renderer/__init__.py:22-35,143-199 of the reference) inside the rasterizer's forward tile kernel, and one autograd
+node runs the reflection backward and then the rasterizer backward.  It must give what the two-node path — GaussianRasterizer, then
+deferred_reflection(), each checked against the oracle and the float64 chain elsewhere — gives: the rasterizer's own outputs bit for bit
+(the same kernel code produced them), the reflection outputs and every gradient to rounding (the arithmetic is the same text compiled into
+another kernel; atomics land in another order)."""
 import numpy as np
 import pytest
 import torch
@@ -114,23 +115,30 @@ def test_fused_without_autograd_and_with_an_empty_scene():
     assert float((oe["final"] - ue["final"]).abs().max()) <= 5e-6
 
 
-@pytest.mark.parametrize("async_tail", [False, True])
-def test_fused_with_sinks_accumulates_two_views_like_the_two_node_path(async_tail):
+@pytest.mark.parametrize("async_tail,P", [(False, 20_000), (True, 20_000), (False, 0), (True, 0)],
+                         ids=["False", "True", "empty-False", "empty-True"])
+def test_fused_with_sinks_accumulates_two_views_like_the_two_node_path(async_tail, P):
     """As bench.py drives a batch: both sinks into one flat buffer, first view overwriting, second adding, the texel-gradient tail on the
-    side stream; the fused path against the two-node path, and both against the sum of two plain-autograd views."""
+    side stream; the fused path against the two-node path, and both against the sum of two plain-autograd views.  P = 0: the empty scene
+    takes the same tail (with async_tail the fused forward sorts the keys early into the backward's scratch); its per-Gaussian gradients
+    are empty, so the cubemap and fail-value gradients are compared.  Its reflection strength is zero, so only an upstream gradient of
+    refl_color reaches the cubemap; its normals are zero, so the reflection vector is the view ray and no pixel takes the fail value."""
     import _gsr
     from gsr_dist import FlatGrads
     W, H = 320, 200
     src, mask, cam, ct, bg = _scene(20_000, 43, -3.2, 32, W, H)
+    if P == 0:
+        src, mask = {k: (v if k in ("cubemap", "fail") else v[:0]) for k, v in src.items()}, mask[:0]
+    checked = PARAMS if P else ("cubemap", "fail")
     cam2 = S.look_at_camera(W, H, eye=(-0.5, 0.3, -0.6), target=(0, 0, 5))
     ct2 = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in cam2.items() if isinstance(v, np.ndarray)}
-    ups = _upstream(H, W, 4, ("final", "allmap"))
+    ups = _upstream(H, W, 4, ("final", "allmap") if P else ("final", "allmap", "refl_color"))
     plain = None
     for c, t in ((cam, ct), (cam2, ct2)):
         p = {k: v.clone().requires_grad_(True) for k, v in src.items()}
         _run(False, p, mask, c, t, W, H, bg, ups)
-        g = {k: p[k].grad.clone() for k in PARAMS}
-        plain = g if plain is None else {k: plain[k] + g[k] for k in PARAMS}
+        g = {k: p[k].grad.clone() for k in checked}
+        plain = g if plain is None else {k: plain[k] + g[k] for k in checked}
     flat = {}
     for fused in (False, True):
         p = {k: v.clone().requires_grad_(True) for k, v in src.items()}
@@ -142,9 +150,9 @@ def test_fused_with_sinks_accumulates_two_views_like_the_two_node_path(async_tai
         _gsr.side_join()
         torch.cuda.synchronize()
         flat[fused] = {k: fg.view(k).clone() for k in PARAMS}
-    for k in PARAMS:
+    for k in checked:
         a, b, c = flat[True][k].cpu().numpy(), flat[False][k].cpu().numpy(), plain[k].cpu().numpy()
-        assert np.isfinite(a).all(), k
+        assert np.isfinite(a).all() and (k == "fail" or np.abs(c).max() > 0), k      # (a reference of zeros would compare nothing)
         assert rel_maxnorm(a, b) <= 5e-5, k
         assert rel_maxnorm(a, c) <= 5e-5, k
 

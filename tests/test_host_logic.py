@@ -155,3 +155,16 @@ def test_bench_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
     assert np.array_equal(np.load(a / "grad_fail.npy"), arrays["grad_fail"].numpy())
     r = np.load(a / "radii.npy")
     assert 0 < r.size < 1_000_000 and np.isin(r, arrays["radii"].numpy().astype(np.float32)).all()
+
+
+def test_surfel_backward_takes_an_empty_scene_with_sh_input(hip_lib_built):
+    """An empty scene's SH tensor is (0, M, 3): the backward binding keeps M for its gradient (a FlatGrads sink has that shape) and does
+    not mistake it for the 1-D placeholder of an omitted input.  Past those checks the CPU tensors are refused."""
+    from diff_surfel_rasterization import _C
+    z = torch.empty(0)
+    args = lambda sh: (z, torch.empty(0, 3), z, z, z, torch.empty(0, 2), torch.empty(0, 4), 1.0, z, z, z, 1.0, 1.0, torch.zeros(3, 4, 4),
+                       torch.zeros(8, 4, 4), None, sh, 3, z, z, 0, z, z, False)
+    with pytest.raises(RuntimeError, match="must be a CUDA tensor"):
+        _C.rasterize_gaussians_backward(*args(torch.empty(0, 16, 3)), unused=("colors",), grad_sink={"shs": torch.empty(0, 16, 3)})
+    with pytest.raises(ValueError, match="'colors' needs shs as the colour input"):
+        _C.rasterize_gaussians_backward(*args(z), unused=("colors",))
