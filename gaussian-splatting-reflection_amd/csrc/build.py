@@ -71,9 +71,9 @@ def _digest():
     return h.hexdigest()
 
 
-def _compile(src):
-    obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
-    cmd = [HIPCC] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-c", os.path.join(HERE, src), "-o", obj]
+def _compile(src, obj_dir=OBJ_DIR, defines=()):
+    obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
+    cmd = [HIPCC] + FLAGS + EXTRA_FLAGS.get(src, []) + list(defines) + ["-c", os.path.join(HERE, src), "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
@@ -89,17 +89,31 @@ def build(force=False, verbose=True):
     if not force and os.path.exists(OUT) and os.path.exists(stamp) and open(stamp).read().strip() == dig:
         return OUT
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
-    with concurrent.futures.ThreadPoolExecutor(max_workers=4) as ex:
-        objs = list(ex.map(_compile, srcs))
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    _compile_and_link(srcs, OBJ_DIR, OUT)
     with open(stamp, "w") as fh:
         fh.write(dig)
     if verbose:
         print(f"built {OUT}")
     return OUT
+
+
+def _compile_and_link(srcs, obj_dir, out, defines=()):
+    """Every translation unit in `srcs` to obj_dir (at most 4 hipcc jobs at a time), linked into `out`."""
+    with concurrent.futures.ThreadPoolExecutor(max_workers=4) as ex:
+        objs = list(ex.map(lambda src: _compile(src, obj_dir, defines), srcs))
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    return out
+
+
+def build_variant(out_dir, defines):
+    """Build a variant of the library with extra preprocessor `defines` ({"NAME": value}) into out_dir/libgsr_hip.so, for tests that
+    compare builds (load it in a fresh process through GSR_LIB).  Every translation unit gets the defines: the headers they share
+    (gsr_refl.hpp is in gsr_cubemap.hip and gsr_surfel.hip) must see one setting.  libgsr_hip.so, _obj/ and the digest are not touched."""
+    os.makedirs(out_dir, exist_ok=True)
+    srcs = [s for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
+    return _compile_and_link(srcs, out_dir, os.path.join(out_dir, "libgsr_hip.so"), ["-D%s=%s" % kv for kv in sorted(defines.items())])
 
 
 BINDING_OUT = os.path.join(PKG, "_gsr_C.so")

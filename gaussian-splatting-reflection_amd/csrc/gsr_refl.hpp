@@ -10,8 +10,10 @@ namespace gsr {
 // Reciprocals and square roots of this per-pixel code.  Since round 4 it also runs inside the rasterizer's tile kernels, which are bound by
 // the NUMBER of vector instructions they issue: an IEEE-rounded fp32 division costs ~10 instructions (v_div_scale x2, v_rcp, 4 FMAs,
 // v_div_fmas, v_div_fixup) and the reflection code had sixteen of them per pixel plus two IEEE square roots.  GSR_REFL_FAST = 1: the
-// 1-ulp hardware forms (v_rcp_f32, v_rsq_f32, v_sqrt_f32) — the results move by ~1e-7 relative, far inside what the float64 chain of the
-// tests allows (2e-5 absolute on the final colour).  0: IEEE division / sqrt as in rounds 1-3.
+// 1-ulp hardware forms (v_rcp_f32, v_rsq_f32, v_sqrt_f32).  The direction moves by ~1e-7 relative, but the lookup scales it by L/2 into
+// texel coordinates: measured against the IEEE build (tests/test_gpu_refl_seams.py), the reflected colour moves by up to 1.7e-6 at L = 16,
+// 1.4e-5 at L = 128 and 1.1e-4 at L = 1024, the normal gradient by 5.7e-6 / 5.3e-5 / 3.5e-4 of its scale — the size of float32's own
+// texel-coordinate error, inside the tests' bar against float64 (2e-5 max(1, L/128) on the colour).  0: IEEE division / sqrt as in rounds 1-3.
 #ifndef GSR_REFL_FAST
 #define GSR_REFL_FAST 1
 #endif

@@ -93,8 +93,9 @@ class OracleCubemap(torch.autograd.Function):
         return torch.from_numpy(gin), torch.from_numpy(gcm), torch.from_numpy(gf)
 
 
-def reference_chain(normal_view, base, strength, cubemap, fail, cam, W, H):
-    """gaussian_renderer/__init__.py:22-35,148,178-179,197-199 + utils/general_utils.py:177-197, float64 on the CPU."""
+def reference_dirs(normal_view, cam, W, H):
+    """The geometric part of reference_chain: (shading normal rn [H,W,3], unit view ray rd [H,W,3], reflected direction refl [H,W,3]),
+    in the dtype of normal_view (float64 for the checks)."""
     wvt = torch.from_numpy(cam["viewmatrix"]).double()
     R = torch.from_numpy(cam["R"]).double()
     T = torch.from_numpy(cam["T"]).double()
@@ -110,6 +111,12 @@ def reference_chain(normal_view, base, strength, cubemap, fail, cam, W, H):
     rd = pw - rays_o[None]
     rd = (rd / torch.norm(rd, dim=1, keepdim=True)).reshape(H, W, 3)
     refl = rd - 2 * rn * torch.sum(rd * rn, dim=-1, keepdim=True)
+    return rn, rd, refl
+
+
+def reference_chain(normal_view, base, strength, cubemap, fail, cam, W, H):
+    """gaussian_renderer/__init__.py:22-35,148,178-179,197-199 + utils/general_utils.py:177-197, float64 on the CPU."""
+    rn, _, refl = reference_dirs(normal_view, cam, W, H)
     col = torch.sigmoid(OracleCubemap.apply(refl.reshape(-1, 3), cubemap, fail).permute(1, 0))
     col = col.reshape(H, W, 3).permute(2, 0, 1)
     final = (1 - strength) * base + strength * col
