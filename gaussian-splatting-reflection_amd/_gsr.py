@@ -143,6 +143,13 @@ def _load():
     lib.gsr_profile_enable.argtypes = [c_int]
     lib.gsr_profile_collect.restype = c_int
     lib.gsr_profile_collect.argtypes = [P, P]
+    if hasattr(lib, "gsr_knn_mean_dist"):
+        # (added under ABI 102 without a version change: a library built before it lacks these two, and simple_knn refuses to import
+        # while the rasterizers keep working)
+        lib.gsr_knn_scratch_bytes.restype = c_size_t
+        lib.gsr_knn_scratch_bytes.argtypes = [c_int]
+        lib.gsr_knn_mean_dist.restype = c_int
+        lib.gsr_knn_mean_dist.argtypes = [c_int, P, P, P, c_size_t, P]
     return lib
 
 
@@ -182,7 +189,7 @@ EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_b
             "gsr_deferred_reflection_backward_accum", "gsr_deferred_reflection_backward_ex", "gsr_deferred_reflection_forward_ex", "gsr_side_join", "gsr_normal_world_forward", "gsr_normal_world_backward", "gsr_gauss_forward", "gsr_gauss_backward", "gsr_gauss_backward_accum",
             "gsr_mark_visible", "gsr_debug_fetch", "gsr_cubemap_forward", "gsr_cubemap_backward", "gsr_deferred_reflection_forward",
             "gsr_deferred_reflection_scratch_floats", "gsr_deferred_reflection_backward", "gsr_ssim_l1_scratch_floats", "gsr_ssim_l1_forward", "gsr_ssim_l1_backward", "gsr_normal_loss_scratch_floats", "gsr_normal_loss_forward", "gsr_normal_loss_backward", "gsr_adam_step", "gsr_adam_step_range", "gsr_densification_stats", "gsr_gather_rows", "gsr_split_children", "gsr_surface_forward", "gsr_surface_backward", "gsr_profile_enable",
-            "gsr_profile_collect", "gsr_set_option"]
+            "gsr_profile_collect", "gsr_set_option", "gsr_knn_scratch_bytes", "gsr_knn_mean_dist"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

@@ -398,6 +398,16 @@ int gsr_gather_rows(const float* src, float* dst, const int* row_map, uint64_t n
 int gsr_split_children(int n_children, int scale_dims, int N, const int* parent, const float* xyz, const float* scaling,
                        const float* rotation, const float* noise, float* child_xyz, float* child_scaling, void* stream);
 
+/* Point-cloud initialisation: simple_knn.distCUDA2 (scene/gaussian_model.py:20, 170 of the reference).
+ * gsr_knn_mean_dist: mean_dist[i] = (b0 + b1 + b2) / 3 in float32, b0 <= b1 <= b2 the three smallest squared distances
+ *   dx*dx + dy*dy + dz*dz (d = other - self, float32) from point i to the OTHER points (excluded by index: a duplicate is a
+ *   neighbour at distance 0); a missing neighbour (P < 4) counts as FLT_MAX.  Exact search: the output does not depend on the
+ *   input order.  points float[P,3] row-major, mean_dist float[P]; scratch: device memory of at least gsr_knn_scratch_bytes(P)
+ *   bytes (the library allocates nothing).  Runs on `stream`, no host synchronisation.  0 <= P < 2^30; P = 0 does nothing.
+ * gsr_knn_scratch_bytes: the scratch size for P points (0 for P <= 0 or P >= 2^30).  Added in ABI 102 without a version change. */
+size_t gsr_knn_scratch_bytes(int P);
+int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Normal-consistency term of the training loss (reference train.py:182-189): normal_error = (1 - sum_c rend_normal[c] *
  * surf_normal[c]) [* mask], loss = lambda * mean(normal_error).  rend_normal, surf_normal: [3,H,W]; mask: [H,W] (1,H,W) or NULL.
  * Forward: sum2[0] = sum over pixels of normal_error (sum2[1] = 0), scratch = gsr_normal_loss_scratch_floats() floats.
