@@ -846,6 +846,7 @@ surfel_render_bwd_rows_body(const uint2* __restrict__ ranges, const uint32_t* __
 	__shared__ uint8_t s_list[64];                      // by slab slot (a row's slots are consecutive, in the order it visits them: last entry first): the batch position
 #endif
 	static_assert(S_CAP + 1 < 64, "slab slots are packed into 6 bits");
+	static_assert(S_CAP >= 32, "a chunk always takes the first 8-position group of its batch, up to 4 rows x 8 = 32 pairs");
 
 	SurfelBwdPix st;
 	surfel_bwd_init(st, inside, pix, HW, bg, final_Ts, n_contrib, dL_dpixels, dL_depths, dL_drefl_map, dL_dnormal_extra);
