@@ -3,7 +3,7 @@
 // of its eight parameter groups (scene/gaussian_model.py:196-209, torch.optim.Adam(lr=0, eps=1e-15)).
 //
 // Both are streaming, HBM-bound passes:
-//   * SSIM + L1: one 16x16 output tile per workgroup; the 26x26 halo of both images is staged in LDS once, the 11x11
+//   * SSIM + L1: one 32x32 output tile per workgroup; the 42x42 halo of both images is staged in LDS once, the 11x11
 //     Gaussian window (sigma 1.5, zero padding 5: F.conv2d(padding=5, groups=C)) is applied separably to the five moment
 //     planes x, y, x^2, y^2, xy from LDS, and the kernel leaves only what the backward needs: the three partial-derivative
 //     planes of the SSIM map and two block-reduced sums.  ~8 B read + 12 B written per pixel-channel.

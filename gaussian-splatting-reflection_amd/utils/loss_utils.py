@@ -52,6 +52,8 @@ class _SsimL1(torch.autograd.Function):
         # l1.backward(retain_graph=True) for the render graph, then ssim.backward(), two graphs in the reference — reaches it twice, the
         # second time after autograd has released the saved tensors (x, y are inputs and maps an intermediate: no reference cycle)
         ctx.kept = (x, y, maps)
+        ctx.versions = (x._version, y._version)
+        ctx.ran = False
         ctx.in_shape = img1.shape
         ctx.want_map = want_map
         if want_map:
@@ -64,10 +66,20 @@ class _SsimL1(torch.autograd.Function):
         global _last_sums
         if _last_sums is not None and _last_sums[4].grad_fn is not None and getattr(_last_sums[4].grad_fn, "kept", None) is ctx.kept:
             _last_sums = None          # consumed: a later l1_loss / ssim call on the same tensors starts a fresh forward (and a fresh graph)
-        try:
-            x, y, maps = ctx.saved_tensors      # (first pass: with autograd's check that nothing was modified in place since the forward)
-        except RuntimeError:
-            x, y, maps = ctx.kept               # a second pass through the shared node
+        if not ctx.ran:
+            # first pass: autograd's own checks apply (an input modified in place since the forward raises here)
+            x, y, maps = ctx.saved_tensors
+            ctx.ran = True
+        else:
+            try:
+                x, y, maps = ctx.saved_tensors  # a later pass with the buffers retained (retain_graph=True)
+            except RuntimeError as ex:
+                if "freed" not in str(ex):
+                    raise
+                x, y, maps = ctx.kept           # a later pass through the shared node after autograd released the buffers
+                if (x._version, y._version) != ctx.versions:
+                    raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace "
+                                       "operation: an input of the fused SSIM + L1 loss changed after its forward") from ex
         C, H, W = x.shape
         grad = torch.empty_like(x)
         w = f32c(g_sums, "grad_sums")
