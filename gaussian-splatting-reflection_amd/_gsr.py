@@ -277,6 +277,66 @@ def f32c(t, name):
     return t.contiguous()
 
 
+# ------------------------------------------------------------------ what the two rasterizer bindings share
+# (diff_gaussian_rasterization._C and diff_surfel_rasterization._C, over their ctypes paths)
+
+def sh_coeffs(sh, empty_scene_counts=True):
+    """M, the SH coefficients per Gaussian: an omitted input is a 1-D empty placeholder, an empty scene's shs are (0, M, 3).  Variant S takes
+    M from the shape; variant G (empty_scene_counts=False) takes 0 for any empty sh, as the reference's RasterizeGaussiansCUDA does, so its
+    dL_dsh of an empty scene is (0, 0, 3).  (The compiled binding, gsr_torch_binding.cpp, takes M = 0 for any empty sh in both variants; the
+    two differ only at P = 0, where the library reads nothing and autograd drops the empty gradient, and gradient sinks always take ctypes.)"""
+    if empty_scene_counts:
+        return sh.size(1) if sh.dim() > 1 else 0
+    return sh.size(1) if sh.numel() != 0 else 0
+
+
+def check_backward_keywords(grad_sink, accumulate, unused, sinkable, M, unused_needs, unused_message):
+    """The keyword-only extensions of both `rasterize_gaussians_backward`: `grad_sink` names come from `sinkable`; `accumulate` needs a sink
+    for every one of them (minus shs without SH input): the kernel has ONE accumulate switch for all parameter gradients, and fresh
+    (uninitialised) tensors cannot be added to; `unused_needs` maps each name `unused` may hold to whether the input that makes that
+    gradient unused was supplied.  Returns `unused` as a frozenset."""
+    if grad_sink:
+        unknown = set(grad_sink) - sinkable
+        if unknown:
+            raise ValueError(f"grad sink: unknown gradient name(s) {sorted(unknown)}; expected a subset of {sorted(sinkable)}")
+    if accumulate and (not grad_sink or not set(grad_sink) >= (sinkable - ({"shs"} if M == 0 else set()))):
+        raise ValueError("accumulate=True needs a sink for every parameter gradient: " + ", ".join(sorted(sinkable)))
+    unused = frozenset(unused)
+    if unused - set(unused_needs) or not all(unused_needs[name] for name in unused):
+        raise ValueError(unused_message % (sorted(unused),))
+    return unused
+
+
+def grad_allocator(grad_sink, dev, mk0):
+    """mk(shape, sink_name=None, **kw) for the outputs of a backward: the caller-owned tensor `grad_sink[sink_name]` where there is one (the
+    kernel then writes that gradient straight into it), checked for shape, dtype, device and alignment; otherwise mk0(shape, **kw)."""
+    def mk(shape, sink_name=None, **kw):
+        t = grad_sink.get(sink_name) if (grad_sink and sink_name is not None) else None
+        if t is not None:
+            if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"grad sink '{sink_name}': expected contiguous float32 {tuple(shape)} on {dev}, got {tuple(t.shape)} {t.dtype}")
+            if t.data_ptr() % 16:
+                # the kernel stores dL_dsh / dL_drot rows as float4 (include/gsr_hip.h, "alignment"); the C ABI refuses too
+                raise ValueError(f"grad sink '{sink_name}': storage must be 16-byte aligned (got {t.data_ptr():#x}); pad the slices of a packed buffer "
+                                 "to multiples of 4 floats as gsr_dist.FlatGrads does")
+            return t
+        return mk0(shape, **kw)
+    return mk
+
+
+def mark_visible(means3D, viewmatrix, projmatrix):
+    """`_C.mark_visible` of both variants (markVisible of the references' rasterize_points.cu)."""
+    if PYBIND is not None:
+        return PYBIND.mark_visible(means3D, viewmatrix, projmatrix)
+    P = means3D.size(0)
+    present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
+    if P != 0:
+        m3, vm, pm = f32c(means3D, "means3D"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix")
+        with torch.cuda.device(means3D.device):
+            check(lib.gsr_mark_visible(P, ptr(m3), ptr(vm), ptr(pm), ptr(present), stream_ptr(means3D.device)), "gsr_mark_visible")
+    return present
+
+
 class Workspace:
     """The three opaque byte buffers of one forward call (geomBuffer, binningBuffer, imgBuffer of
     DSR rasterize_points.cu:102-108), allocated by torch when the library asks for them."""

@@ -9,6 +9,7 @@
 // A 16x16 tile is one 256-thread workgroup = 4 waves, each wave owning an 8x8 pixel quadrant so that
 // wave-uniform skips ("no lane of this wave touches Gaussian j") fire as often as possible.
 #include "gsr_internal.hpp"
+#include "gsr_tile_walk.hpp"
 #include "gsr_sort.hpp"
 #include "gsr_math.hpp"
 
@@ -23,14 +24,6 @@ namespace gsr {
 #define GA_MEAN2DP 10
 #define GA_CONIC 12
 #define GA_OPAC 15
-
-struct GaussCam {
-	const float* view;
-	const float* proj;
-	const float* campos;
-	int W, H;
-	float tan_fovx, tan_fovy, focal_x, focal_y;
-};
 
 // computeCov3D (DGR forward.cu:114-148): quaternion used as given (not normalised).
 __device__ __forceinline__ void cov3d_from_scale_rot(const float* __restrict__ scale, float mod, const float* __restrict__ rot, float* cov3D) {
@@ -54,7 +47,7 @@ struct Cov2DCtx {
 	float tx, ty, tz, txtz, tytz, limx, limy;
 	M3 T, Wm;
 };
-__device__ __forceinline__ Cov2DCtx cov2d_ctx(float mx, float my, float mz, const GaussCam& c) {
+__device__ __forceinline__ Cov2DCtx cov2d_ctx(float mx, float my, float mz, const RasterCam& c) {
 #pragma clang fp contract(off)
 	const float* vm = c.view;
 	Cov2DCtx k;
@@ -83,7 +76,7 @@ __device__ __forceinline__ bool
 gauss_preprocess_one(int idx, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
                      const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
                      const float* __restrict__ cov3D_precomp, const float* __restrict__ colors_precomp, const float* __restrict__ normals,
-                     const float* __restrict__ refl, const GaussCam& cam, int* __restrict__ radii, const GeomState& g, int gx, int gy, int prefiltered,
+                     const float* __restrict__ refl, const RasterCam& cam, int* __restrict__ radii, const GeomState& g, int gx, int gy, int prefiltered,
                      int antialiasing, float4* o, float* cov3D) {
 #pragma clang fp contract(off)
 	radii[idx] = 0;
@@ -176,7 +169,7 @@ __global__ void __launch_bounds__(256)
 gauss_preprocess_kernel(int P, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
                         const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
                         const float* __restrict__ cov3D_precomp, const float* __restrict__ colors_precomp, const float* __restrict__ normals,
-                        const float* __restrict__ refl, GaussCam cam, int* __restrict__ radii, GeomState g, int gx, int gy, int prefiltered,
+                        const float* __restrict__ refl, RasterCam cam, int* __restrict__ radii, GeomState g, int gx, int gy, int prefiltered,
                         int antialiasing) {
 	const int idx = blockIdx.x * 256 + threadIdx.x;
 	// look-back state of the depth sort that follows (gsr_sort.hpp): cleared here instead of by a dispatch of its own
@@ -224,13 +217,11 @@ __device__ __forceinline__ lmask gauss_pair(float4 r0, float conz, float opac, f
 // renderCUDA forward (DGR forward.cu:274-411), wave-per-quadrant form (see surfel_render_fwd_wave_kernel in
 // gsr_surfel.hip for the design: one wave = one 8x8 pixel block, ballot-compacted private work list from
 // conservative cull bounds, per-Gaussian record through the scalar memory path, no workgroup barriers).
-#define G_WBATCH 64
 #define G_SUB 16      // hits between two flushes of the backward's gradient slab (power of two)
 template <bool INVDEPTH>
 // The vote tests the cull ellipse against the box of the wave's pixel CENTRES, and alpha >= 1/255 is exactly q <= q_max for
 // this variant (the screen-space blur is part of the conic), so the 5 % + 0.1 margin on q_max already makes the record
-// conservative; the pad only covers the float rounding of the edge minimisation.
-#define G_CULL_PAD 0.05f
+// conservative; CULL_PAD only covers the float rounding of the edge minimisation.
 __global__ void __launch_bounds__(64)
 gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ point_list, int W, int H, int tiles_x, int ntiles,
                              const float4* __restrict__ rec, const float4* __restrict__ bbox, int cull, const float* __restrict__ bg,
@@ -239,11 +230,10 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
                              unsigned long long* __restrict__ blend_mask, size_t mask_stride) {
 	const uint32_t slot = xcd_slot(blockIdx.x);   // dispatch slot -> (tile, quadrant), longest lists first
 	if (slot >= (uint32_t)ntiles * 4u) return;
-	const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_order[slot >> 2]), quad = slot & 3u;   // (readfirstlane: the compiler cannot see that the loaded tile id is wave-uniform)
-	const int tile_x = tile % tiles_x, tile_y = tile / tiles_x;
-	const int lane = threadIdx.x;
-	const int bx0 = tile_x * 16 + (quad & 1) * 8, by0 = tile_y * 16 + (quad >> 1) * 8;
-	if (bx0 >= W || by0 >= H) return;
+	const TileBlock blk = tile_block(tile_order, slot, tiles_x);
+	if (blk.bx0 >= W || blk.by0 >= H) return;
+	const uint32_t tile = blk.tile, quad = blk.quad;
+	const int lane = threadIdx.x, bx0 = blk.bx0, by0 = blk.by0;
 	const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
 	const bool inside = px < W && py < H;
 	const float pixx = (float)px, pixy = (float)py;
@@ -251,50 +241,42 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 	const int count = (int)(range.y - range.x);
 	const float qx0 = (float)bx0, qy0 = (float)by0, qx1 = qx0 + 7.0f, qy1 = qy0 + 7.0f;
 
-	__shared__ uint32_t s_hid[G_WBATCH];
-	__shared__ uint32_t s_hj[G_WBATCH];
+	__shared__ uint32_t s_hid[WBATCH];
+	__shared__ uint32_t s_hj[WBATCH];
 
 	lmask done = ~LMASK(px < W) | ~LMASK(py < H);   // lanes outside the image never blend
 	float T = 1.0f;
 	uint32_t last_contributor = 0;
 	float C0 = 0, C1 = 0, C2 = 0, N0 = 0, N1 = 0, N2 = 0, RS = 0, ID = 0;
-	const size_t batch0 = (size_t)(range.x / G_WBATCH) + tile;     // where this tile's batches sit in blend_mask (see BinningState)
+	const size_t batch0 = (size_t)(range.x / WBATCH) + tile;     // where this tile's batches sit in blend_mask (see BinningState)
 
-	for (int base = 0; base < count; base += G_WBATCH) {
+	for (int base = 0; base < count; base += WBATCH) {
 		if (done == ~0ull) break;
-		const int nb = min(G_WBATCH, count - base);
+		const int nb = min(WBATCH, count - base);
 		bool hit = lane < nb;
 		uint32_t id = 0;
 		if (hit) {
 			id = point_list[range.x + (uint32_t)(base + lane)];
 			if (cull) {
-				hit = cull_hit(bbox[2 * id], bbox[2 * id + 1], qx0 - G_CULL_PAD, qx1 + G_CULL_PAD, qy0 - G_CULL_PAD, qy1 + G_CULL_PAD);
+				hit = cull_hit(bbox[2 * id], bbox[2 * id + 1], qx0 - CULL_PAD, qx1 + CULL_PAD, qy0 - CULL_PAD, qy1 + CULL_PAD);
 			}
 		}
 		const unsigned long long mm = __ballot(hit);
 		const int nh = __popcll(mm);
 		if (nh == 0) continue;
-		const int kown = __popcll(mm & ((1ull << lane) - 1ull));   // this lane's entry is hit number kown (if it is a hit)
-		if (hit) {
-			s_hid[kown] = id;
-			s_hj[kown] = (uint32_t)lane;
-		}
-		__syncthreads();
-		const uint32_t hid = lane < nh ? s_hid[lane] : 0u;
-		const uint32_t hj = lane < nh ? s_hj[lane] : 0u;
+		const HitList hl = compact_hits(hit, mm, nh, lane, id, (uint32_t)lane, s_hid, s_hj);
+		const int kown = hl.kown;                 // this lane's entry is hit number kown (if it is a hit)
+		const uint32_t hid = hl.a, hj = hl.b;
 		__syncthreads();
 		unsigned long long blendk = 0ull;    // hits that blended into at least one pixel of the block
 		// two SGPR record buffers ping-pong so that the next record's s_load stays in flight for a whole pair
-		struct Rec { float4 r0, r1, r2, r3; };
-		auto fetch = [&](int k) -> Rec {
-			const float4* q = rec + (size_t)__builtin_amdgcn_readlane(hid, k) * G_REC_F4;
-			return Rec{q[0], q[1], q[2], q[3]};
-		};
+		using Rec = TileRec<G_REC_F4>;
+		auto fetch = [&](int k) { return fetch_rec<G_REC_F4>(rec, hid, k); };
 		auto blend = [&](int k, const Rec& R, auto&& prefetch_next) -> bool {   // true: every pixel of the block has retired
 			const uint32_t contributor = (uint32_t)(base + (int)__builtin_amdgcn_readlane(hj, k) + 1);
 			// straight-line for all 64 lanes: a rejected pair blends with weight 0 (see surfel_render_fwd_wave_kernel)
 			float dx, dy, G, alpha;
-			const lmask live = gauss_pair(R.r0, R.r1.x, R.r1.y, pixx, pixy, dx, dy, G, alpha) & ~done;
+			const lmask live = gauss_pair(R.f[0], R.f[1].x, R.f[1].y, pixx, pixy, dx, dy, G, alpha) & ~done;
 			__builtin_amdgcn_sched_barrier(0);
 			prefetch_next();
 			__builtin_amdgcn_sched_barrier(0);
@@ -304,10 +286,10 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 			done |= sat;
 			if (ok != 0ull) {
 				const float w = selm0(ok, alpha * T);
-				C0 = fmaf(R.r1.z, w, C0); C1 = fmaf(R.r1.w, w, C1); C2 = fmaf(R.r2.x, w, C2);
-				N0 = fmaf(R.r2.y, w, N0); N1 = fmaf(R.r2.z, w, N1); N2 = fmaf(R.r2.w, w, N2);
-				RS = fmaf(R.r3.x, w, RS);
-				if (INVDEPTH) ID = fmaf(R.r3.y, w, ID);
+				C0 = fmaf(R.f[1].z, w, C0); C1 = fmaf(R.f[1].w, w, C1); C2 = fmaf(R.f[2].x, w, C2);
+				N0 = fmaf(R.f[2].y, w, N0); N1 = fmaf(R.f[2].z, w, N1); N2 = fmaf(R.f[2].w, w, N2);
+				RS = fmaf(R.f[3].x, w, RS);
+				if (INVDEPTH) ID = fmaf(R.f[3].y, w, ID);
 				T = selm(ok, test_T, T);
 				last_contributor = selmu(ok, contributor, last_contributor);
 				blendk |= 1ull << k;
@@ -322,7 +304,7 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 		}
 		// the batch's blend mask (bit = position in the batch): the backward tile kernel walks exactly these entries
 		const lmask blended = __ballot(hit && ((blendk >> kown) & 1ull) != 0ull);
-		if (lane == 0) blend_mask[(size_t)quad * mask_stride + batch0 + (size_t)(base / G_WBATCH)] = blended;
+		if (lane == 0) blend_mask[(size_t)quad * mask_stride + batch0 + (size_t)(base / WBATCH)] = blended;
 	}
 	if (inside) {
 		const size_t HW = (size_t)H * W;
@@ -366,11 +348,10 @@ gauss_render_bwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
                              size_t mask_stride) {
 	const uint32_t slot = xcd_slot(blockIdx.x);   // dispatch slot -> (tile, quadrant), longest lists first
 	if (slot >= (uint32_t)ntiles * 4u) return;
-	const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_order[slot >> 2]), quad = slot & 3u;   // (readfirstlane: the compiler cannot see that the loaded tile id is wave-uniform)
-	const int tile_x = tile % tiles_x, tile_y = tile / tiles_x;
-	const int lane = threadIdx.x;
-	const int bx0 = tile_x * 16 + (quad & 1) * 8, by0 = tile_y * 16 + (quad >> 1) * 8;
-	if (bx0 >= W || by0 >= H) return;
+	const TileBlock blk = tile_block(tile_order, slot, tiles_x);
+	if (blk.bx0 >= W || blk.by0 >= H) return;
+	const uint32_t tile = blk.tile, quad = blk.quad;
+	const int lane = threadIdx.x, bx0 = blk.bx0, by0 = blk.by0;
 	const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
 	const bool inside = px < W && py < H;
 	const float pixx = (float)px, pixy = (float)py;
@@ -379,8 +360,8 @@ gauss_render_bwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 	const size_t HW = (size_t)H * W;
 	const size_t pix = (size_t)W * py + px;
 	__shared__ float s_slab[G_SUB * 4 * G_ACC_F];   // [hit in sub-batch][16-lane row][16 floats]
-	__shared__ uint32_t s_hid[G_WBATCH];
-	__shared__ uint32_t s_hj[G_WBATCH];
+	__shared__ uint32_t s_hid[WBATCH];
+	__shared__ uint32_t s_hj[WBATCH];
 
 	const lmask inside_m = LMASK(px < W) & LMASK(py < H);
 	// where this lane parks its row totals: quad q of a row holds value slot(q) of every reduced register (row_reduce_slot)
@@ -412,33 +393,24 @@ gauss_render_bwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 	if (wave_last == 0) return;
 	// back to front through the forward's batches; per batch the forward left the mask of the entries that blended into this
 	// block: only those are differentiated (no footprint vote, no cull-record traffic, no pair that cannot contribute)
-	const size_t batch0 = (size_t)(range.x / G_WBATCH) + tile;
-	for (int b = (min(wave_last, count) - 1) / G_WBATCH; b >= 0; b--) {
+	const size_t batch0 = (size_t)(range.x / WBATCH) + tile;
+	for (int b = (min(wave_last, count) - 1) / WBATCH; b >= 0; b--) {
 		const unsigned long long bits = blend_mask[(size_t)quad * mask_stride + batch0 + (size_t)b];
 		if (bits == 0ull) continue;
-		const int pos = b * G_WBATCH + (G_WBATCH - 1 - lane);      // lane l looks at batch slot 63 - l: ascending lanes = descending positions
-		const bool hit = ((bits >> (G_WBATCH - 1 - lane)) & 1ull) != 0ull && pos < wave_last;
+		const int pos = b * WBATCH + (WBATCH - 1 - lane);      // lane l looks at batch slot 63 - l: ascending lanes = descending positions
+		const bool hit = ((bits >> (WBATCH - 1 - lane)) & 1ull) != 0ull && pos < wave_last;
 		const unsigned long long mm = __ballot(hit);
 		const int nh = __popcll(mm);
 		if (nh == 0) continue;
-		if (hit) {
-			const int k = __popcll(mm & ((1ull << lane) - 1ull));
-			s_hid[k] = point_list[range.x + (uint32_t)pos];
-			s_hj[k] = (uint32_t)pos;
-		}
-		__syncthreads();
-		const uint32_t hid = lane < nh ? s_hid[lane] : 0u;
-		const uint32_t hj = lane < nh ? s_hj[lane] : 0u;
+		const HitList hl = compact_hits(hit, mm, nh, lane, hit ? point_list[range.x + (uint32_t)pos] : 0u, (uint32_t)pos, s_hid, s_hj);
+		const uint32_t hid = hl.a, hj = hl.b;
 		unsigned long long touched = 0ull;
-		struct Rec { float4 r0, r1, r2, r3; };
-		auto fetch = [&](int k) -> Rec {
-			const float4* q = rec + (size_t)__builtin_amdgcn_readlane(hid, k) * G_REC_F4;
-			return Rec{q[0], q[1], q[2], q[3]};
-		};
+		using Rec = TileRec<G_REC_F4>;
+		auto fetch = [&](int k) { return fetch_rec<G_REC_F4>(rec, hid, k); };
 		auto differentiate = [&](int k, const Rec& R, auto&& prefetch_next) {
 			const int contributor = (int)__builtin_amdgcn_readlane(hj, k);   // 0-based position in the tile's list
 			float dx, dy, Gp, alpha_p;
-			const lmask ok = gauss_pair(R.r0, R.r1.x, R.r1.y, pixx, pixy, dx, dy, Gp, alpha_p) & LMASK(contributor < last_contributor) & inside_m;
+			const lmask ok = gauss_pair(R.f[0], R.f[1].x, R.f[1].y, pixx, pixy, dx, dy, Gp, alpha_p) & LMASK(contributor < last_contributor) & inside_m;
 			__builtin_amdgcn_sched_barrier(0);
 			prefetch_next();
 			__builtin_amdgcn_sched_barrier(0);
@@ -451,9 +423,9 @@ gauss_render_bwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 			const float inv_1ma = div_nr(1.0f, 1.f - alpha);
 			T *= inv_1ma;
 			const float w = alpha * T;
-			float D1 = R.r1.z * dp0 + R.r1.w * dp1 + R.r2.x * dp2 + R.r2.y * dn0 + R.r2.z * dn1 + R.r2.w * dn2 + R.r3.x * dr;
-			if (INVDEPTH) D1 += R.r3.y * di;
-			const float D2 = R.r1.z * dp0x3 + R.r1.w * dp1x2 + R.r2.x * dp2;
+			float D1 = R.f[1].z * dp0 + R.f[1].w * dp1 + R.f[2].x * dp2 + R.f[2].y * dn0 + R.f[2].z * dn1 + R.f[2].w * dn2 + R.f[3].x * dr;
+			if (INVDEPTH) D1 += R.f[3].y * di;
+			const float D2 = R.f[1].z * dp0x3 + R.f[1].w * dp1x2 + R.f[2].x * dp2;
 			A1 = last_alpha * D1p + (1.f - last_alpha) * A1;
 			A2 = last_alpha * D2p + (1.f - last_alpha) * A2;
 			D1p = D1; D2p = D2; last_alpha = alpha;
@@ -468,11 +440,11 @@ gauss_render_bwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 			v[GA_NORMAL + 2] = w * dn2;
 			v[GA_REFL] = w * dr;
 			v[GA_INVD] = INVDEPTH ? w * di : 0.f;
-			const float dL_dG = R.r1.y * dL_dalpha;
-			const float dL_dG_means2d = R.r1.y * dL_dalpha_means2d;
+			const float dL_dG = R.f[1].y * dL_dalpha;
+			const float dL_dG_means2d = R.f[1].y * dL_dalpha_means2d;
 			const float gdx = G * dx, gdy = G * dy;
-			const float dG_ddelx = (-gdx * R.r0.z - gdy * R.r0.w) * ddelx_dx;
-			const float dG_ddely = (-gdy * R.r1.x - gdx * R.r0.w) * ddely_dy;
+			const float dG_ddelx = (-gdx * R.f[0].z - gdy * R.f[0].w) * ddelx_dx;
+			const float dG_ddely = (-gdy * R.f[1].x - gdx * R.f[0].w) * ddely_dy;
 			v[GA_MEAN2D + 0] = dL_dG * dG_ddelx;
 			v[GA_MEAN2D + 1] = dL_dG * dG_ddely;
 			v[GA_MEAN2DP + 0] = dL_dG_means2d * dG_ddelx;
@@ -527,7 +499,7 @@ template <bool ACC>
 __global__ void __launch_bounds__(256)
 gauss_preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means, const int* __restrict__ radii, const float* __restrict__ shs,
                             const uint8_t* __restrict__ clamped, const float* __restrict__ opacities, const float* __restrict__ scales,
-                            const float* __restrict__ rotations, float scale_modifier, const float* __restrict__ cov3Ds, GaussCam cam,
+                            const float* __restrict__ rotations, float scale_modifier, const float* __restrict__ cov3Ds, RasterCam cam,
                             const float* __restrict__ acc, int has_invdepth, int antialiasing, float* __restrict__ dL_dmean2D,
                             float* __restrict__ dL_dmean2D_pixels, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,
                             float* __restrict__ dL_dcolor, float* __restrict__ dL_dnormals, float* __restrict__ dL_drefl,
@@ -737,15 +709,6 @@ gauss_preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means
 
 using namespace gsr;
 
-static GaussCam make_cam(const float* view, const float* proj, const float* campos, int W, int H, float tan_fovx, float tan_fovy) {
-	GaussCam c;
-	c.view = view; c.proj = proj; c.campos = campos; c.W = W; c.H = H;
-	c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy;
-	c.focal_y = H / (2.0f * tan_fovy);   // DGR rasterizer_impl.cu:228-229
-	c.focal_x = W / (2.0f * tan_fovx);
-	return c;
-}
-
 extern "C" int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,
                                  const float* means3D, const float* shs, const float* colors_precomp, const float* normals,
                                  const float* refl_strengths, const float* opacities, const float* scales, float scale_modifier,
@@ -777,7 +740,7 @@ extern "C" int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, in
 	if (const int rc = forward_workspace(alloc, alloc_user, GAUSS_LAYOUT, P, HW, ntiles, &geom, &img); rc < 0) return rc;
 
 	if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));   // the flag is only written and read then
-	const GaussCam cam = make_cam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
+	const RasterCam cam = make_cam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
 { StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	gauss_preprocess_kernel<<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, cov3D_precomp,
 	                                                             colors_precomp, normals, refl_strengths, cam, radii, geom, tiles_x, tiles_y,
 	                                                             prefiltered, antialiasing); }
@@ -790,14 +753,9 @@ extern "C" int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, in
 	const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
 	{
 		StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
-		if (out_invdepth)
-			gauss_render_fwd_wave_kernel<true><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
-			                                                              option_cull(), background, img.final_T, img.n_contrib, out_color, out_normal_map,
-			                                                              out_refl_strength_map, out_invdepth, bin.blend_mask, bin.mask_stride);
-		else
-			gauss_render_fwd_wave_kernel<false><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox,
-			                                                               option_cull(), background, img.final_T, img.n_contrib, out_color, out_normal_map,
-			                                                               out_refl_strength_map, nullptr, bin.blend_mask, bin.mask_stride);
+		auto kern = out_invdepth ? gauss_render_fwd_wave_kernel<true> : gauss_render_fwd_wave_kernel<false>;
+		kern<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(), background,
+		                                img.final_T, img.n_contrib, out_color, out_normal_map, out_refl_strength_map, out_invdepth, bin.blend_mask, bin.mask_stride);
 	}
 	GSR_LAUNCH_CHECK(debug, stream);
 	return R;
@@ -814,42 +772,26 @@ extern "C" int gsr_gauss_backward_accum(int P, int D, int M, int R, const float*
                                   float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing, int accumulate, int debug, void* stream_) {
 	(void)colors_precomp; (void)normals; (void)refl_strengths;
 	hipStream_t stream = (hipStream_t)stream_;
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) { set_error("gsr_gauss_backward: invalid size"); return GSR_E_INVALID; }
-	if (P == 0) return 0;
-	if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dnormal_map || !dL_drefl_strength_map ||
+	const bool missing = !geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dnormal_map || !dL_drefl_strength_map ||
 	    !dL_dmean2D_pixels || !dL_dopacity || (!shs && !dL_dcolor) || !dL_dnormals || !dL_drefl_strengths || !dL_dmean3D || (!scales && !dL_dcov3D) ||
-	    !dL_dscale || !dL_drot || (shs && !dL_dsh) || (dL_invdepths && !dL_dinvdepth) || !radii || !means3D || !opacities) {
-		set_error("gsr_gauss_backward: missing required pointer");
-		return GSR_E_INVALID;
-	}
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(shs, "shs (rows of a multiple of 16 bytes)");
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(dL_dsh, "dL_dsh");
-	GSR_REQUIRE_ALIGNED16(dL_drot, "dL_drot");
-	GSR_REQUIRE_ALIGNED16(dL_dconic, "dL_dconic");
-	const size_t HW = (size_t)width * height;
-	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
-	const int ntiles = tiles_x * tiles_y;
-	GeomState geom = carve_geom(geom_buffer, P, GAUSS_LAYOUT, nullptr);
-	ImageState img = carve_image(image_buffer, HW, ntiles, GAUSS_LAYOUT, nullptr);
-	BinningState bin = carve_binning(binning_buffer, R, ntiles, 0, nullptr);
-
-	GSR_HIP_CHECK(hipMemsetAsync(geom.acc, 0, (size_t)P * GAUSS_LAYOUT.acc_floats * sizeof(float), stream));
+	    !dL_dscale || !dL_drot || (shs && !dL_dsh) || (dL_invdepths && !dL_dinvdepth) || !radii || !means3D || !opacities;
+	BackwardWorkspace w;
+	if (const int rc = backward_prologue("gsr_gauss_backward", __func__, GAUSS_LAYOUT, P, M, R, width, height, missing, shs, dL_dsh, dL_drot, dL_dconic, "dL_dconic",
+	                                     geom_buffer, binning_buffer, image_buffer, stream, &w); rc <= 0) return rc;
+	const GeomState& geom = w.geom; const ImageState& img = w.img; const BinningState& bin = w.bin;
+	const int tiles_x = w.tiles_x, ntiles = w.ntiles;
 	if (R > 0) {
 		const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
 		{
 			StageTimer st_(GSR_STAGE_RENDER_BWD, stream);
-			if (dL_invdepths)
-				gauss_render_bwd_wave_kernel<true><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, background, geom.rec,
-				                                                              geom.bbox, option_cull(), img.final_T, img.n_contrib, dL_dpix, dL_dnormal_map,
-				                                                              dL_drefl_strength_map, dL_invdepths, geom.acc, bin.blend_mask, bin.mask_stride);
-			else
-				gauss_render_bwd_wave_kernel<false><<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, background, geom.rec,
-				                                                               geom.bbox, option_cull(), img.final_T, img.n_contrib, dL_dpix, dL_dnormal_map,
-				                                                               dL_drefl_strength_map, nullptr, geom.acc, bin.blend_mask, bin.mask_stride);
+			auto kern = dL_invdepths ? gauss_render_bwd_wave_kernel<true> : gauss_render_bwd_wave_kernel<false>;
+			kern<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, background, geom.rec, geom.bbox, option_cull(),
+			                                img.final_T, img.n_contrib, dL_dpix, dL_dnormal_map, dL_drefl_strength_map, dL_invdepths, geom.acc, bin.blend_mask,
+			                                bin.mask_stride);
 		}
 		GSR_LAUNCH_CHECK(debug, stream);
 	}
-	const GaussCam cam = make_cam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
+	const RasterCam cam = make_cam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
 	const float* cov3D_ptr = cov3D_precomp;      // NULL: the kernel recomputes it from scales / rotations
 { StageTimer st_(GSR_STAGE_PREPROCESS_BWD, stream);
 	auto kern = accumulate ? gauss_preprocess_bwd_kernel<true> : gauss_preprocess_bwd_kernel<false>;

@@ -34,13 +34,14 @@ void set_error(const char* fmt, ...);
 // (M = 16) and dL_drot rows as float4.  torch allocations are 256-byte aligned; VIEWS into a packed buffer (gradient sinks) need not be.
 // Checked at the C ABI so that a misaligned caller gets GSR_E_INVALID instead of a faulting or sector-splitting kernel.
 static inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-#define GSR_REQUIRE_ALIGNED16(ptr, what)                                                                      \
+#define GSR_REQUIRE_ALIGNED16_IN(func, ptr, what)                                                             \
 	do {                                                                                                      \
 		if ((ptr) && gsr::misaligned16(ptr)) {                                                                \
-			gsr::set_error("%s: %s must be 16-byte aligned (float4 accesses); got %p", __func__, what, (const void*)(ptr)); \
+			gsr::set_error("%s: %s must be 16-byte aligned (float4 accesses); got %p", func, what, (const void*)(ptr)); \
 			return GSR_E_INVALID;                                                                             \
 		}                                                                                                     \
 	} while (0)
+#define GSR_REQUIRE_ALIGNED16(ptr, what) GSR_REQUIRE_ALIGNED16_IN(__func__, ptr, what)
 
 // ------------------------------------------------------------------ per-stage timing (off by default)
 // RAII: records a start event at construction and a stop event at destruction on `stream` when profiling
@@ -148,6 +149,48 @@ static inline int check_sh_input(const char* entry, int D, int M, const float* s
 		return GSR_E_INVALID;
 	}
 	return 0;
+}
+
+// One camera for both variants' per-Gaussian kernels (reference rasterizer_impl.cu:228-229 for the focal lengths, the same in DGR and DSR).
+struct RasterCam {
+	const float* view;
+	const float* proj;
+	const float* campos;
+	int W, H;
+	float tan_fovx, tan_fovy, focal_x, focal_y;
+};
+static inline RasterCam make_cam(const float* view, const float* proj, const float* campos, int W, int H, float tan_fovx, float tan_fovy) {
+	RasterCam c;
+	c.view = view; c.proj = proj; c.campos = campos; c.W = W; c.H = H;
+	c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy;
+	c.focal_y = H / (2.0f * tan_fovy);
+	c.focal_x = W / (2.0f * tan_fovx);
+	return c;
+}
+
+// What both backward drivers do before their kernels: size check, P == 0 (returns 0: nothing to do), the variant's required-pointer test
+// (`missing_pointer`: the caller evaluates it, it only compares pointers), 16-byte alignment of what the per-Gaussian pass accesses as
+// float4 (`also_aligned`: one more such pointer of the variant, or NULL), the forward's buffers carved again, the accumulator zeroed.
+// `entry` / `func` name the operation / the driver in the messages.  Returns 1 to go on, < 0 on error.
+struct BackwardWorkspace { GeomState geom; ImageState img; BinningState bin; int tiles_x, ntiles; };
+static inline int backward_prologue(const char* entry, const char* func, const WorkspaceLayout& layout, int P, int M, int R, int width, int height,
+                                    bool missing_pointer, const float* shs, const float* dL_dsh, const float* dL_drot, const float* also_aligned,
+                                    const char* also_what, void* geom_buffer, void* binning_buffer, void* image_buffer, hipStream_t stream,
+                                    BackwardWorkspace* w) {
+	if (P < 0 || R < 0 || width <= 0 || height <= 0) { set_error("%s: invalid size", entry); return GSR_E_INVALID; }
+	if (P == 0) return 0;
+	if (missing_pointer) { set_error("%s: missing required pointer", entry); return GSR_E_INVALID; }
+	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16_IN(func, shs, "shs (rows of a multiple of 16 bytes)");
+	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16_IN(func, dL_dsh, "dL_dsh");
+	GSR_REQUIRE_ALIGNED16_IN(func, dL_drot, "dL_drot");
+	GSR_REQUIRE_ALIGNED16_IN(func, also_aligned, also_what);
+	w->tiles_x = (width + 15) / 16;
+	w->ntiles = w->tiles_x * ((height + 15) / 16);
+	w->geom = carve_geom(geom_buffer, P, layout, nullptr);
+	w->img = carve_image(image_buffer, (size_t)width * height, w->ntiles, layout, nullptr);
+	w->bin = carve_binning(binning_buffer, R, w->ntiles, 0, nullptr);
+	GSR_HIP_CHECK(hipMemsetAsync(w->geom.acc, 0, (size_t)P * layout.acc_floats * sizeof(float), stream));
+	return 1;
 }
 
 int option_cull();   // 1 (default): per-wave bounding-box culling in the tile kernels; 0: evaluate every list entry

@@ -8,6 +8,7 @@
 // {r, g | b, mask}   (Tu, Tv, Tw = rows of the 3x3 homography "transMat").
 #include <type_traits>
 #include "gsr_internal.hpp"
+#include "gsr_tile_walk.hpp"
 #include "gsr_sort.hpp"
 #include "gsr_math.hpp"
 #include "gsr_refl.hpp"
@@ -24,14 +25,6 @@ namespace gsr {
 #define S_NEAR 0.2f
 #define S_FAR 100.0f
 #define S_FILTER_INV_SQ 2.0f
-
-struct SurfelCam {
-	const float* view;
-	const float* proj;
-	const float* campos;
-	int W, H;
-	float tan_fovx, tan_fovy, focal_x, focal_y;
-};
 
 // quat_to_rotmat (DSR auxiliary.h:217-239); the reference's rsqrtf is restated as an exact 1/sqrt.
 __device__ __forceinline__ M3 quat_to_rotmat(const float* __restrict__ q, float& w, float& x, float& y, float& z) {
@@ -65,7 +58,7 @@ __device__ __forceinline__ P34 make_P(const float* __restrict__ pm, int W, int H
 // compute_transmat (DSR forward.cu:75-115): T = (splat2world^T * world2ndc) * ndc2pix, evaluated in that
 // association and left-to-right order (zero terms of the 4-vectors dropped: adding an exact zero is exact).
 __device__ __forceinline__ void compute_transmat(float px, float py, float pz, const float* __restrict__ scale, float mod,
-                                                 const float* __restrict__ rot, const SurfelCam& cam, M3& T, F3& normal) {
+                                                 const float* __restrict__ rot, const RasterCam& cam, M3& T, F3& normal) {
 #pragma clang fp contract(off)
 	float qw, qx, qy, qz;
 	const M3 R = quat_to_rotmat(rot, qw, qx, qy, qz);
@@ -150,7 +143,7 @@ __device__ __forceinline__ bool
 surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
                       const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
                       const float* __restrict__ transMat_precomp, const float* __restrict__ colors_precomp, const float* __restrict__ refl,
-                      const uint8_t* __restrict__ env_scope_mask, const SurfelCam& cam, int* __restrict__ radii, const GeomState& g, int gx, int gy,
+                      const uint8_t* __restrict__ env_scope_mask, const RasterCam& cam, int* __restrict__ radii, const GeomState& g, int gx, int gy,
                       int prefiltered, float* __restrict__ gaussian_weights, float4* o) {
 #pragma clang fp contract(off)
 	radii[idx] = 0;
@@ -249,7 +242,7 @@ __global__ void __launch_bounds__(256)
 surfel_preprocess_kernel(int P, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
                          const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
                          const float* __restrict__ transMat_precomp, const float* __restrict__ colors_precomp,
-                         const float* __restrict__ refl, const uint8_t* __restrict__ env_scope_mask, SurfelCam cam, int* __restrict__ radii,
+                         const float* __restrict__ refl, const uint8_t* __restrict__ env_scope_mask, RasterCam cam, int* __restrict__ radii,
                          GeomState g, int gx, int gy, int prefiltered, float* __restrict__ gaussian_weights, CubemapInterleave ci) {
 	const int idx = blockIdx.x * 256 + threadIdx.x;
 	for (uint32_t t = (uint32_t)idx; t < ci.ntex; t += gridDim.x * 256u) {
@@ -283,21 +276,20 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f mk2(float a, float b) { v2f r; r.x = a; r.y = b; return r; }
 
 // The five float4 of a render record by meaning (layout: see surfel_preprocess_kernel).
-struct SurfelRec {
-	float4 r0, r1, r2, r3, r4;
-	__device__ __forceinline__ v2f xy() const { return mk2(r0.x, r0.y); }
-	__device__ __forceinline__ v2f TuvX() const { return mk2(r0.z, r0.w); }
-	__device__ __forceinline__ v2f TuvY() const { return mk2(r1.x, r1.y); }
-	__device__ __forceinline__ v2f TuvZ() const { return mk2(r1.z, r1.w); }
-	__device__ __forceinline__ v2f Twxy() const { return mk2(r2.x, r2.y); }
-	__device__ __forceinline__ float Twz() const { return r2.z; }
-	__device__ __forceinline__ float opac() const { return r2.w; }
-	__device__ __forceinline__ v2f nxy() const { return mk2(r3.x, r3.y); }
-	__device__ __forceinline__ float nz() const { return r3.z; }
-	__device__ __forceinline__ float refl() const { return r3.w; }
-	__device__ __forceinline__ v2f rg() const { return mk2(r4.x, r4.y); }
-	__device__ __forceinline__ float b() const { return r4.z; }
-	__device__ __forceinline__ float mask() const { return r4.w; }
+struct SurfelRec : TileRec<S_REC_F4> {
+	__device__ __forceinline__ v2f xy() const { return mk2(f[0].x, f[0].y); }
+	__device__ __forceinline__ v2f TuvX() const { return mk2(f[0].z, f[0].w); }
+	__device__ __forceinline__ v2f TuvY() const { return mk2(f[1].x, f[1].y); }
+	__device__ __forceinline__ v2f TuvZ() const { return mk2(f[1].z, f[1].w); }
+	__device__ __forceinline__ v2f Twxy() const { return mk2(f[2].x, f[2].y); }
+	__device__ __forceinline__ float Twz() const { return f[2].z; }
+	__device__ __forceinline__ float opac() const { return f[2].w; }
+	__device__ __forceinline__ v2f nxy() const { return mk2(f[3].x, f[3].y); }
+	__device__ __forceinline__ float nz() const { return f[3].z; }
+	__device__ __forceinline__ float refl() const { return f[3].w; }
+	__device__ __forceinline__ v2f rg() const { return mk2(f[4].x, f[4].y); }
+	__device__ __forceinline__ float b() const { return f[4].z; }
+	__device__ __forceinline__ float mask() const { return f[4].w; }
 };
 
 // renderCUDA forward (DSR forward.cu:258-489), wave-per-quadrant form.
@@ -316,8 +308,6 @@ struct SurfelRec {
 // materialisation for ballots), the rare `unstable` case leaves the straight-line path through a wave-uniform branch,
 // the 64-lane max for gaussian_weights is done for four pairs at a time (row_max4: 2 DPP per pair instead of 6 + 6 nops),
 // the env-scope plane is an accumulated weight, and the median bookkeeping stops once no pixel has T > 0.5.
-#define S_WBATCH 64
-#define CULL_PAD 0.05f    // the wave's pixel block is padded by this much in the footprint vote (the cull record itself is already dilated by half a pixel)
 #ifndef GSR_BWD_WPE
 #define GSR_BWD_WPE 4
 #endif
@@ -460,11 +450,10 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 	const SurfelReflFwd& rf = refl_args(args);
 	const uint32_t slot = xcd_slot(blockIdx.x);   // dispatch slot -> (tile, quadrant), longest lists first
 	if (slot >= (uint32_t)ntiles * 4u) return;
-	const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_order[slot >> 2]), quad = slot & 3u;   // (readfirstlane: the compiler cannot see that the loaded tile id is wave-uniform)
-	const int tile_x = tile % tiles_x, tile_y = tile / tiles_x;
-	const int lane = threadIdx.x;
-	const int bx0 = tile_x * 16 + (quad & 1) * 8, by0 = tile_y * 16 + (quad >> 1) * 8;
-	if (bx0 >= W || by0 >= H) return;
+	const TileBlock blk = tile_block(tile_order, slot, tiles_x);
+	if (blk.bx0 >= W || blk.by0 >= H) return;
+	const uint32_t tile = blk.tile, quad = blk.quad;
+	const int lane = threadIdx.x, bx0 = blk.bx0, by0 = blk.by0;
 	// a 16-lane row (the unit of the DPP reductions) is a 4x4 pixel sub-block: the backward walks one list per sub-block
 	const int px = bx0 + sub_px(lane), py = by0 + sub_py(lane);
 	const bool inside = px < W && py < H;
@@ -473,9 +462,9 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 	const int count = (int)(range.y - range.x);
 	const float qx0 = (float)bx0, qy0 = (float)by0, qx1 = qx0 + 7.0f, qy1 = qy0 + 7.0f;
 
-	__shared__ uint32_t s_hid[S_WBATCH];
-	__shared__ uint32_t s_hc[TRAIN ? S_WBATCH : 1];
-	__shared__ float4 s_wmax[TRAIN ? S_WBATCH : 1];   // [hit][16-lane row = 4x4 sub-block]: row maxima of the blend weight
+	__shared__ uint32_t s_hid[WBATCH];
+	__shared__ uint32_t s_hc[TRAIN ? WBATCH : 1];
+	__shared__ float4 s_wmax[TRAIN ? WBATCH : 1];   // [hit][16-lane row = 4x4 sub-block]: row maxima of the blend weight
 
 	lmask done = ~LMASK(px < W) | ~LMASK(py < H);  // lanes outside the image never blend
 	SurfelFwdPix st;
@@ -485,19 +474,20 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 	st.Crg = st.Nxy = st.NzR = st.DM = mk2(0.f, 0.f);
 	st.last_contributor = 0;
 	bool med_live = true;
-	const size_t batch0 = (size_t)(range.x / S_WBATCH) + tile;     // where this tile's batches sit in blend_mask (see BinningState)
+	const size_t batch0 = (size_t)(range.x / WBATCH) + tile;     // where this tile's batches sit in blend_mask (see BinningState)
 	// (hit ordinal + value slot of this lane's quad) * 16 bytes + row * 4: where the lane parks a row maximum (row_max4)
 	const uint32_t wmax_off = (uint32_t)row_reduce_slot(lane) * 16u + (uint32_t)(lane >> 4) * 4u;
 
-	for (int base = 0; base < count; base += S_WBATCH) {
+	for (int base = 0; base < count; base += WBATCH) {
 		if (done == ~0ull) break;
-		const int nb = min(S_WBATCH, count - base);
+		const int nb = min(WBATCH, count - base);
 		// ---- 1. vote
 		bool hit = lane < nb;
 		uint32_t id = 0;
 		if (hit) {
 			id = point_list[range.x + (uint32_t)(base + lane)];
 			if (cull) {
+				// (the cull record itself is already dilated by half a pixel)
 				hit = cull_hit(bbox[2 * id], bbox[2 * id + 1], qx0 - CULL_PAD, qx1 + CULL_PAD, qy0 - CULL_PAD, qy1 + CULL_PAD);
 			}
 		}
@@ -505,6 +495,8 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 		const int nh = __popcll(mm);
 		if (nh == 0) continue;
 		if constexpr (TRAIN) s_wmax[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+		// (compact_hits of gsr_tile_walk.hpp spelled out: through the helper the compiler lays s_hid and s_hc out in the other order and
+		// splits the two reads of the TRAIN instances)
 		const int kown = __popcll(mm & ((1ull << lane) - 1ull));   // this lane's entry is hit number kown (if it is a hit)
 		if (hit) {
 			s_hid[kown] = id;
@@ -517,10 +509,7 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 		// right after the arithmetic of the current one has started; with a single rotating buffer the compiler copies the 20
 		// SGPRs twice per pair.  Four pairs per trip: their blend weights share one packed row-max reduction.
 		using Rec = SurfelRec;
-		auto fetch = [&](int k) -> Rec {
-			const float4* q = rec + (size_t)__builtin_amdgcn_readlane(hid, k) * S_REC_F4;
-			return Rec{q[0], q[1], q[2], q[3], q[4]};
-		};
+		auto fetch = [&](int k) { return Rec{fetch_rec<S_REC_F4>(rec, hid, k)}; };
 		Rec A = fetch(0), B = A;
 		unsigned long long force = 0ull;     // hits whose pair had a grazing lane (rare): the backward must evaluate them itself
 		for (int k = 0; k < nh; k += 4) {
@@ -581,7 +570,7 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 		const lmask b0 = LMASK(r.x > 0.f) | forced, b1 = LMASK(r.y > 0.f) | forced, b2 = LMASK(r.z > 0.f) | forced, b3 = LMASK(r.w > 0.f) | forced;
 		if (lane < 4) {
 			const lmask mine = lane == 0 ? b0 : (lane == 1 ? b1 : (lane == 2 ? b2 : b3));
-			blend_mask[(batch0 + (size_t)(base / S_WBATCH)) * 16u + quad * 4u + (uint32_t)lane] = mine;
+			blend_mask[(batch0 + (size_t)(base / WBATCH)) * 16u + quad * 4u + (uint32_t)lane] = mine;
 		}
 		__syncthreads();
 	}
@@ -825,11 +814,10 @@ surfel_render_bwd_rows_body(const uint2* __restrict__ ranges, const uint32_t* __
                             const unsigned long long* __restrict__ blend_mask) {
 	const uint32_t slot = xcd_slot(blockIdx.x);   // dispatch slot -> (tile, quadrant), longest lists first
 	if (slot >= (uint32_t)ntiles * 4u) return;
-	const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_order[slot >> 2]), quad = slot & 3u;   // (readfirstlane: the compiler cannot see that the loaded tile id is wave-uniform)
-	const int tile_x = tile % tiles_x, tile_y = tile / tiles_x;
-	const int lane = threadIdx.x, row = lane >> 4;
-	const int bx0 = tile_x * 16 + (quad & 1) * 8, by0 = tile_y * 16 + (quad >> 1) * 8;
-	if (bx0 >= W || by0 >= H) return;
+	const TileBlock blk = tile_block(tile_order, slot, tiles_x);
+	if (blk.bx0 >= W || blk.by0 >= H) return;
+	const uint32_t tile = blk.tile, quad = blk.quad;
+	const int lane = threadIdx.x, row = lane >> 4, bx0 = blk.bx0, by0 = blk.by0;
 	const int px = bx0 + sub_px(lane), py = by0 + sub_py(lane);
 	const bool inside = px < W && py < H;
 	const lmask inside_m = LMASK(px < W) & LMASK(py < H);
@@ -840,8 +828,8 @@ surfel_render_bwd_rows_body(const uint2* __restrict__ ranges, const uint32_t* __
 	const size_t pix = (size_t)W * py + px;
 
 	__shared__ float s_slab[(S_CAP + 2) * S_ACC_F];     // [slot][20 floats]; slot S_CAP takes the stores of rows that have run out, slot S_CAP + 1 stays zero
-	__shared__ float4 s_rec[S_WBATCH * S_REC_F4];       // records of the batch's blended entries (indexed by position in the batch)
-	__shared__ uint32_t s_cw[S_WBATCH];                 // per entry of the chunk (compacted): the slab slot of each of the four rows (6 bits each) and, from bit 24, its batch position
+	__shared__ float4 s_rec[WBATCH * S_REC_F4];       // records of the batch's blended entries (indexed by position in the batch)
+	__shared__ uint32_t s_cw[WBATCH];                 // per entry of the chunk (compacted): the slab slot of each of the four rows (6 bits each) and, from bit 24, its batch position
 #if GSR_BWD_LIST
 	__shared__ uint8_t s_list[64];                      // by slab slot (a row's slots are consecutive, in the order it visits them: last entry first): the batch position
 #endif
@@ -866,8 +854,8 @@ surfel_render_bwd_rows_body(const uint2* __restrict__ ranges, const uint32_t* __
 	float* const fl_acc = acc + fl_d;
 	const char* const slab_b = reinterpret_cast<const char*>(s_slab);
 
-	const size_t batch0 = (size_t)(range.x / S_WBATCH) + tile;
-	for (int b = (min(wave_last, count) - 1) / S_WBATCH; b >= 0; b--) {
+	const size_t batch0 = (size_t)(range.x / WBATCH) + tile;
+	for (int b = (min(wave_last, count) - 1) / WBATCH; b >= 0; b--) {
 		const unsigned long long* mp = blend_mask + ((batch0 + (size_t)b) * 16u + quad * 4u);
 		const lmask m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
 		const lmask any = (m0 | m1) | (m2 | m3);
@@ -875,7 +863,7 @@ surfel_render_bwd_rows_body(const uint2* __restrict__ ranges, const uint32_t* __
 		// ---- 1. stage: lane l owns batch position l; if its entry blended anywhere in the block it fetches the record for the wave
 		uint32_t id = 0u;
 		if ((any >> lane) & 1ull) {
-			id = point_list[range.x + (uint32_t)(b * S_WBATCH + lane)];
+			id = point_list[range.x + (uint32_t)(b * WBATCH + lane)];
 			const float4* q = rec + (size_t)id * S_REC_F4;
 			const float4 r0 = q[0], r1 = q[1], r2 = q[2], r3 = q[3];
 			float4 r4 = q[4];
@@ -952,7 +940,7 @@ surfel_render_bwd_rows_body(const uint2* __restrict__ ranges, const uint32_t* __
 				float v[S_ACC_F];
 				v[S_ACC_F - 1] = 0.f;
 				// (no early exit: the masks are exact, an entry without a blending lane is a rare forced one, and then v is all zeros)
-				surfel_bwd_pair(st, R, pixv, b * S_WBATCH + (int)j, inside_m & valid, v);
+				surfel_bwd_pair(st, R, pixv, b * WBATCH + (int)j, inside_m & valid, v);
 				// 20 values -> 5 registers of per-row totals; every lane of quad q of row r parks value slot(q) of each register
 				float z[5];
 				row_reduce20(v, z);
@@ -1011,7 +999,7 @@ template <bool ACC>
 __global__ void __launch_bounds__(256)
 surfel_preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means, const int* __restrict__ radii, const float* __restrict__ shs,
                              const uint8_t* __restrict__ clamped, const float* __restrict__ scales, const float* __restrict__ rotations,
-                             const float4* __restrict__ rec, SurfelCam cam, const float* __restrict__ acc, float* __restrict__ dL_dmean2D,
+                             const float4* __restrict__ rec, RasterCam cam, const float* __restrict__ acc, float* __restrict__ dL_dmean2D,
                              float* __restrict__ dL_dnormal, float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor,
                              float* __restrict__ dL_drefl, float* __restrict__ dL_dmean3D, float* __restrict__ dL_dtransMat,
                              float* __restrict__ dL_dsh, float* __restrict__ dL_dscale, float* __restrict__ dL_drot) {
@@ -1203,15 +1191,6 @@ surfel_preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ mean
 
 using namespace gsr;
 
-static SurfelCam make_scam(const float* view, const float* proj, const float* campos, int W, int H, float tan_fovx, float tan_fovy) {
-	SurfelCam c;
-	c.view = view; c.proj = proj; c.campos = campos; c.W = W; c.H = H;
-	c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy;
-	c.focal_y = H / (2.0f * tan_fovy);   // DSR rasterizer_impl.cu:228-229
-	c.focal_x = W / (2.0f * tan_fovx);
-	return c;
-}
-
 // The checks both surfel forwards make, before their first allocation or device call.  `entry` names the caller in the message.
 static int check_refl_descriptor(const char* entry, const gsr_refl_forward* refl) {
 	if (!refl) return 0;
@@ -1281,7 +1260,7 @@ static int surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, in
 		if (const int rc = forward_workspace(alloc, alloc_user, TRAIN ? SURFEL_LAYOUT : SURFEL_LAYOUT.inference(), P, HW, ntiles, &geom, &img); rc < 0) return rc;
 
 		if (prefiltered) GSR_HIP_CHECK(hipMemsetAsync(geom.flags, 0, 4 * sizeof(int), stream));   // the flag is only written and read then
-		const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
+		const RasterCam cam = make_cam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
 		CubemapInterleave ci{nullptr, nullptr, 0u, 1u};
 		SurfelReflFwd rf{};
 		if (refl) {
@@ -1378,25 +1357,14 @@ extern "C" int gsr_surfel_backward_ex(int P, int D, int M, int R, const float* b
                                    float* dL_drot, int accumulate, const float* dL_dnormal_extra, int debug, void* stream_) {
 	(void)colors_precomp; (void)refl_strengths; (void)scale_modifier; (void)transMat_precomp;
 	hipStream_t stream = (hipStream_t)stream_;
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) { set_error("gsr_surfel_backward: invalid size"); return GSR_E_INVALID; }
-	if (P == 0) return 0;
-	if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dothers || !dL_drefl_strength_map || !dL_dmean2D ||
+	const bool missing = !geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dothers || !dL_drefl_strength_map || !dL_dmean2D ||
 	    !dL_dopacity || !dL_drefl_strengths || !dL_dmean3D || !dL_dscale || !dL_drot || (!shs && !dL_dcolor) || (!scales && !dL_dtransMat) ||
-	    (shs && !dL_dsh) || !radii || !means3D) {
-		set_error("gsr_surfel_backward: missing required pointer");
-		return GSR_E_INVALID;
-	}
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(shs, "shs (rows of a multiple of 16 bytes)");
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16(dL_dsh, "dL_dsh");
-	GSR_REQUIRE_ALIGNED16(dL_drot, "dL_drot");
-	const size_t HW = (size_t)width * height;
-	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
-	const int ntiles = tiles_x * tiles_y;
-	GeomState geom = carve_geom(geom_buffer, P, SURFEL_LAYOUT, nullptr);
-	ImageState img = carve_image(image_buffer, HW, ntiles, SURFEL_LAYOUT, nullptr);
-	BinningState bin = carve_binning(binning_buffer, R, ntiles, 0, nullptr);
-
-	GSR_HIP_CHECK(hipMemsetAsync(geom.acc, 0, (size_t)P * SURFEL_LAYOUT.acc_floats * sizeof(float), stream));
+	    (shs && !dL_dsh) || !radii || !means3D;
+	BackwardWorkspace w;
+	if (const int rc = backward_prologue("gsr_surfel_backward", __func__, SURFEL_LAYOUT, P, M, R, width, height, missing, shs, dL_dsh, dL_drot, nullptr, nullptr,
+	                                     geom_buffer, binning_buffer, image_buffer, stream, &w); rc <= 0) return rc;
+	const GeomState& geom = w.geom; const ImageState& img = w.img; const BinningState& bin = w.bin;
+	const int tiles_x = w.tiles_x, ntiles = w.ntiles;
 	if (R > 0) {
 		// a key sort of the reflection backward on the library's side stream must have reached its last pass before this kernel takes
 		// every wave slot of the chip (side_gate_wait, gsr_cubemap.hip); nothing pending: no wait
@@ -1408,7 +1376,7 @@ extern "C" int gsr_surfel_backward_ex(int P, int D, int M, int R, const float* b
 		                                                         geom.acc, bin.blend_mask); }
 		GSR_LAUNCH_CHECK(debug, stream);
 	}
-	const SurfelCam cam = make_scam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
+	const RasterCam cam = make_cam(viewmatrix, projmatrix, cam_pos, width, height, tan_fovx, tan_fovy);
 	// scales == NULL selects the transMat_precomp path in the per-surfel backward (DSR backward.cu:639)
 { StageTimer st_(GSR_STAGE_PREPROCESS_BWD, stream);
 	auto kern = accumulate ? surfel_preprocess_bwd_kernel<true> : surfel_preprocess_bwd_kernel<false>;

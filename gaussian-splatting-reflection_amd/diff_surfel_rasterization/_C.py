@@ -13,17 +13,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import _gsr  # noqa: E402
-from _gsr import check, f32c, lib, ptr, require_cuda, stream_ptr  # noqa: E402
+from _gsr import check, f32c, lib, mark_visible, ptr, require_cuda, stream_ptr  # noqa: E402,F401 (mark_visible: re-exported)
+from _gsr import sh_coeffs as _sh_coeffs  # noqa: E402
 
 NUM_CHANNELS = 3
 SINKABLE = frozenset(("means3D", "shs", "opacities", "scales", "rotations", "refl_strengths"))   # gradients a grad_sink may take
-
-
-def _sh_coeffs(sh):
-    """M, the SH coefficients per Gaussian: an omitted input is a 1-D empty placeholder, an empty scene's shs are (0, M, 3).  (The compiled
-    binding, gsr_torch_binding.cpp, takes M = 0 for any empty sh; the two differ only at P = 0, where the library reads nothing and
-    autograd drops the empty gradient, and gradient sinks always take this binding.)"""
-    return sh.size(1) if sh.dim() > 1 else 0
 
 
 def _forward_inputs(background, means3D, colors, refl_strengths, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix, sh,
@@ -159,16 +153,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, refl_streng
     output (the blended view-space normal) that the tile kernel adds to dL_dout_others[2:5] while loading it
     (gsr_surfel_backward_ex) — what the output tap `normal_view` of GaussianRasterizer receives."""
     M = _sh_coeffs(sh)
-    if grad_sink:
-        unknown = set(grad_sink) - SINKABLE
-        if unknown:
-            raise ValueError(f"grad sink: unknown gradient name(s) {sorted(unknown)}; expected a subset of {sorted(SINKABLE)}")
-    if accumulate and (not grad_sink or not set(grad_sink) >= (SINKABLE - ({"shs"} if M == 0 else set()))):
-        # the kernel has ONE accumulate switch for all six parameter gradients: fresh (uninitialised) tensors cannot be added to
-        raise ValueError("accumulate=True needs a sink for every parameter gradient: " + ", ".join(sorted(SINKABLE)))
-    unused = frozenset(unused)
-    if unused - {"colors", "transMat"} or ("colors" in unused and _sh_coeffs(sh) == 0) or ("transMat" in unused and scales.dim() < 2):
-        raise ValueError("unused: 'colors' needs shs as the colour input, 'transMat' needs scales / rotations; got %r" % (sorted(unused),))
+    unused = _gsr.check_backward_keywords(grad_sink, accumulate, unused, SINKABLE, M, {"colors": M != 0, "transMat": scales.dim() >= 2},
+                                          "unused: 'colors' needs shs as the colour input, 'transMat' needs scales / rotations; got %r")
     if extra_normal_grad is not None:
         hw = tuple(dL_dout_color.shape[1:])
         if tuple(extra_normal_grad.shape) != (3,) + hw or extra_normal_grad.device != means3D.device:
@@ -190,21 +176,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, refl_streng
     dev = means3D.device
     o = dict(dtype=torch.float32, device=dev)
     # the library writes every element, so no zero-fill is needed (the reference uses torch::zeros)
-    mk0 = torch.empty if P != 0 else torch.zeros
-
-
-    def mk(shape, sink_name=None, **kw):
-        # gradient sink: the kernel writes this output straight into a caller-owned tensor
-        t = grad_sink.get(sink_name) if (grad_sink and sink_name is not None) else None
-        if t is not None:
-            if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"grad sink '{sink_name}': expected contiguous float32 {tuple(shape)} on {dev}, got {tuple(t.shape)} {t.dtype}")
-            if t.data_ptr() % 16:
-                # the kernel stores dL_dsh / dL_drot rows as float4 (include/gsr_hip.h, "alignment"); the C ABI refuses too
-                raise ValueError(f"grad sink '{sink_name}': storage must be 16-byte aligned (got {t.data_ptr():#x}); pad the slices of a packed buffer "
-                                 "to multiples of 4 floats as gsr_dist.FlatGrads does")
-            return t
-        return mk0(shape, **kw)
+    mk = _gsr.grad_allocator(grad_sink, dev, torch.empty if P != 0 else torch.zeros)
     # dL_dnormal3D is internal to the reference's backward (never returned): not materialised at all
     dL_dmeans3D, dL_dmeans2D, dL_dnormal = mk((P, 3), "means3D", **o), mk((P, 3), **o), None
     dL_dcolors = torch.empty(0, **o) if "colors" in unused else mk((P, NUM_CHANNELS), **o)
@@ -229,15 +201,3 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, refl_streng
                                           ptr(dL_drefl), ptr(dL_dmeans3D), ptr(dL_dtransMat), ptr(dL_dsh), ptr(dL_dscales),
                                           ptr(dL_drotations), int(bool(accumulate)), ptr(gnx), int(bool(debug)), stream_ptr(dev)), "gsr_surfel_backward")
     return dL_dmeans2D, dL_dcolors, dL_drefl, dL_dopacity, dL_dmeans3D, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations
-
-
-def mark_visible(means3D, viewmatrix, projmatrix):
-    if _gsr.PYBIND is not None:
-        return _gsr.PYBIND.mark_visible(means3D, viewmatrix, projmatrix)
-    P = means3D.size(0)
-    present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
-    if P != 0:
-        m3, vm, pm = f32c(means3D, "means3D"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix")
-        with torch.cuda.device(means3D.device):
-            check(lib.gsr_mark_visible(P, ptr(m3), ptr(vm), ptr(pm), ptr(present), stream_ptr(means3D.device)), "gsr_mark_visible")
-    return present
