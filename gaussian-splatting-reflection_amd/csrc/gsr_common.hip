@@ -8,7 +8,6 @@
 #include <initializer_list>
 #include <vector>
 #include <mutex>
-#include <rocprim/device/device_radix_sort.hpp>
 #include "gsr_sort.hpp"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -86,8 +85,9 @@ uint32_t higher_msb(uint32_t n) {
 // (11-bit digits — three passes over the 31 depth bits instead of four; they fit LDS only with the `match` ranking —
 // were measured too: 0.43 ms against 0.27 ms for the whole two-level sort.)
 using SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 65536>;
-// Both sorts go through gsr_sort.hpp (rocPRIM's Onesweep device code, one clear per sort instead of three dispatches per
-// pass).  Workgroup shapes: the depth sort of P keys is launch-latency-bound (a pass over 1 M pairs moves 16 MB) and
+// Both sorts go through RadixSort of gsr_sort.hpp (rocPRIM's Onesweep device code, one clear per sort instead of three dispatches
+// per pass; it chooses the driver, SortConfig is the public one's).
+// Workgroup shapes: the depth sort of P keys is launch-latency-bound (a pass over 1 M pairs moves 16 MB) and
 // rocPRIM's tuned shape for 4-byte pairs (1024 threads x 16 items: 61 workgroups at P = 1 M) leaves most CUs idle;
 // 1024 x 4 measured best (whole two-level sort at P = 1 M, ms: tuned 0.274, 256x8 0.270, 512x4 0.251, 1024x2 0.250,
 // 1024x3 0.233, 1024x4 0.220, 1024x6 0.251, 1024x8 0.235; it also wins at 0.3 M, 2 M and 5 M).  The second-level sort of
@@ -101,7 +101,7 @@ using SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::
 #define DEPTH_SORT_SHAPE DEPTH_SORT_BS, DEPTH_SORT_IPT, 8
 #define DEPTH_KEY_BITS 31u             // depths are positive floats (culled Gaussians carry FLT_MAX): their bit patterns order like the values
 #define DEPTH_KEY_PLACES 4u            // 8-bit digits
-// (Round 3, measured and dropped: keys = float bits minus the bits of the near plane have 27 significant bits for every depth below 13 107,
+// (Measured and dropped: keys = float bits minus the bits of the near plane have 27 significant bits for every depth below 13 107,
 // i.e. three 9-bit places instead of four 8-bit ones, with a host-side fallback to the 31-bit sort for scenes that reach beyond.  A 9-bit
 // pass over 1 M pairs takes 29 us against 17.7 us for an 8-bit one — the ranking works bit by bit and its LDS counters double — so three of
 // them cost more than four: depth passes 86 vs 71 us at C3, the same at C5.)
@@ -126,15 +126,23 @@ using SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::
 #define TILE_SORT_SHAPE_SMALL7 TILE_SORT_BS, (TILE_SORT_IPT / 2), 7
 static bool tile_sort_small(size_t R) { return R >= (size_t)TILE_SORT_SMALL_FROM; }
 static bool tile_sort_7bit(size_t R, int end_bit) { return tile_sort_small(R) && end_bit > 7 && end_bit <= 14; }
-static const size_t SORT_MAX_ITEMS = ((size_t)1 << 30) - 1;   // gsr_sort.hpp handles one rocPRIM batch; beyond it rocPRIM itself
+// The tile sort of R instances with end_bit tile-id bits: f(the RadixSort of its shape).  Temp size, bytes to clear and the sort itself all
+// come through here, so they cannot disagree about the shape.
+template <class F>
+static auto with_tile_sort(size_t R, int end_bit, F&& f) {
+	if (tile_sort_7bit(R, end_bit)) return f(RadixSort<TILE_SORT_SHAPE_SMALL7, SortConfig>{});
+	if (tile_sort_small(R)) return f(RadixSort<TILE_SORT_SHAPE_SMALL, SortConfig>{});
+	return f(RadixSort<TILE_SORT_SHAPE, SortConfig>{});
+}
+using DepthSort = RadixSort<DEPTH_SORT_SHAPE, SortConfig>;
 
-// What the depth sort carries as its VALUE (round 4): the Gaussian's index (low word) and its tile rectangle packed to 4 x 8 bits
+// What the depth sort carries as its VALUE: the Gaussian's index (low word) and its tile rectangle packed to 4 x 8 bits
 // (high word: x0 | y0 << 8 | x1 << 16 | y1 << 24).  Key emission then reads index and rectangle of the Gaussians in depth order as ONE
-// coalesced 8-byte stream; before, it read the 4-byte index coalesced and gathered the 8-byte rectangle through it — a whole line per
+// coalesced 8-byte stream; reading the 4-byte index coalesced and gathering the 8-byte rectangle through it costs a whole line per
 // Gaussian for 8 bytes: 135 MB of traffic against 44 MB of algorithmic bytes at C3, 763 against 180 MB at C5, where the kernel was bound by
 // exactly that.  The first pass reads the rectangles in INDEX order (coalesced, through this iterator); the three further passes move 8
 // instead of 4 bytes of value per Gaussian.  Grids beyond 255 tiles per axis (images beyond 4080 pixels) do not fit 8 bits per
-// coordinate: `packed` = 0 leaves the high word empty and emit_tiles_kernel<true> gathers the rectangle as before.
+// coordinate: `packed` = 0 leaves the high word empty and emit_tiles_kernel<true> gathers the rectangle (GeomState::rect) itself.
 struct OrderRect {
 	const uint32_t* rect;
 	int packed;
@@ -150,50 +158,22 @@ struct OrderRect {
 using OrderIn = rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, OrderRect, unsigned long long>;
 static OrderIn order_in(const uint32_t* rect, int packed) { return OrderIn(rocprim::counting_iterator<uint32_t>(0), OrderRect{rect, packed}); }
 
-// tiles_touched read through the depth order: element i of the sequence the second scan runs over
-struct TouchedInOrder {
-	const uint32_t* tiles_touched;
-	__host__ __device__ uint32_t operator()(uint32_t idx) const { return tiles_touched[idx]; }
-};
-// bytes of the P-sized temp region: the two scans share the first part, the depth pre-sort has the second one to itself
-// (its look-back state is cleared by the preprocess kernel, before the first scan runs)
+// bytes of the first part of the P-sized temp region (the depth pre-sort has the second part to itself): temp of a rocPRIM inclusive_scan
+// over P values.  The forward runs no such scan; the only user is gsr_debug_fetch("point_offsets").  (The size once was the larger of
+// this scan's and of one reading tiles_touched through the depth order.  rocPRIM sizes a scan's temp by its config, chosen by the value
+// type, and P, not by the input iterator: both ask for 524, 524, 2476 and 10284 bytes at P = 1, 1000, 10^6 and 5 * 10^6 on MI355X.)
 static size_t scan_part_bytes(size_t P) {
-	size_t a = 0, b = 0;
+	size_t a = 0;
 	(void)rocprim::inclusive_scan(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, P, rocprim::plus<uint32_t>(), 0, false);
-	auto it = rocprim::make_transform_iterator((const uint32_t*)nullptr, TouchedInOrder{nullptr});
-	(void)rocprim::inclusive_scan(nullptr, b, it, (uint32_t*)nullptr, P, rocprim::plus<uint32_t>(), 0, false);
-	return (std::max(a, b) + 255) & ~(size_t)255;
-}
-// temp bytes: the larger of the two drivers' needs, so that the runtime switch (option_sort_driver) never changes a workspace size
-static size_t depth_sort_bytes(size_t P) {
-	size_t c = 0, d = 0;
-	if (P <= SORT_MAX_ITEMS)
-		(void)onesweep_sort_pairs<DEPTH_SORT_SHAPE>(nullptr, c, (const uint32_t*)nullptr, (uint32_t*)nullptr, order_in(nullptr, 0),
-		                                            (unsigned long long*)nullptr, P, 0u, DEPTH_KEY_BITS, 0);
-	(void)rocprim::radix_sort_pairs<SortConfig>(nullptr, d, (const uint32_t*)nullptr, (uint32_t*)nullptr, order_in(nullptr, 0),
-	                                            (unsigned long long*)nullptr, P, 0, 31, 0, false);
-	return std::max(c, d);
+	return (a + 255) & ~(size_t)255;
 }
 size_t sort_temp_bytes(size_t R, int end_bit) {
-	size_t bytes = 0, pub = 0;
-	if (R <= SORT_MAX_ITEMS) {
-		if (tile_sort_7bit(R, end_bit))
-			(void)onesweep_sort_pairs<TILE_SORT_SHAPE_SMALL7>(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-			                                                  R, 0u, (unsigned)end_bit, 0);
-		else if (tile_sort_small(R))
-			(void)onesweep_sort_pairs<TILE_SORT_SHAPE_SMALL>(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-			                                                 R, 0u, (unsigned)end_bit, 0);
-		else
-			(void)onesweep_sort_pairs<TILE_SORT_SHAPE>(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, R,
-			                                           0u, (unsigned)end_bit, 0);
-	}
-	(void)rocprim::radix_sort_pairs<SortConfig>(nullptr, pub, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, R, 0,
-	                                            end_bit, 0, false);
-	return std::max(bytes, pub);
+	return with_tile_sort(R, end_bit, [&](auto sort) { return sort.temp_bytes((uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, R, (unsigned)end_bit); });
 }
 
 GeomState carve_geom(void* buf, size_t P, const WorkspaceLayout& layout, size_t* total) {
-	const size_t scan_bytes = scan_part_bytes(P), sort_bytes = depth_sort_bytes(P);
+	const size_t scan_bytes = scan_part_bytes(P);
+	const size_t sort_bytes = DepthSort::temp_bytes((const uint32_t*)nullptr, order_in(nullptr, 0), (unsigned long long*)nullptr, P, DEPTH_KEY_BITS);
 	Carver c(buf);
 	GeomState g;
 	g.depths = c.take<float>(P);
@@ -214,7 +194,7 @@ GeomState carve_geom(void* buf, size_t P, const WorkspaceLayout& layout, size_t*
 	g.scan_temp_bytes = scan_bytes + sort_bytes;
 	g.depth_sort_temp = g.scan_temp ? static_cast<char*>(g.scan_temp) + scan_bytes : nullptr;
 	g.depth_sort_bytes = sort_bytes;
-	g.depth_sort_clear = P <= SORT_MAX_ITEMS ? onesweep_cleared_bytes<DEPTH_SORT_SHAPE>(P, 0u, DEPTH_KEY_BITS) : 0;
+	g.depth_sort_clear = DepthSort::cleared_bytes(P, DEPTH_KEY_BITS);
 	if (total) *total = c.size();
 	return g;
 }
@@ -267,8 +247,8 @@ BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_bytes,
 // (A wave-cooperative version — the 64 Gaussians of a wave own one contiguous output run; lanes take instances begin + l,
 // + 64, ..., find the owner by bisection over the start offsets in LDS and store 256 contiguous bytes per instruction —
 // was measured slower: 75 us against 57 us at R = 3.9 M.)
-// Per-Gaussian statistics between preprocess and the sorts, ONE dispatch (round 3; it replaces rocPRIM's 64-bit reduce of tiles_touched
-// and the histogram dispatch of the depth sort):
+// Per-Gaussian statistics between preprocess and the sorts, ONE dispatch (instead of a 64-bit rocPRIM reduce of tiles_touched and the
+// histogram dispatch of the depth sort):
 //   * num_rendered = sum of tiles_touched in 64 bits (the reference's 32-bit InclusiveSum, rasterizer_impl.cu:282, wraps silently),
 //   * the counts of the four 8-bit digits of the depth keys (per-workgroup LDS histogram, non-zero bins flushed with global atomics: what
 //     rocPRIM's onesweep_histograms does), laid out as the sort's pass kernels expect them.
@@ -342,10 +322,10 @@ __device__ __forceinline__ unsigned long long emit_pack(uint32_t flag, uint32_t 
 __device__ __forceinline__ void emit_publish(unsigned long long* p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned long long emit_peek(unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// duplicateWithKeys (rasterizer_impl.cu:70-111) for the Gaussians in depth order.  Round 3: the exclusive prefix sum of the instance
+// duplicateWithKeys (rasterizer_impl.cu:70-111) for the Gaussians in depth order.  The exclusive prefix sum of the instance
 // counts in that order — where each Gaussian's run starts — is computed HERE, as a single-pass chained scan (per-workgroup scan +
-// decoupled look-back over the workgroups in front, wave-parallel), instead of a rocPRIM inclusive_scan in front of this kernel: that
-// scan read tiles_touched through the depth order (a random 4-byte gather per Gaussian) and cost two dispatches, 19 us at C3 and 97 us
+// decoupled look-back over the workgroups in front, wave-parallel), instead of a rocPRIM inclusive_scan in front of this kernel: such a
+// scan reads tiles_touched through the depth order (a random 4-byte gather per Gaussian) and costs two dispatches, 19 us at C3 and 97 us
 // at C5; the count is the area of the tile rectangle, which this kernel gathers anyway (culled Gaussians carry an empty rectangle).
 // EMIT_ITEMS: Gaussians per thread (consecutive positions of the depth order).  Two halve the number of workgroups and of look-back hops but
 // double what a workgroup does between its ticket and its last store: emission 0.041 -> 0.060 ms at C3 (977 workgroups: two rounds over the
@@ -572,6 +552,47 @@ struct Readback {
 	int* dev_word = nullptr;   // the same memory as the device sees it
 	uint32_t seq = 0;
 	hipEvent_t done = nullptr;
+	int* mailbox = nullptr;    // of the read-back in flight: dev_word, or NULL = copy + event
+
+	// In front of gaussian_stats_kernel: mailbox or copy?  Returns the kernel's `mailbox` argument; its `seq` argument is this->seq.
+	// The trap flag flags[0] is only ever set, and cleared, with `prefiltered`: that (debugging) mode copies the four words back instead.
+	int* begin(int prefiltered) {
+		mailbox = (!prefiltered && dev_word != nullptr && option_mailbox()) ? dev_word : nullptr;
+		++seq;
+		return mailbox;
+	}
+	// Behind the kernel, copy path only: the four flag words to the pinned ones, and the event the host will wait on — THIS point of the
+	// stream, not the level-1 work enqueued behind it.  (With the mailbox no event is recorded: an event record is a 5-us bubble between the
+	// statistics kernel and the depth sort; the fallback of the spin in wait() is the stream itself.)
+	int copy_back(const int* flags, hipStream_t stream) {
+		if (mailbox) return 0;
+		GSR_HIP_CHECK(hipMemcpyAsync(word, flags, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+		GSR_HIP_CHECK(hipEventRecord(done, stream));
+		return 0;
+	}
+	// The host wait: 0 with num_rendered in *total and the trap flag in *trap, or < 0.
+	int wait(hipStream_t stream, unsigned long long* total, int* trap) {
+		if (mailbox) {
+			// spin on the sequence number the last workgroup of gaussian_stats_kernel stores; the way out, should the store not be seen while
+			// the kernel runs, is the stream running dry (the depth sort behind it, ~0.07 ms later): once the kernel has completed its writes are
+			// visible in any case
+			volatile uint32_t* box = reinterpret_cast<volatile uint32_t*>(word);
+			unsigned spins = 0;
+			while (box[4] != seq) {
+				if ((++spins & 63u) == 0u && hipStreamQuery(stream) != hipErrorNotReady) break;
+			}
+			if (box[4] != seq) {
+				GSR_HIP_CHECK(hipStreamSynchronize(stream));
+				if (box[4] != seq) { set_error("num_rendered mailbox was not written"); return GSR_E_HIP; }
+			}
+			__atomic_thread_fence(__ATOMIC_ACQUIRE);
+		} else {
+			GSR_HIP_CHECK(hipEventSynchronize(done));
+		}
+		memcpy(total, word + 2, sizeof(*total));
+		*trap = word[0];
+		return 0;
+	}
 };
 static Readback* readback_slot() {
 	static thread_local Readback slots[64];
@@ -594,67 +615,41 @@ static Readback* readback_slot() {
 
 static int rect_packs(int tiles_x, int tiles_y) { return (tiles_x <= 255 && tiles_y <= 255) ? 1 : 0; }   // see OrderRect
 
+// The stages in stream order: statistics (+ read-back on the copy path), depth sort, [the host waits for num_rendered and carves the
+// binning buffer], key emission, tile sort, tile ranges, tile order.
 int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int tiles_y, const GeomState& geom, const ImageState& img,
                 BinningState* out_binning, int prefiltered, int debug, hipStream_t stream, bool blend_masks) {
 	Readback* rb = readback_slot();
 	if (!rb) { set_error("pinned word / event for the num_rendered readback could not be created"); return GSR_E_HIP; }
-	int* host = rb->word;
-	int* mailbox = nullptr;
-	uint32_t seq = 0;
-	const bool own_depth_sort = option_sort_driver() && (size_t)P <= SORT_MAX_ITEMS;
 	{
+		// one dispatch (gaussian_stats_kernel): num_rendered = sum of tiles_touched, reduced in 64 bits (the reference's 32-bit InclusiveSum,
+		// rasterizer_impl.cu:282, wraps silently at 2^32 instances; its per-Gaussian offsets are not needed here: emit_tiles_kernel scans the
+		// instance counts in depth order itself, and gsr_debug_fetch("point_offsets") computes them on demand), and the depth keys' digit
+		// counts, into the start of the depth sort's temp where the preprocess kernel has cleared it (depth_sort_clear bytes)
 		StageTimer st_(GSR_STAGE_SCAN, stream);
-		// num_rendered = sum of tiles_touched, reduced in 64 bits (the reference's 32-bit InclusiveSum, rasterizer_impl.cu:282,
-		// wraps silently at 2^32 instances; its per-Gaussian offsets are not needed here: the instances are emitted in depth
-		// order from the second scan below, and gsr_debug_fetch("point_offsets") computes them on demand)
-		// one dispatch: the 64-bit sum and the depth keys' digit counts (gaussian_stats_kernel)
 		const unsigned blocks = (unsigned)std::min<size_t>(512, ((size_t)P + 4 * STATS_BLOCK - 1) / (4 * STATS_BLOCK));
-		// the trap flag flags[0] is only ever set, and cleared, with `prefiltered`: that (debugging) mode copies the four words back instead
-		mailbox = (!prefiltered && rb->dev_word != nullptr && option_mailbox()) ? rb->dev_word : nullptr;
-		seq = ++rb->seq;
+		int* mailbox = rb->begin(prefiltered);
 		gaussian_stats_kernel<<<blocks, STATS_BLOCK, 0, stream>>>(P, geom.depths, geom.tiles_touched,
-		                                                          own_depth_sort ? reinterpret_cast<uint32_t*>(geom.depth_sort_temp) : nullptr, geom.flags, mailbox, seq);
+		                                                          geom.depth_sort_clear ? reinterpret_cast<uint32_t*>(geom.depth_sort_temp) : nullptr, geom.flags, mailbox,
+		                                                          rb->seq);
 		GSR_LAUNCH_CHECK(debug, stream);
-		if (!mailbox) GSR_HIP_CHECK(hipMemcpyAsync(host, geom.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+		const int rc = rb->copy_back(geom.flags, stream);
+		if (rc < 0) return rc;
 	}
-	// the host waits on THIS point only, not on the level-1 work enqueued behind it.  (With the mailbox no event is recorded: an event record
-	// is a 5-us bubble between the statistics kernel and the depth sort; the fallback of the spin below is the stream itself.)
-	hipEvent_t readback_done = rb->done;
-	if (!mailbox) GSR_HIP_CHECK(hipEventRecord(readback_done, stream));
 	{
 		// level 1 (independent of num_rendered, so it runs while the host waits for the read-back): depth order of the
-		// Gaussians (31 key bits: depths are positive floats, their bit patterns order like the values); the scan of the
-		// instance counts taken in that order happens inside emit_tiles_kernel
+		// Gaussians (31 key bits: depths are positive floats, their bit patterns order like the values).  Look-back state cleared by the
+		// preprocess kernel, digit counts accumulated by gaussian_stats_kernel: four dispatches
 		StageTimer st_(GSR_STAGE_SORT, stream);
-		size_t tmp = geom.depth_sort_bytes;
-		if (own_depth_sort)   // look-back state cleared by the preprocess kernel, digit counts accumulated by gaussian_stats_kernel: four dispatches
-			GSR_HIP_CHECK(onesweep_sort_pairs<DEPTH_SORT_SHAPE>(geom.depth_sort_temp, tmp, reinterpret_cast<const uint32_t*>(geom.depths), geom.depth_sorted,
-			                                                   order_in(geom.rect, rect_packs(tiles_x, tiles_y)), geom.order, (size_t)P, 0u, DEPTH_KEY_BITS, stream, true,
-			                                                   reinterpret_cast<const uint32_t*>(geom.depth_sort_temp)));
-		else
-			GSR_HIP_CHECK(rocprim::radix_sort_pairs<SortConfig>(geom.depth_sort_temp, tmp, reinterpret_cast<const uint32_t*>(geom.depths), geom.depth_sorted,
-			                                                   order_in(geom.rect, rect_packs(tiles_x, tiles_y)), geom.order, (size_t)P, 0u, 31u, stream, false));
-	}
-	if (mailbox) {
-		// spin on the sequence number the last workgroup of gaussian_stats_kernel stores; the way out, should the store not be seen while
-		// the kernel runs, is the stream running dry (the depth sort behind it, ~0.07 ms later): once the kernel has completed its writes are
-		// visible in any case
-		volatile uint32_t* box = reinterpret_cast<volatile uint32_t*>(host);
-		unsigned spins = 0;
-		while (box[4] != seq) {
-			if ((++spins & 63u) == 0u && hipStreamQuery(stream) != hipErrorNotReady) break;
-		}
-		if (box[4] != seq) {
-			GSR_HIP_CHECK(hipStreamSynchronize(stream));
-			if (box[4] != seq) { set_error("num_rendered mailbox was not written"); return GSR_E_HIP; }
-		}
-		__atomic_thread_fence(__ATOMIC_ACQUIRE);
-	} else {
-		GSR_HIP_CHECK(hipEventSynchronize(readback_done));
+		GSR_HIP_CHECK(DepthSort::pairs(geom.depth_sort_temp, geom.depth_sort_bytes, reinterpret_cast<const uint32_t*>(geom.depths), geom.depth_sorted,
+		                               order_in(geom.rect, rect_packs(tiles_x, tiles_y)), geom.order, (size_t)P, DEPTH_KEY_BITS, stream, true,
+		                               reinterpret_cast<const uint32_t*>(geom.depth_sort_temp)));
 	}
 	unsigned long long total64;
-	memcpy(&total64, host + 2, sizeof(total64));
-	if (prefiltered && host[0] != 0) { set_error("Point is filtered although prefiltered is set. This shouldn't happen!"); return GSR_E_PREFILTERED; }
+	int trap;
+	const int waited = rb->wait(stream, &total64, &trap);
+	if (waited < 0) return waited;
+	if (prefiltered && trap != 0) { set_error("Point is filtered although prefiltered is set. This shouldn't happen!"); return GSR_E_PREFILTERED; }
 	if (total64 > 0x7fffffffull) { set_error("num_rendered = %llu does not fit the int the API returns", total64); return GSR_E_INVALID; }
 	const int R = (int)total64;
 	const uint32_t tiles = (uint32_t)tiles_x * (uint32_t)tiles_y;
@@ -669,41 +664,37 @@ int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int ti
 
 	if (R == 0) GSR_HIP_CHECK(hipMemsetAsync(img.ranges, 0, (size_t)tiles * sizeof(uint2), stream));   // otherwise emit_tiles_kernel clears them
 	if (R > 0) {
-		{ StageTimer st_(GSR_STAGE_EMIT_KEYS, stream);
-		const bool own_sort = option_sort_driver() && (size_t)R <= SORT_MAX_ITEMS;
-		const size_t clear_bytes = !own_sort ? 0 : tile_sort_7bit((size_t)R, bit) ? onesweep_cleared_bytes<TILE_SORT_SHAPE_SMALL7>((size_t)R, 0u, (unsigned)bit)
-		                         : tile_sort_small((size_t)R) ? onesweep_cleared_bytes<TILE_SORT_SHAPE_SMALL>((size_t)R, 0u, (unsigned)bit)
-		                                                                       : onesweep_cleared_bytes<TILE_SORT_SHAPE>((size_t)R, 0u, (unsigned)bit);
-		uint32_t* ticket = reinterpret_cast<uint32_t*>(geom.emit_state + (geom.emit_state_bytes / sizeof(unsigned long long) - 1));   // last state word: never a scan position
-		const int items = g_opt_emit_items ? g_opt_emit_items : (P >= EMIT_ITEMS2_FROM ? 2 : 1);
-		auto emit = rect_packs(tiles_x, tiles_y) ? (items == 2 ? emit_tiles_kernel<false, 2> : emit_tiles_kernel<false, 1>)
-		                                         : (items == 2 ? emit_tiles_kernel<true, 2> : emit_tiles_kernel<true, 1>);
-		emit<<<(P + EMIT_BLOCK * items - 1) / (EMIT_BLOCK * items), EMIT_BLOCK, 0, stream>>>(P, geom.order, geom.rect, geom.emit_state, ticket, b.tile_keys_unsorted,
-		                                                       b.vals_unsorted, (uint32_t)tiles_x, img.ranges, tiles, b.sort_temp, clear_bytes, b.blend_mask,
-		                                                       16 * b.mask_stride); }
+		{
+			// the (tile, index) instances in depth order; the kernel also clears the tile ranges, the blend masks and the tile sort's look-back state
+			StageTimer st_(GSR_STAGE_EMIT_KEYS, stream);
+			const size_t clear_bytes = with_tile_sort((size_t)R, bit, [&](auto sort) { return sort.cleared_bytes((size_t)R, (unsigned)bit); });
+			uint32_t* ticket = reinterpret_cast<uint32_t*>(geom.emit_state + (geom.emit_state_bytes / sizeof(unsigned long long) - 1));   // last state word: never a scan position
+			const int items = g_opt_emit_items ? g_opt_emit_items : (P >= EMIT_ITEMS2_FROM ? 2 : 1);
+			auto emit = rect_packs(tiles_x, tiles_y) ? (items == 2 ? emit_tiles_kernel<false, 2> : emit_tiles_kernel<false, 1>)
+			                                         : (items == 2 ? emit_tiles_kernel<true, 2> : emit_tiles_kernel<true, 1>);
+			emit<<<(P + EMIT_BLOCK * items - 1) / (EMIT_BLOCK * items), EMIT_BLOCK, 0, stream>>>(P, geom.order, geom.rect, geom.emit_state, ticket, b.tile_keys_unsorted,
+			                                                       b.vals_unsorted, (uint32_t)tiles_x, img.ranges, tiles, b.sort_temp, clear_bytes, b.blend_mask,
+			                                                       16 * b.mask_stride);
+		}
 		GSR_LAUNCH_CHECK(debug, stream);
-		size_t sb = b.sort_temp_bytes;
-		{ StageTimer st_(GSR_STAGE_SORT, stream);   // level 2: stable by tile id only
-		if (option_sort_driver() && (size_t)R <= SORT_MAX_ITEMS && tile_sort_7bit((size_t)R, bit))
-			GSR_HIP_CHECK(onesweep_sort_pairs<TILE_SORT_SHAPE_SMALL7>(b.sort_temp, sb, (const uint32_t*)b.tile_keys_unsorted, b.tile_keys,
-			                                                         (const uint32_t*)b.vals_unsorted, b.point_list, (size_t)R, 0u, (unsigned)bit, stream, true));
-		else if (option_sort_driver() && (size_t)R <= SORT_MAX_ITEMS && tile_sort_small((size_t)R))
-			GSR_HIP_CHECK(onesweep_sort_pairs<TILE_SORT_SHAPE_SMALL>(b.sort_temp, sb, (const uint32_t*)b.tile_keys_unsorted, b.tile_keys,
-			                                                        (const uint32_t*)b.vals_unsorted, b.point_list, (size_t)R, 0u, (unsigned)bit, stream, true));
-		else if (option_sort_driver() && (size_t)R <= SORT_MAX_ITEMS)
-			GSR_HIP_CHECK(onesweep_sort_pairs<TILE_SORT_SHAPE>(b.sort_temp, sb, (const uint32_t*)b.tile_keys_unsorted, b.tile_keys,
-			                                                  (const uint32_t*)b.vals_unsorted, b.point_list, (size_t)R, 0u, (unsigned)bit, stream, true));
-		else
-			GSR_HIP_CHECK(rocprim::radix_sort_pairs<SortConfig>(b.sort_temp, sb, b.tile_keys_unsorted, b.tile_keys, b.vals_unsorted, b.point_list, (size_t)R,
-			                                                   0u, (unsigned)bit, stream, false)); }
+		{
+			StageTimer st_(GSR_STAGE_SORT, stream);   // level 2: stable by tile id only
+			GSR_HIP_CHECK(with_tile_sort((size_t)R, bit, [&](auto sort) {
+				return sort.pairs(b.sort_temp, b.sort_temp_bytes, b.tile_keys_unsorted, b.tile_keys, b.vals_unsorted, b.point_list, (size_t)R, (unsigned)bit, stream, true);
+			}));
+		}
 		if (debug) GSR_HIP_CHECK(hipStreamSynchronize(stream));
-		{ StageTimer st_(GSR_STAGE_RANGES, stream);
-		tile_ranges_kernel<<<(R + 255) / 256, 256, 0, stream>>>(R, b.tile_keys, img.ranges); }
+		{
+			StageTimer st_(GSR_STAGE_RANGES, stream);
+			tile_ranges_kernel<<<(R + 255) / 256, 256, 0, stream>>>(R, b.tile_keys, img.ranges);
+		}
 		GSR_LAUNCH_CHECK(debug, stream);
 	}
-	{ StageTimer st_(GSR_STAGE_RANGES, stream);
-	const int rc = run_tile_order(img, tiles, stream);
-	if (rc < 0) return rc; }
+	{
+		StageTimer st_(GSR_STAGE_RANGES, stream);
+		const int rc = run_tile_order(img, tiles, stream);
+		if (rc < 0) return rc;
+	}
 	return R;
 }
 

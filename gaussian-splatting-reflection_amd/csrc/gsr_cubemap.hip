@@ -3,11 +3,11 @@
 // LEFT_TOP_AS_ORIGIN branch) and gaussian_renderer/__init__.py:22-35,148,178-179,197-199 +
 // utils/general_utils.py:177-197 of the reference.  One thread per direction / pixel; the cubemap itself
 // (<= 4.7 MB at L = 256) lives in L2 / Infinity Cache, the streaming traffic is the per-pixel planes.
+#include <algorithm>
 #include <cstring>
 #include "gsr_internal.hpp"
 #include <mutex>
 #include <memory>
-#include <rocprim/device/device_radix_sort.hpp>
 #include "gsr_sort.hpp"
 #include <rocprim/iterator/counting_iterator.hpp>
 #include "gsr_refl.hpp"
@@ -587,7 +587,7 @@ struct ReflScratch {
 // passes with 9- or 10-bit digits instead of three with 8.  Workgroup shape measured at n = 2 M pairs (whole backward, ms):
 // 256x12 0.361, 512x12 0.320, 1024x4 0.313, 1024x6 0.306, 1024x8 0.297, 1024x12 0.309, 1024x16 0.314.
 // `small`: 256-thread workgroups with 8-bit digits (for the choice see gsr_deferred_reflection_backward_keys).
-// Shape of the 9-bit sort (L = 128).  Round 4: 512 x 16 instead of 1024 x 8 — the same 8192 pairs per workgroup, but a workgroup that finds
+// Shape of the 9-bit sort (L = 128): 512 x 16 instead of 1024 x 8 — the same 8192 pairs per workgroup, but a workgroup that finds
 // room beside the backward's pixel kernel (see ENTRIES_BS); alone on the chip the two shapes are within 2 us of each other.
 #ifndef REFL_SORT_BS
 #define REFL_SORT_BS 512
@@ -595,38 +595,13 @@ struct ReflScratch {
 #ifndef REFL_SORT_IPT
 #define REFL_SORT_IPT 16
 #endif
-static hipError_t refl_sort(void* temp, size_t& bytes, int key_bits, const uint32_t* keys_in, uint32_t* keys_out, uint32_t* pix_out, size_t n, hipStream_t stream,
-                            bool pre_cleared = false, bool small = false, hipEvent_t gate = nullptr) {
-	rocprim::counting_iterator<uint32_t> pix_in(0);
-	if (temp == nullptr) {   // size query: the largest of the drivers' needs (neither the runtime switch nor the stream a tail runs on changes a scratch size)
-		size_t own = 0, pub = 0, sm = 0;
-		if (key_bits > 16 && key_bits <= 18) (void)onesweep_sort_pairs<REFL_SORT_BS, REFL_SORT_IPT, 9>(nullptr, own, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream);
-		else if (key_bits > 18 && key_bits <= 20) (void)onesweep_sort_pairs<1024, 8, 10>(nullptr, own, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream);
-		else (void)onesweep_sort_pairs<1024, 8, 8>(nullptr, own, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream);
-		(void)onesweep_sort_pairs<256, 8, 8>(nullptr, sm, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream);
-		(void)rocprim::radix_sort_pairs(nullptr, pub, (const uint32_t*)keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream, false);
-		bytes = own > pub ? own : pub;
-		if (sm > bytes) bytes = sm;
-		return hipSuccess;
-	}
-	if (!option_sort_driver()) {  // gsr_set_option("sort_driver", 0) or an unknown rocPRIM release: the public entry point (the gate then is the sort's end)
-		hipError_t e = rocprim::radix_sort_pairs(temp, bytes, (const uint32_t*)keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream, false);
-		if (e == hipSuccess && gate) e = hipEventRecord(gate, stream);
-		return e;
-	}
-	if (small)
-		return onesweep_sort_pairs<256, 8, 8>(temp, bytes, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream, pre_cleared, nullptr, gate);
-	if (key_bits > 16 && key_bits <= 18)
-		return onesweep_sort_pairs<REFL_SORT_BS, REFL_SORT_IPT, 9>(temp, bytes, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream, pre_cleared, nullptr, gate);
-	if (key_bits > 18 && key_bits <= 20)
-		return onesweep_sort_pairs<1024, 8, 10>(temp, bytes, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream, pre_cleared, nullptr, gate);
-	return onesweep_sort_pairs<1024, 8, 8>(temp, bytes, keys_in, keys_out, pix_in, pix_out, n, 0u, (unsigned)key_bits, stream, pre_cleared, nullptr, gate);
-}
-static size_t refl_sort_cleared_bytes(int key_bits, size_t n, bool small) {
-	if (small) return onesweep_cleared_bytes<256, 8, 8>(n, 0u, (unsigned)key_bits);
-	if (key_bits > 16 && key_bits <= 18) return onesweep_cleared_bytes<REFL_SORT_BS, REFL_SORT_IPT, 9>(n, 0u, (unsigned)key_bits);
-	if (key_bits > 18 && key_bits <= 20) return onesweep_cleared_bytes<1024, 8, 10>(n, 0u, (unsigned)key_bits);
-	return onesweep_cleared_bytes<1024, 8, 8>(n, 0u, (unsigned)key_bits);
+// The sort for key_bits-bit texel ids: f(the RadixSort of its shape).  Temp size, bytes to clear and the sort itself all come through here.
+template <class F>
+static auto with_refl_sort(int key_bits, bool small, F&& f) {
+	if (small) return f(RadixSort<256, 8, 8>{});
+	if (key_bits > 16 && key_bits <= 18) return f(RadixSort<REFL_SORT_BS, REFL_SORT_IPT, 9>{});
+	if (key_bits > 18 && key_bits <= 20) return f(RadixSort<1024, 8, 10>{});
+	return f(RadixSort<1024, 8, 8>{});
 }
 static ReflScratch refl_scratch(uint32_t L, int width, int height) {
 	ReflScratch r;
@@ -634,8 +609,13 @@ static ReflScratch refl_scratch(uint32_t L, int width, int height) {
 	r.n = (size_t)width * height;
 	r.key_bits = 1;
 	while (((size_t)1 << r.key_bits) <= r.ntex) r.key_bits++;   // keys take values 0..ntex (ntex = nothing to add)
-	r.sort_bytes = 0;
-	(void)refl_sort(nullptr, r.sort_bytes, r.key_bits, nullptr, nullptr, nullptr, r.n, 0);
+	// the larger of the normal and the `small` shape's needs: the stream a tail runs on does not change a scratch size
+	auto need = [&](bool small) {
+		return with_refl_sort(r.key_bits, small, [&](auto sort) {
+			return sort.temp_bytes((const uint32_t*)nullptr, rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, r.n, (unsigned)r.key_bits);
+		});
+	};
+	r.sort_bytes = std::max(need(false), need(true));
 	r.total_floats = (r.ntex + 2) * 4 + 8 * r.n + 3 * r.n + (r.sort_bytes + 3) / 4 + 128;   // + slack to align the sort temp
 	return r;
 }
@@ -714,16 +694,21 @@ struct ReflTail {
 		side = side_stream(true);
 		if (side) tail = side->stream;
 	}
-	size_t sort_cleared_bytes(bool small) const { return refl_sort_cleared_bytes(rs.key_bits, rs.n, small); }
+	size_t sort_cleared_bytes(bool small) const {
+		return with_refl_sort(rs.key_bits, small, [&](auto sort) { return sort.cleared_bytes(rs.n, (unsigned)rs.key_bits); });
+	}
 	// the side stream waits for what `stream` has enqueued so far
 	hipError_t fork(hipEvent_t ev) {
 		hipError_t e = hipEventRecord(ev, stream);
 		return e == hipSuccess ? hipStreamWaitEvent(side->stream, ev, 0) : e;
 	}
-	// gated: on the side stream, arm the gate (see side_gate_wait)
+	// (texel id, pixel) pairs; the caller has cleared sort_cleared_bytes(small) of the temp.  gated: on the side stream, arm the gate (see
+	// side_gate_wait): recorded in front of the sort's last pass, with the public driver at its end
 	hipError_t sort(const uint32_t* keys, bool small, bool gated) {
-		size_t sb = rs.sort_bytes;
-		hipError_t e = refl_sort(sort_temp, sb, rs.key_bits, keys, keys_out, pix_out, rs.n, tail, true, small, gated && side ? side->gate : nullptr);
+		hipError_t e = with_refl_sort(rs.key_bits, small, [&](auto sort) {
+			return sort.pairs(sort_temp, rs.sort_bytes, keys, keys_out, rocprim::counting_iterator<uint32_t>(0), pix_out, rs.n, (unsigned)rs.key_bits, tail, true, nullptr,
+			                  gated && side ? side->gate : nullptr);
+		});
 		if (e == hipSuccess && gated && side) side->gate_pending = true;
 		return e;
 	}

@@ -74,9 +74,10 @@ struct Carver {
 // kernels: REC_F4 float4 per Gaussian (G: 4 = 64 B, S: 5 = 80 B), written by preprocess.
 struct GeomState {
 	float* depths;           // P        view-space z (sort key low word)
-	uint32_t* rect;          // P        packed tile rect: xmin | ymin<<8 ... see pack_rect (2 words)
+	uint32_t* rect;          // 2P       tile rectangle, two words per Gaussian with 16-bit coordinates: xmin | ymin << 16, xmax | ymax << 16 (read by
+	                         //          emit_tiles_kernel<true> and OrderRect in gsr_common.hip; the 4 x 8-bit packing is OrderRect's, see `order`)
 	uint32_t* tiles_touched; // P
-	uint32_t* point_offsets; // P        inclusive scan
+	uint32_t* point_offsets; // P        inclusive scan of tiles_touched: not written by the forward, only by gsr_debug_fetch("point_offsets")
 	uint8_t* clamped;        // P        bit c set = SH colour channel c clamped at 0
 	float4* rec;             // P*REC_F4
 	float4* bbox;            // 2P       cull record: conservative screen-space footprint of the pixels a Gaussian can
@@ -89,9 +90,11 @@ struct GeomState {
 	uint32_t* depth_sorted;  // P        depth bits in ascending order (output of the depth pre-sort; keys only)
 	unsigned long long* order;   // P    at each position of the depth order (stable: ties by index): Gaussian index (low word) and its tile
 	                         //          rectangle packed to 4 x 8 bits (high word; 0 on grids beyond 255 tiles per axis) — OrderRect in gsr_common.hip
-	unsigned long long* emit_state;   // one word per 256 Gaussians: decoupled look-back state of emit_tiles_kernel's scan of the instance counts;
-	size_t emit_state_bytes;          //   the LAST word is the scan's ticket counter (multiple of 16; zeroed by the preprocess kernel)
-	void* scan_temp;         // temp of the two scans (shared) followed by the temp of the P-sized depth sort
+	unsigned long long* emit_state;   // decoupled look-back state of emit_tiles_kernel's scan of the instance counts, one word per workgroup of that
+	                                  //   kernel (EMIT_BLOCK = 1024 Gaussians or more each); SIZED as one word per 256 Gaussians, the bound for any
+	size_t emit_state_bytes;          //   EMIT_BLOCK >= 256.  The LAST word is the scan's ticket counter (multiple of 16; zeroed by the preprocess kernel)
+	void* scan_temp;         // temp of a rocPRIM scan over P values — the forward runs none, gsr_debug_fetch("point_offsets") does — followed by the
+	                         //   temp of the P-sized depth sort
 	size_t scan_temp_bytes;
 	void* depth_sort_temp;   // = scan_temp + scan part; its first depth_sort_clear bytes are zeroed by the preprocess kernel (they start with
 	                         //   the digit counts of the depth sort, which gaussian_stats_kernel then accumulates)
@@ -200,8 +203,9 @@ int run_tile_order(const ImageState& img, size_t tiles, hipStream_t stream);
 uint32_t higher_msb(uint32_t n);
 
 // Binning pipeline shared by both variants (reference: DSR/DGR rasterizer_impl.cu:282-325):
-// inclusive scan of tiles_touched -> num_rendered (pinned 4-byte readback) -> binning buffer via alloc
-// -> key/value emission -> radix sort -> tile ranges.  Returns num_rendered or <0.  blend_masks = false (a forward without backward):
+// per-Gaussian statistics (num_rendered in 64 bits, digit counts of the depth keys) -> depth sort of the P Gaussians, enqueued before the
+// host waits for num_rendered (mailbox in pinned memory, or copy + event) -> binning buffer via alloc -> emission of the (tile, index)
+// instances in depth order -> sort by tile id -> tile ranges -> longest-first tile order.  Returns num_rendered or <0.  blend_masks = false (a forward without backward):
 // no blend mask is reserved or cleared (mask_stride 0, blend_mask NULL); sort and ranges are the same.
 int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int tiles_y, const GeomState& geom,
                 const ImageState& img, BinningState* out_binning, int prefiltered, int debug, hipStream_t stream, bool blend_masks = true);

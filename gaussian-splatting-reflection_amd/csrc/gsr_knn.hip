@@ -19,7 +19,6 @@
 #include "gsr_internal.hpp"
 #include <algorithm>
 #include <cfloat>
-#include <rocprim/device/device_radix_sort.hpp>
 #include "gsr_sort.hpp"
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -31,7 +30,8 @@ namespace gsr {
 #define KNN_MORTON_BITS 30u
 #define KNN_SORT_SHAPE 1024, 4, 8   // the depth sort's shape (gsr_common.hip): P keys, four 8-bit places
 using KnnSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 65536>;
-static const size_t KNN_MAX_POINTS = (size_t)1 << 30;   // gsr_sort.hpp handles fewer than 2^30 items
+using KnnSort = RadixSort<KNN_SORT_SHAPE, KnnSortConfig>;
+static const size_t KNN_MAX_POINTS = (size_t)1 << 30;   // the C entries' range of P
 
 // The squared distance of the contract: dx*dx + dy*dy + dz*dz in float32, in this order and without contraction, for points and
 // for the lower bounds of boxes alike (see the exactness note above).
@@ -256,18 +256,6 @@ struct KnnLayout {
 	int n[KNN_LEVELS];
 };
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-// sort temp: the larger of the two drivers' needs, so that the runtime switch (option_sort_driver) never changes the size
-static size_t knn_sort_bytes(size_t P) {
-	size_t c = 0, d = 0;
-#if GSR_ONESWEEP_DRIVER
-	(void)onesweep_sort_pairs<KNN_SORT_SHAPE>(nullptr, c, (const uint32_t*)nullptr, (uint32_t*)nullptr, rocprim::counting_iterator<uint32_t>(0),
-	                                          (uint32_t*)nullptr, P, 0u, KNN_MORTON_BITS, 0);
-#endif
-	if (rocprim::radix_sort_pairs<KnnSortConfig>(nullptr, d, (const uint32_t*)nullptr, (uint32_t*)nullptr, rocprim::counting_iterator<uint32_t>(0),
-	                                             (uint32_t*)nullptr, P, 0u, KNN_MORTON_BITS, 0, false) != hipSuccess)
-		d = 0;
-	return std::max(c, d);
-}
 static KnnLayout knn_layout(size_t P) {
 	KnnLayout l;
 	size_t o = 0;
@@ -283,7 +271,7 @@ static KnnLayout knn_layout(size_t P) {
 		l.lo[k] = take((size_t)l.n[k] * 16);
 		l.hi[k] = take((size_t)l.n[k] * 16);
 	}
-	l.sort_bytes = knn_sort_bytes(P);
+	l.sort_bytes = KnnSort::temp_bytes((const uint32_t*)nullptr, rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, P, KNN_MORTON_BITS);
 	l.sort_temp = take(l.sort_bytes);
 	l.total = o;
 	return l;
@@ -328,14 +316,7 @@ extern "C" int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, v
 	const unsigned blocks = (unsigned)(((size_t)P + 255) / 256);
 	knn_morton_kernel<<<blocks, 256, 0, stream>>>(P, n_partial, points, partial, keys);
 	GSR_LAUNCH_CHECK(0, stream);
-	size_t tmp = l.sort_bytes;
-	void* sort_temp = base + l.sort_temp;
-	if (option_sort_driver())
-		GSR_HIP_CHECK(onesweep_sort_pairs<KNN_SORT_SHAPE>(sort_temp, tmp, keys, keys_sorted, rocprim::counting_iterator<uint32_t>(0), order, (size_t)P, 0u,
-		                                                  KNN_MORTON_BITS, stream));
-	else
-		GSR_HIP_CHECK(rocprim::radix_sort_pairs<KnnSortConfig>(sort_temp, tmp, keys, keys_sorted, rocprim::counting_iterator<uint32_t>(0), order, (size_t)P,
-		                                                       0u, KNN_MORTON_BITS, stream, false));
+	GSR_HIP_CHECK(KnnSort::pairs(base + l.sort_temp, l.sort_bytes, keys, keys_sorted, rocprim::counting_iterator<uint32_t>(0), order, (size_t)P, KNN_MORTON_BITS, stream));
 	knn_gather_leaves_kernel<<<blocks, 256, 0, stream>>>(P, points, order, sorted, reinterpret_cast<float4*>(base + l.lo[0]),
 	                                                     reinterpret_cast<float4*>(base + l.hi[0]));
 	GSR_LAUNCH_CHECK(0, stream);

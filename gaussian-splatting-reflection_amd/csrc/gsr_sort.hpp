@@ -6,7 +6,7 @@
 // are small enough (1-4 M pairs) to be bound by exactly that: the eight passes of a training step carried 17 fills.  This
 // driver gives every pass its own look-back states and block-id counter inside one temp region and clears the region once;
 // the device code is rocPRIM's own (rocprim::detail::onesweep_histograms / onesweep_iteration, header-only, ROCm 7.2), instantiated
-// with a fixed workgroup shape instead of the architecture dispatch.  Round 3: the per-place scan of the digit histograms is done by
+// with a fixed workgroup shape instead of the architecture dispatch.  The per-place scan of the digit histograms is done by
 // every workgroup of a pass in LDS (no scan dispatch), and a caller that has the keys in its hands in an earlier kernel can supply
 // the digit counts itself (no histogram dispatch): a sort is then exactly one dispatch per digit place.
 // Stable, ascending, keys compared on bits [begin_bit, end_bit).
@@ -17,7 +17,8 @@
 // What this file assumes about rocPRIM's PRIVATE device code, and how each assumption is guarded:
 //   * the signatures of detail::onesweep_histograms / onesweep_iteration and of block_id_wrapper:
 //     checked by the compiler; the driver is only compiled for the rocPRIM release it was written against
-//     (GSR_ONESWEEP_DRIVER below), any other release takes the public rocprim::radix_sort_pairs for every sort;
+//     (GSR_ONESWEEP_DRIVER below), any other release takes the public rocprim::radix_sort_pairs for every sort (RadixSort, the one
+//     entry every sort of the library goes through, chooses);
 //   * an all-zero onesweep_lookback_state means "empty" and is 4 bytes: static_asserts below;
 //   * the temp layout is THIS driver's own (it passes every pointer explicitly), not rocPRIM's;
 //   * a runtime switch (gsr_set_option("sort_driver", 0)) forces the public path, and tests/test_gpu_api_paths.py asserts that
@@ -31,15 +32,17 @@
 #if ROCPRIM_VERSION / 100 == 4002      // rocPRIM 4.2.x (ROCm 7.2): the release whose detail:: entry points are used below
 #define GSR_ONESWEEP_DRIVER 1
 #else
-#define GSR_ONESWEEP_DRIVER 0          // unknown internals: public rocprim::radix_sort_pairs only
+#define GSR_ONESWEEP_DRIVER 0          // unknown internals: public rocprim::radix_sort_pairs only (the driver is not compiled)
 #endif
 
 namespace gsr {
 
 int option_sort_driver();   // 1 (default): one-clear Onesweep driver of this file; 0: rocprim::radix_sort_pairs (gsr_set_option("sort_driver", ...))
 
-#if GSR_ONESWEEP_DRIVER
 using SortOffset = unsigned int;
+constexpr size_t ONESWEEP_MAX_ITEMS = (size_t)1 << 30;   // the driver handles one rocPRIM batch; from here on rocPRIM itself
+
+#if GSR_ONESWEEP_DRIVER
 using SortBlockId = rocprim::detail::block_id_wrapper<unsigned int, true>;
 using SortLookback = rocprim::detail::onesweep_lookback_state;
 static_assert(sizeof(SortLookback) == 4, "onesweep_lookback_state is expected to be one 32-bit word (flag in the top two bits)");
@@ -83,63 +86,54 @@ __global__ void __launch_bounds__(BS) sort_pass_kernel(const uint32_t* keys_in, 
 	    full_blocks, block_id);
 }
 
-// Bytes at the start of the temp region that must be zero when the sort starts (multiple of 256).  A caller that has a
-// kernel running in front of the sort anyway can clear them there (sort_clear_region below) and pass pre_cleared = true:
-// one dispatch less.
+// The temp region of one sort.  First what must be zero when the sort starts — digit counts at 0 [radix * places], offsets of the next batch
+// [radix], per pass its look-back states [radix * blocks], the block-id counters [places, one per 64 bytes] — `cleared` bytes in all (a
+// multiple of 256); behind them the key and the value buffer the passes alternate with.  size < ONESWEEP_MAX_ITEMS, begin_bit < end_bit.
+struct OnesweepLayout { unsigned places, blocks; size_t o_next, o_lookback, lookback_pass, o_ids, cleared; };
+static inline size_t sort_up256(size_t b) { return (b + 255) & ~(size_t)255; }
 template <unsigned BS, unsigned IPT, unsigned BITS>
-size_t onesweep_cleared_bytes(size_t size_, unsigned begin_bit, unsigned end_bit) {
-	constexpr unsigned radix = 1u << BITS, items_per_block = BS * IPT;
-	if (size_ >= ((size_t)1 << 30) || end_bit <= begin_bit) return 0;
-	const unsigned size = (unsigned)size_;
-	const unsigned places = (end_bit - begin_bit + BITS - 1) / BITS;
-	const unsigned blocks = (size + items_per_block - 1) / items_per_block;
-	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-	return up((size_t)radix * places * sizeof(SortOffset)) + up((size_t)radix * sizeof(SortOffset)) +
-	       up((size_t)radix * (blocks ? blocks : 1) * sizeof(SortLookback)) * places + up((size_t)places * 64);
-}
-// grid-stride clear of `bytes` (multiple of 16) at `ptr` (16-byte aligned) by the calling kernel's threads
-__device__ __forceinline__ void sort_clear_region(void* ptr, size_t bytes, size_t thread, size_t threads) {
-	uint4* p = static_cast<uint4*>(ptr);
-	for (size_t i = thread; i < bytes / 16; i += threads) p[i] = make_uint4(0u, 0u, 0u, 0u);
+OnesweepLayout onesweep_layout(unsigned size, unsigned begin_bit, unsigned end_bit) {
+	constexpr size_t radix = (size_t)1 << BITS;
+	OnesweepLayout l;
+	l.places = (end_bit - begin_bit + BITS - 1) / BITS;
+	l.blocks = (size + BS * IPT - 1) / (BS * IPT);
+	l.o_next = sort_up256(radix * l.places * sizeof(SortOffset));
+	l.o_lookback = l.o_next + sort_up256(radix * sizeof(SortOffset));
+	l.lookback_pass = sort_up256(radix * (l.blocks ? l.blocks : 1) * sizeof(SortLookback));
+	l.o_ids = l.o_lookback + l.lookback_pass * l.places;
+	l.cleared = l.o_ids + sort_up256((size_t)l.places * 64);
+	return l;
 }
 
-// temp == nullptr: returns the required bytes in `bytes` and does nothing else.  size < 2^30.
+// temp == nullptr: returns the required bytes in `bytes` and does nothing else.
+// pre_cleared: the first `cleared` bytes of temp are zero already — a caller that has a kernel running in front of the sort anyway clears
+// them there (sort_clear_region below): one dispatch less.
 // ext_counts != nullptr: the raw digit counts — 2^BITS per place, place p counting digit (key >> (begin_bit + p * BITS)) & (2^BITS - 1)
 // over ALL `size` keys — have already been accumulated there by a kernel that had the keys in its hands anyway (the per-Gaussian
-// statistics kernel for the depth keys, key emission for the tile ids): no histogram dispatch.
+// statistics kernel for the depth keys): no histogram dispatch.
+// before_last_pass: recorded in front of the last pass (a caller that must not let another kernel take the chip before that pass has started).
 template <unsigned BS, unsigned IPT, unsigned BITS, class ValuesIn, class Value>
 hipError_t onesweep_sort_pairs(void* temp, size_t& bytes, const uint32_t* keys_in, uint32_t* keys_out, ValuesIn values_in, Value* values_out, size_t size_,
-                               unsigned begin_bit, unsigned end_bit, hipStream_t stream, bool pre_cleared = false, const SortOffset* ext_counts = nullptr,
-                               hipEvent_t before_last_pass = nullptr) {
+                               unsigned begin_bit, unsigned end_bit, hipStream_t stream, bool pre_cleared, const SortOffset* ext_counts,
+                               hipEvent_t before_last_pass) {
 	static_assert(sizeof(Value) == 4 || sizeof(Value) == 8, "4- or 8-byte values");
 	constexpr unsigned radix = 1u << BITS, items_per_block = BS * IPT;
-	if (size_ >= ((size_t)1 << 30) || end_bit <= begin_bit) return hipErrorInvalidValue;
+	if (size_ >= ONESWEEP_MAX_ITEMS || end_bit <= begin_bit) return hipErrorInvalidValue;
 	const unsigned size = (unsigned)size_;
-	const unsigned places = (end_bit - begin_bit + BITS - 1) / BITS;
-	const unsigned blocks = (size + items_per_block - 1) / items_per_block;
-	const unsigned full_blocks = size % items_per_block == 0 ? blocks : blocks - 1;
-	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-	// cleared region: [digit offsets radix*places][offsets of the next batch radix][per pass: look-back radix*blocks][block-id counters places]
-	const size_t o_digits = 0;
-	const size_t o_next = o_digits + up((size_t)radix * places * sizeof(SortOffset));
-	const size_t o_lookback = o_next + up((size_t)radix * sizeof(SortOffset));
-	const size_t lookback_pass = up((size_t)radix * (blocks ? blocks : 1) * sizeof(SortLookback));
-	const size_t o_ids = o_lookback + lookback_pass * places;
-	const size_t cleared = o_ids + up((size_t)places * 64);   // one counter per 64 bytes
-	const size_t o_keys_tmp = cleared;
-	const size_t o_vals_tmp = o_keys_tmp + up((size_t)size * 4);
-	const size_t total = o_vals_tmp + up((size_t)size * sizeof(Value));
+	const OnesweepLayout l = onesweep_layout<BS, IPT, BITS>(size, begin_bit, end_bit);
+	const unsigned places = l.places, blocks = l.blocks, full_blocks = size % items_per_block == 0 ? blocks : blocks - 1;
+	const size_t o_vals_tmp = l.cleared + sort_up256((size_t)size * 4), total = o_vals_tmp + sort_up256((size_t)size * sizeof(Value));
 	if (temp == nullptr) { bytes = total; return hipSuccess; }
 	if (bytes < total) return hipErrorInvalidValue;
 	if (size == 0) return hipSuccess;
 	char* base = static_cast<char*>(temp);
-	SortOffset* digits = reinterpret_cast<SortOffset*>(base + o_digits);
-	SortOffset* next = reinterpret_cast<SortOffset*>(base + o_next);
-	uint32_t* keys_tmp = reinterpret_cast<uint32_t*>(base + o_keys_tmp);
+	SortOffset* digits = reinterpret_cast<SortOffset*>(base);
+	SortOffset* next = reinterpret_cast<SortOffset*>(base + l.o_next);
+	uint32_t* keys_tmp = reinterpret_cast<uint32_t*>(base + l.cleared);
 	Value* values_tmp = reinterpret_cast<Value*>(base + o_vals_tmp);
 
 	if (!pre_cleared) {
-		hipError_t e = hipMemsetAsync(base, 0, cleared, stream);
+		hipError_t e = hipMemsetAsync(base, 0, l.cleared, stream);
 		if (e != hipSuccess) return e;
 	}
 	const SortOffset* counts = ext_counts;
@@ -157,12 +151,12 @@ hipError_t onesweep_sort_pairs(void* temp, size_t& bytes, const uint32_t* keys_i
 	unsigned place = 0;
 	for (unsigned bit = begin_bit; bit < end_bit; bit += BITS, ++place) {
 		const unsigned current_bits = (end_bit - bit) < BITS ? (end_bit - bit) : BITS;
-		SortLookback* lookback = reinterpret_cast<SortLookback*>(base + o_lookback + lookback_pass * place);
-		SortBlockId block_id = SortBlockId::create(base + o_ids + (size_t)place * 64);
+		SortLookback* lookback = reinterpret_cast<SortLookback*>(base + l.o_lookback + l.lookback_pass * place);
+		SortBlockId block_id = SortBlockId::create(base + l.o_ids + (size_t)place * 64);
 		const SortOffset* d_in = counts + (size_t)place * radix;
 		uint32_t* k_out = to_output ? keys_out : keys_tmp;
 		Value* v_out = to_output ? values_out : values_tmp;
-		if (before_last_pass != nullptr && place + 1 == places) {     // (a caller that must not let another kernel take the chip before the LAST pass has started)
+		if (before_last_pass != nullptr && place + 1 == places) {
 			hipError_t e = hipEventRecord(before_last_pass, stream);
 			if (e != hipSuccess) return e;
 		}
@@ -180,16 +174,58 @@ hipError_t onesweep_sort_pairs(void* temp, size_t& bytes, const uint32_t* keys_i
 	}
 	return hipGetLastError();
 }
-#else   // !GSR_ONESWEEP_DRIVER: nothing to clear, and the sort entry point reports "not available" so that callers take rocPRIM's own
-template <unsigned BS, unsigned IPT, unsigned BITS>
-size_t onesweep_cleared_bytes(size_t, unsigned, unsigned) { return 0; }
-__device__ __forceinline__ void sort_clear_region(void*, size_t, size_t, size_t) {}
-template <unsigned BS, unsigned IPT, unsigned BITS, class ValuesIn, class Value>
-hipError_t onesweep_sort_pairs(void* temp, size_t& bytes, const uint32_t*, uint32_t*, ValuesIn, Value*, size_t, unsigned, unsigned, hipStream_t, bool = false,
-                               const unsigned* = nullptr, hipEvent_t = nullptr) {
-	if (temp == nullptr) bytes = 0;
-	return hipErrorNotSupported;
-}
 #endif
+
+// grid-stride clear of `bytes` (multiple of 16) at `ptr` (16-byte aligned) by the calling kernel's threads
+__device__ __forceinline__ void sort_clear_region(void* ptr, size_t bytes, size_t thread, size_t threads) {
+	uint4* p = static_cast<uint4*>(ptr);
+	for (size_t i = thread; i < bytes / 16; i += threads) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// the first pass reads pointer values through the later passes' `const Value*`: one pass kernel per sort, not two
+template <class T> const T* sort_values_in(T* p) { return p; }
+template <class It> It sort_values_in(It it) { return it; }
+
+// THE sort entry of the library: n (uint32 key, value) pairs, stable, ascending on key bits [0, end_bit), with workgroups of BS threads x
+// IPT items and BITS-bit digits.  Which driver sorts, how much temp that takes and how much of it must be zero is decided here and
+// nowhere else: the Onesweep driver above when option_sort_driver() and n < ONESWEEP_MAX_ITEMS, else rocprim::radix_sort_pairs with
+// PublicConfig (results bit-identical: tests/test_gpu_api_paths.py, tests/test_gpu_knn.py).
+template <unsigned BS, unsigned IPT, unsigned BITS, class PublicConfig = rocprim::default_config>
+struct RadixSort {
+	// Bytes of temp: the LARGER of the two drivers' needs, so that the runtime switch never changes a workspace size.  (The arguments
+	// only give the types.)
+	template <class KeysIn, class ValuesIn, class Value>
+	static size_t temp_bytes(KeysIn keys_in, ValuesIn values_in, Value* values_out, size_t n, unsigned end_bit) {
+		size_t own = 0, pub = 0;
+#if GSR_ONESWEEP_DRIVER
+		(void)onesweep_sort_pairs<BS, IPT, BITS>(nullptr, own, keys_in, nullptr, sort_values_in(values_in), values_out, n, 0u, end_bit, nullptr, false, nullptr, nullptr);
+#endif
+		(void)rocprim::radix_sort_pairs<PublicConfig>(nullptr, pub, keys_in, (uint32_t*)nullptr, values_in, values_out, n, 0u, end_bit, nullptr, false);
+		return own > pub ? own : pub;
+	}
+	// Bytes at the start of temp that must be zero when pairs(..., pre_cleared = true) starts.  By shape, n and end_bit only, never by the
+	// runtime option: callers fix this number — and kernels clear that many bytes — before the option is consulted.  Bytes cleared for
+	// nothing when the public driver then runs are harmless: temp is at least the own driver's size.
+	static size_t cleared_bytes(size_t n, unsigned end_bit) {
+#if GSR_ONESWEEP_DRIVER
+		if (n < ONESWEEP_MAX_ITEMS && end_bit > 0) return onesweep_layout<BS, IPT, BITS>((unsigned)n, 0u, end_bit).cleared;
+#endif
+		return 0;
+	}
+	// The sort; temp of temp_bytes() bytes.  pre_cleared, ext_counts: see onesweep_sort_pairs; the public driver ignores both.
+	// before_last_pass: recorded on `stream` exactly once — in front of the own driver's last pass, behind the public sort.
+	template <class KeysIn, class ValuesIn, class Value>
+	static hipError_t pairs(void* temp, size_t bytes, KeysIn keys_in, uint32_t* keys_out, ValuesIn values_in, Value* values_out, size_t n, unsigned end_bit,
+	                        hipStream_t stream, bool pre_cleared = false, const SortOffset* ext_counts = nullptr, hipEvent_t before_last_pass = nullptr) {
+#if GSR_ONESWEEP_DRIVER
+		if (option_sort_driver() && n < ONESWEEP_MAX_ITEMS)
+			return onesweep_sort_pairs<BS, IPT, BITS>(temp, bytes, keys_in, keys_out, sort_values_in(values_in), values_out, n, 0u, end_bit, stream, pre_cleared,
+			                                          ext_counts, before_last_pass);
+#endif
+		hipError_t e = rocprim::radix_sort_pairs<PublicConfig>(temp, bytes, keys_in, keys_out, values_in, values_out, n, 0u, end_bit, stream, false);
+		if (e == hipSuccess && before_last_pass != nullptr) e = hipEventRecord(before_last_pass, stream);
+		return e;
+	}
+};
 
 }  // namespace gsr

@@ -1,13 +1,16 @@
-"""Development aid (runs here, no GPU): one line per kernel of the two rasterizer variants' translation units with the sha256 of its
-normalised gfx950 instruction stream and the VGPR / SGPR / LDS / scratch sizes of its kernel descriptor.  Two trees whose output is equal
-run the same device code, so a refactor of the tile kernels is checked by
+"""Development aid (runs here, no GPU): one line per kernel of every translation unit of the library (csrc/build.py's SOURCES) with the
+sha256 of its normalised gfx950 instruction stream and the VGPR / SGPR / LDS / scratch sizes of its kernel descriptor.  Two trees whose
+output is equal run the same device code, so a refactor of the kernels' surroundings or of the host code is checked by
 
     python tests/isa_digest.py [CSRC_DIR] > result.txt        # CSRC_DIR: another tree's csrc/ (default: this tree's)
     diff parent.txt result.txt
 
 The compile is csrc/build.py's (same flags, per-file extras included) with -S --cuda-device-only.  Normalised means: comments, debug and
 assembler directives dropped, and every mangled symbol replaced by its demangled name without the parameter list, so that renaming a
-parameter type (which changes only the mangling) leaves the digest alone while any moved or changed instruction does not."""
+parameter type (which changes only the mangling) leaves the digest alone while any moved or changed instruction does not.  Where a
+kernel stands in its translation unit is no device code either: basic-block labels lose the function's number and the lines are sorted by
+kernel name, so host code that instantiates the same kernels in another order gives the same output."""
+import concurrent.futures
 import hashlib
 import os
 import re
@@ -19,7 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-reflection_amd", "csrc"))
 import build as B  # noqa: E402
 
-SOURCES = ["gsr_gauss.hip", "gsr_surfel.hip"]
 DESC = {"vgpr": ".amdhsa_next_free_vgpr", "sgpr": ".amdhsa_next_free_sgpr", "lds": ".amdhsa_group_segment_fixed_size",
         "scratch": ".amdhsa_private_segment_fixed_size"}
 
@@ -56,17 +58,20 @@ def kernels(csrc, src):
         for l in lines[start + 1:end]:
             t = l.split(";")[0].strip()
             if t and not re.match(r"\.(loc|file|cfi_|ident|p2align)", t):
-                body.append(re.sub(r"\b_Z\w+", lambda s: short[s.group(0)], " ".join(t.split())))
+                t = re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", " ".join(t.split()))      # (.LBB<position of the function in the unit>_<block>)
+                body.append(re.sub(r"\b_Z\w+", lambda s: short[s.group(0)], t))
         desc = text[m.end():text.index(".end_amdhsa_kernel", m.end())]
         sizes = {k: int(re.search(re.escape(d) + r" (\d+)", desc).group(1)) for k, d in DESC.items()}
         res.append((short[name], body, sizes))
-    return res
+    return sorted(res, key=lambda r: r[0])
 
 
 def main():
     csrc = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else B.HERE
-    for src in SOURCES:
-        for name, body, sizes in kernels(csrc, src):
+    with concurrent.futures.ThreadPoolExecutor(max_workers=4) as ex:      # (as build.py: at most 4 hipcc jobs at a time)
+        per_source = list(ex.map(lambda src: kernels(csrc, src), B.SOURCES))
+    for src, found in zip(B.SOURCES, per_source):
+        for name, body, sizes in found:
             print("%s %s lines=%d vgpr=%d sgpr=%d lds=%d scratch=%d sha256=%s" % (src, name, len(body), sizes["vgpr"], sizes["sgpr"], sizes["lds"], sizes["scratch"],
                                                                                 hashlib.sha256("\n".join(body).encode()).hexdigest()))
 
