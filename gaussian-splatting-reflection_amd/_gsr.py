@@ -17,6 +17,7 @@ c_void_p, c_int, c_float, c_size_t, c_uint32, c_char_p = (ctypes.c_void_p, ctype
 ALLOC_FN = ctypes.CFUNCTYPE(c_void_p, c_void_p, c_int, c_size_t)
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE = 0, 1, 2
+GSR_PRESENT_CLAMP, GSR_PRESENT_QUANT8 = 1, 2     # presentation flags of gsr_image_metrics
 
 
 class GsrError(RuntimeError):
@@ -150,6 +151,17 @@ def _load():
         lib.gsr_knn_scratch_bytes.argtypes = [c_int]
         lib.gsr_knn_mean_dist.restype = c_int
         lib.gsr_knn_mean_dist.argtypes = [c_int, P, P, P, c_size_t, P]
+    if hasattr(lib, "gsr_image_metrics"):
+        # (likewise: a library built before the evaluation metrics lacks these four; utils.image_utils, utils.mae_utils and gsr_eval
+        # then refuse to import)
+        lib.gsr_image_metrics_scratch_floats.restype = c_size_t
+        lib.gsr_image_metrics_scratch_floats.argtypes = [c_int, c_int, c_int]
+        lib.gsr_image_metrics.restype = c_int
+        lib.gsr_image_metrics.argtypes = [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P, P, P]
+        lib.gsr_normal_mae_scratch_floats.restype = c_size_t
+        lib.gsr_normal_mae_scratch_floats.argtypes = [c_int, c_int]
+        lib.gsr_normal_mae.restype = c_int
+        lib.gsr_normal_mae.argtypes = [P, P, c_int, c_int, c_float, c_float, c_float, P, P, c_size_t, P, P]
     return lib
 
 
@@ -189,7 +201,8 @@ EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_b
             "gsr_deferred_reflection_backward_accum", "gsr_deferred_reflection_backward_ex", "gsr_deferred_reflection_forward_ex", "gsr_side_join", "gsr_normal_world_forward", "gsr_normal_world_backward", "gsr_gauss_forward", "gsr_gauss_backward", "gsr_gauss_backward_accum",
             "gsr_mark_visible", "gsr_debug_fetch", "gsr_cubemap_forward", "gsr_cubemap_backward", "gsr_deferred_reflection_forward",
             "gsr_deferred_reflection_scratch_floats", "gsr_deferred_reflection_backward", "gsr_ssim_l1_scratch_floats", "gsr_ssim_l1_forward", "gsr_ssim_l1_backward", "gsr_normal_loss_scratch_floats", "gsr_normal_loss_forward", "gsr_normal_loss_backward", "gsr_adam_step", "gsr_adam_step_range", "gsr_densification_stats", "gsr_gather_rows", "gsr_split_children", "gsr_surface_forward", "gsr_surface_backward", "gsr_profile_enable",
-            "gsr_profile_collect", "gsr_set_option", "gsr_knn_scratch_bytes", "gsr_knn_mean_dist"]
+            "gsr_profile_collect", "gsr_set_option", "gsr_knn_scratch_bytes", "gsr_knn_mean_dist",
+            "gsr_image_metrics_scratch_floats", "gsr_image_metrics", "gsr_normal_mae_scratch_floats", "gsr_normal_mae"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

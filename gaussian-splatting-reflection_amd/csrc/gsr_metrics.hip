@@ -1,0 +1,219 @@
+// Evaluation metrics on the device: what the reference computes after training to judge a model.
+//   * image_metrics_kernel: metrics.py (PSNR = utils/image_utils.py:20-23, SSIM = utils/loss_utils.py:62-92) on the images as
+//     render.py:48-62 presents them: clamp, alpha compositing onto the background, 8-bit quantisation (save_image + to_tensor).
+//     Same 32x32 tile, 42x42 zero-padded halo and separable 11x11 window as the training loss (gsr_ssim.hpp), but the images
+//     are presented while they are staged into LDS, nothing is kept for a backward, and a view leaves three sums:
+//     sum (v - g)^2, sum |v - g| and sum ssim_map.  Global traffic: the reads alone, 8 B per pixel-channel (+ alpha / mask).
+//   * normal_mae_kernel: eval_mae.py / utils/mae_utils.py:3-29, the angle between predicted and ground-truth normals.
+// Block partials are added in a fixed order in double and written to one row of a caller-owned table: a test set needs one
+// read-back at its end, and every number is bitwise reproducible.
+#include "gsr_internal.hpp"
+#include "gsr_ssim.hpp"
+#include <algorithm>
+
+namespace gsr {
+
+// torchvision.utils.save_image followed by to_tensor: uint8(clamp(t * 255 + 0.5, 0, 255)) / 255 in float32, every operation
+// rounded on its own.  hipcc contracts a * b + c into an FMA by default, which rounds once where torch rounds twice; the _rn
+// intrinsics are never contracted, so the 8-bit images are torch's by construction and not by the luck of the inputs.
+__device__ __forceinline__ float quantize8(float t) {
+	const float s = fminf(fmaxf(__fadd_rn(__fmul_rn(t, 255.0f), 0.5f), 0.0f), 255.0f);
+	return __fdiv_rn((float)(unsigned int)s, 255.0f);
+}
+// render.py:54-56: t * a + (1 - a) * bg, as the four separately rounded float32 operations of the torch expression
+__device__ __forceinline__ float composite(float t, float a, float bg) {
+	return __fadd_rn(__fmul_rn(t, a), __fmul_rn(__fsub_rn(1.0f, a), bg));
+}
+
+struct Presentation {
+	const float* alpha;      // [H,W] or NULL: rendered image composited with clamp(alpha, 0, 1)
+	const float* gt_mask;    // [H,W] or NULL: ground truth composited with it
+	const float* background; // [C]
+	int clamp, quantize;
+};
+
+__global__ void __launch_bounds__(256)
+image_metrics_kernel(const float* __restrict__ img, const float* __restrict__ gt, int H, int W, SsimWindow win, float C1, float C2, Presentation pr,
+                     float4* __restrict__ partials, uint8_t* __restrict__ img_u8, uint8_t* __restrict__ gt_u8) {
+	__shared__ float ta[SSIM_HALO][SSIM_HALO + 1], tb[SSIM_HALO][SSIM_HALO + 1];
+	__shared__ float hs[5][SSIM_HALO][SSIM_T + 1];
+	__shared__ float red[3][4];
+	const size_t plane = (size_t)blockIdx.z * H * W;
+	const int x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
+	{
+		const float* const x = img + plane;
+		const float* const y = gt + plane;
+		const float bg = pr.background ? pr.background[blockIdx.z] : 0.f;
+		float (*const dst[2])[SSIM_HALO + 1] = {ta, tb};
+		// the padding of the convolution surrounds the PRESENTED image: outside the image both planes stay zero
+		ssim_stage_tiles<2>([&](bool in, size_t o, float (&t)[2]) {
+			float v = 0.f, g = 0.f;
+			if (in) {
+				v = x[o]; g = y[o];
+				if (pr.clamp) v = fminf(fmaxf(v, 0.f), 1.f);
+				if (pr.alpha) v = composite(v, fminf(fmaxf(pr.alpha[o], 0.f), 1.f), bg);
+				if (pr.gt_mask) g = composite(g, pr.gt_mask[o], bg);
+				if (pr.quantize) { v = quantize8(v); g = quantize8(g); }
+			}
+			t[0] = v; t[1] = g;
+		}, H, W, x0, y0, dst);
+	}
+	__syncthreads();
+	ssim_moments_hpass(ta, tb, hs, win);
+	__syncthreads();
+	const int tx = threadIdx.x & 31, tq = threadIdx.x >> 5;
+	const int gx = x0 + tx;
+	float col[5][SSIM_B + 10];
+	ssim_load_columns<5>(hs, tx, tq, col);
+	float sse = 0.f, sad = 0.f, ssim_sum = 0.f;
+#pragma unroll
+	for (int r = 0; r < SSIM_B; r++) {
+		const int ty = tq * SSIM_B + r, gy = y0 + ty;
+		if (gx < W && gy < H) {
+			const float v = ta[ty + SSIM_R][tx + SSIM_R], g = tb[ty + SSIM_R][tx + SSIM_R];
+			const float d = v - g;
+			sse += d * d;
+			sad += fabsf(d);
+			ssim_sum += ssim_value(col, r, win, C1, C2);
+			const size_t o = plane + (size_t)gy * W + gx;
+			// a presented value is k / 255 rounded once: times 255 it is within 2^-15 of k, so the truncation gives k back
+			if (img_u8) img_u8[o] = (uint8_t)(unsigned int)(v * 255.0f + 0.5f);
+			if (gt_u8) gt_u8[o] = (uint8_t)(unsigned int)(g * 255.0f + 0.5f);
+		}
+	}
+	float r4[4] = {sse, sad, ssim_sum, 0.f};
+	wave_sum4(r4);
+	const int wave = threadIdx.x >> 6;
+	if ((threadIdx.x & 63) == 63) { red[0][wave] = r4[0]; red[1][wave] = r4[1]; red[2][wave] = r4[2]; }
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+		partials[blk] = make_float4((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]),
+		                            (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]), 0.f);
+	}
+}
+
+// second stage of both kernels: one workgroup adds the blocks' float4 partials in double, in a fixed order, into the row
+__global__ void __launch_bounds__(256) metrics_reduce_kernel(const float4* __restrict__ partials, size_t nblocks, double last, double* __restrict__ row) {
+	__shared__ double red[3][256];
+	double a = 0.0, b = 0.0, c = 0.0;
+	for (size_t i = threadIdx.x; i < nblocks; i += 256) {
+		const float4 p = partials[i];
+		a += (double)p.x; b += (double)p.y; c += (double)p.z;
+	}
+	red[0][threadIdx.x] = a; red[1][threadIdx.x] = b; red[2][threadIdx.x] = c;
+	__syncthreads();
+	for (int s = 128; s > 0; s >>= 1) {
+		if ((int)threadIdx.x < s) {
+#pragma unroll
+			for (int k = 0; k < 3; k++) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x < 3) row[threadIdx.x] = red[threadIdx.x][0];
+	if (threadIdx.x == 3) row[3] = last;
+}
+
+// utils/mae_utils.py:10-27 per pixel, in float32 as torch evaluates it.  A pixel is invalid where a norm is <= eps or the angle
+// is NaN (a NaN input: the clamp below would turn a NaN cosine into -1, so the cosine is tested before it).
+__global__ void __launch_bounds__(256)
+normal_mae_kernel(const float* __restrict__ pred, const float* __restrict__ gt, size_t HW, float pred_div, float gt_div, float eps,
+                  float4* __restrict__ partials, float* __restrict__ map) {
+	__shared__ float red[3][4];
+	float sum = 0.f, valid = 0.f, invalid = 0.f;
+	for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (size_t)gridDim.x * 256) {
+		float a[3], b[3];
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			a[c] = pred[c * HW + p]; b[c] = gt[c * HW + p];
+			if (pred_div != 1.0f) a[c] = __fdiv_rn(a[c], pred_div);
+			if (gt_div != 1.0f) b[c] = __fdiv_rn(b[c], gt_div);
+		}
+		const float dot = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+		const float na = sqrtf(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), nb = sqrtf(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+		const float cs = __fdiv_rn(dot, na * nb + eps);
+		const float ang = acosf(fminf(fmaxf(cs, -1.0f), 1.0f)) * 57.29577951308232f;
+		const bool bad = na <= eps || nb <= eps || cs != cs;
+		if (bad) invalid += 1.f;
+		else { valid += 1.f; sum += ang; }
+		if (map) map[p] = bad ? __int_as_float(0x7fc00000) : ang;
+	}
+	// (the counts stay exact in float32: a block of the 1024 sees at most 2^31 / 1024 = 2^21 pixels)
+	float r4[4] = {sum, valid, invalid, 0.f};
+	wave_sum4(r4);
+	const int wave = threadIdx.x >> 6;
+	if ((threadIdx.x & 63) == 63) { red[0][wave] = r4[0]; red[1][wave] = r4[1]; red[2][wave] = r4[2]; }
+	__syncthreads();
+	if (threadIdx.x == 0)
+		partials[blockIdx.x] = make_float4((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]),
+		                                   (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]), 0.f);
+}
+
+}  // namespace gsr
+
+using namespace gsr;
+
+#define NORMAL_MAE_BLOCKS 1024
+
+static size_t image_metrics_blocks(int C, int H, int W) {
+	return (size_t)C * ((H + SSIM_T - 1) / SSIM_T) * ((W + SSIM_T - 1) / SSIM_T);
+}
+
+extern "C" size_t gsr_image_metrics_scratch_floats(int C, int H, int W) {
+	if (C <= 0 || H <= 0 || W <= 0) return 0;
+	return 4 * image_metrics_blocks(C, H, W);
+}
+
+extern "C" int gsr_image_metrics(const float* img, const float* gt, int C, int H, int W, int flags, const float* alpha, const float* gt_mask,
+                                 const float* background, double* row, float* scratch, size_t scratch_floats, uint8_t* img_u8, uint8_t* gt_u8,
+                                 void* stream_) {
+	hipStream_t stream = (hipStream_t)stream_;
+	if (C <= 0 || H <= 0 || W <= 0) { set_error("gsr_image_metrics: invalid size C = %d, H = %d, W = %d", C, H, W); return GSR_E_INVALID; }
+	if (C > 65535 || (H + SSIM_T - 1) / SSIM_T > 65535) { set_error("gsr_image_metrics: C and H / 32 are grid dimensions, at most 65535"); return GSR_E_INVALID; }
+	if (!img || !gt || !row) { set_error("gsr_image_metrics: NULL image or table row"); return GSR_E_INVALID; }
+	if (flags & ~(GSR_PRESENT_CLAMP | GSR_PRESENT_QUANT8)) { set_error("gsr_image_metrics: unknown presentation flags %d", flags); return GSR_E_INVALID; }
+	if ((img_u8 || gt_u8) && !(flags & GSR_PRESENT_QUANT8)) {
+		set_error("gsr_image_metrics: a uint8 output needs GSR_PRESENT_QUANT8 (it holds the quantised image)");
+		return GSR_E_INVALID;
+	}
+	if ((alpha || gt_mask) && !background) { set_error("gsr_image_metrics: alpha or gt_mask given without a background"); return GSR_E_INVALID; }
+	if (reinterpret_cast<uintptr_t>(row) & 7u) { set_error("gsr_image_metrics: the table row must be 8-byte aligned; got %p", (const void*)row); return GSR_E_INVALID; }
+	const size_t blocks = image_metrics_blocks(C, H, W);
+	if (!scratch || scratch_floats < 4 * blocks) {
+		set_error("gsr_image_metrics: scratch of %zu floats given, gsr_image_metrics_scratch_floats(C,H,W) = %zu needed", scratch ? scratch_floats : (size_t)0, 4 * blocks);
+		return GSR_E_INVALID;
+	}
+	GSR_REQUIRE_ALIGNED16_IN("gsr_image_metrics", scratch, "scratch");
+	static const SsimWindow win = make_window();
+	const Presentation pr = {alpha, gt_mask, background, (flags & GSR_PRESENT_CLAMP) != 0, (flags & GSR_PRESENT_QUANT8) != 0};
+	dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C);
+	image_metrics_kernel<<<grid, 256, 0, stream>>>(img, gt, H, W, win, (float)(0.01 * 0.01), (float)(0.03 * 0.03), pr, (float4*)scratch, img_u8, gt_u8);
+	metrics_reduce_kernel<<<1, 256, 0, stream>>>((const float4*)scratch, blocks, (double)C * H * W, row);
+	GSR_LAUNCH_CHECK(0, stream);
+	return 0;
+}
+
+extern "C" size_t gsr_normal_mae_scratch_floats(int H, int W) {
+	if (H <= 0 || W <= 0) return 0;
+	return 4 * std::min<size_t>(NORMAL_MAE_BLOCKS, ((size_t)H * W + 255) / 256);
+}
+
+extern "C" int gsr_normal_mae(const float* pred, const float* gt, int H, int W, float pred_divisor, float gt_divisor, float eps, double* row,
+                              float* scratch, size_t scratch_floats, float* error_map, void* stream_) {
+	hipStream_t stream = (hipStream_t)stream_;
+	if (H <= 0 || W <= 0) { set_error("gsr_normal_mae: invalid size H = %d, W = %d", H, W); return GSR_E_INVALID; }
+	if (!pred || !gt || !row) { set_error("gsr_normal_mae: NULL normals or table row"); return GSR_E_INVALID; }
+	if (!(pred_divisor > 0.f) || !(gt_divisor > 0.f) || !(eps >= 0.f)) { set_error("gsr_normal_mae: divisors must be positive and eps non-negative"); return GSR_E_INVALID; }
+	if (reinterpret_cast<uintptr_t>(row) & 7u) { set_error("gsr_normal_mae: the table row must be 8-byte aligned; got %p", (const void*)row); return GSR_E_INVALID; }
+	const size_t HW = (size_t)H * W;
+	const size_t blocks = std::min<size_t>(NORMAL_MAE_BLOCKS, (HW + 255) / 256);
+	if (!scratch || scratch_floats < 4 * blocks) {
+		set_error("gsr_normal_mae: scratch of %zu floats given, gsr_normal_mae_scratch_floats(H,W) = %zu needed", scratch ? scratch_floats : (size_t)0, 4 * blocks);
+		return GSR_E_INVALID;
+	}
+	GSR_REQUIRE_ALIGNED16_IN("gsr_normal_mae", scratch, "scratch");
+	normal_mae_kernel<<<(unsigned)blocks, 256, 0, stream>>>(pred, gt, HW, pred_divisor, gt_divisor, eps, (float4*)scratch, error_map);
+	metrics_reduce_kernel<<<1, 256, 0, stream>>>((const float4*)scratch, blocks, (double)HW, row);
+	GSR_LAUNCH_CHECK(0, stream);
+	return 0;
+}

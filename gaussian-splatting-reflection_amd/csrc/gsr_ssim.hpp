@@ -1,0 +1,138 @@
+// The pieces of the 11x11 Gaussian-window SSIM that the training loss (gsr_train.hip) and the evaluation metrics
+// (gsr_metrics.hip) share: the window, the 32x32 output tile with its 42x42 zero-padded halo in LDS, the halo loader and
+// the column window of the vertical pass.  Every function is inlined into the kernel that calls it.
+// ssim_l1_fwd_kernel keeps its own text of the two register-blocked passes (ssim_moments_hpass, ssim_load_columns<5> and
+// ssim_value below restate them for the metrics kernel): calling them from there moves its instruction stream, by a few
+// instructions out of 1546, and that kernel's timing is part of the train step's record; likewise ssim_load_tiles is not
+// written on top of ssim_stage_tiles.  tests/isa_digest.py shows the training kernels unchanged by this header.
+#pragma once
+#include <cmath>
+#include "gsr_internal.hpp"
+
+namespace gsr {
+
+#define SSIM_R 5
+#define SSIM_T 32                          // output tile: 32 x 32 pixels per workgroup, four per thread
+#define SSIM_HALO (SSIM_T + 2 * SSIM_R)   // 42
+#define SSIM_B 4                           // outputs per work item along the filtered direction: 4 + 10 loads instead of 4 x 11
+
+struct SsimWindow { float g[2 * SSIM_R + 1]; };
+
+// utils/loss_utils.py:46-48: exp(-(x - 5)^2 / (2 sigma^2)) as float32, normalised by the float32 sum
+static SsimWindow make_window() {
+	SsimWindow w;
+	float sum = 0.f;
+	for (int i = 0; i < 11; i++) {
+		w.g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
+		sum += w.g[i];
+	}
+	for (int i = 0; i < 11; i++) w.g[i] /= sum;
+	return w;
+}
+
+#ifdef __HIPCC__
+// Stage the zero-padded halo tiles of NS planes into LDS.  `fetch(in, o, t)` gives the NS values of the pixel at offset o of
+// its plane (in: inside the image; outside it must give zeros, the padding).  All of a thread's global loads are issued
+// before the first LDS store (the loop is fully unrolled into registers): with three workgroups per CU a
+// load-store-load-store sequence leaves the kernel waiting on seven dependent HBM round trips per tile.
+#define SSIM_LOADS ((SSIM_HALO * SSIM_HALO + 255) / 256)
+template <int NS, class Fetch>
+__device__ __forceinline__ void ssim_stage_tiles(Fetch fetch, int H, int W, int x0, int y0, float (*const (&dst)[NS])[SSIM_HALO + 1]) {
+	float v[NS][SSIM_LOADS];
+#pragma unroll
+	for (int j = 0; j < SSIM_LOADS; j++) {
+		const int i = threadIdx.x + 256 * j;
+		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
+		const int gx = x0 + lx - SSIM_R, gy = y0 + ly - SSIM_R;
+		const bool in = i < SSIM_HALO * SSIM_HALO && gx >= 0 && gx < W && gy >= 0 && gy < H;
+		const size_t o = in ? (size_t)gy * W + gx : 0;
+		float t[NS];
+		fetch(in, o, t);
+#pragma unroll
+		for (int p = 0; p < NS; p++) v[p][j] = t[p];
+	}
+#pragma unroll
+	for (int j = 0; j < SSIM_LOADS; j++) {
+		const int i = threadIdx.x + 256 * j;
+		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
+		if (i < SSIM_HALO * SSIM_HALO) {
+#pragma unroll
+			for (int p = 0; p < NS; p++) dst[p][ly][lx] = v[p][j];
+		}
+	}
+}
+// the planes as they are in memory
+template <int NP>
+__device__ __forceinline__ void ssim_load_tiles(const float* const (&src)[NP], int H, int W, int x0, int y0, float (*const (&dst)[NP])[SSIM_HALO + 1]) {
+	float v[NP][SSIM_LOADS];
+#pragma unroll
+	for (int j = 0; j < SSIM_LOADS; j++) {
+		const int i = threadIdx.x + 256 * j;
+		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
+		const int gx = x0 + lx - SSIM_R, gy = y0 + ly - SSIM_R;
+		const bool in = i < SSIM_HALO * SSIM_HALO && gx >= 0 && gx < W && gy >= 0 && gy < H;
+		const size_t o = in ? (size_t)gy * W + gx : 0;
+#pragma unroll
+		for (int p = 0; p < NP; p++) v[p][j] = in ? src[p][o] : 0.f;
+	}
+#pragma unroll
+	for (int j = 0; j < SSIM_LOADS; j++) {
+		const int i = threadIdx.x + 256 * j;
+		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
+		if (i < SSIM_HALO * SSIM_HALO) {
+#pragma unroll
+			for (int p = 0; p < NP; p++) dst[p][ly][lx] = v[p][j];
+		}
+	}
+}
+
+// Horizontal pass of the five moments: 42 rows x (32 / 4) strips.  A work item produces SSIM_B neighbouring outputs from one
+// sliding window of SSIM_B + 10 LDS reads, every output accumulating its eleven taps in the same order.
+__device__ __forceinline__ void ssim_moments_hpass(const float (&ta)[SSIM_HALO][SSIM_HALO + 1], const float (&tb)[SSIM_HALO][SSIM_HALO + 1],
+                                                   float (&hs)[5][SSIM_HALO][SSIM_T + 1], const SsimWindow& win) {
+	for (int i = threadIdx.x; i < SSIM_HALO * (SSIM_T / SSIM_B); i += 256) {
+		const int ly = i % SSIM_HALO, lx = (i / SSIM_HALO) * SSIM_B;   // lanes run down the rows: row pitch 43 / 33 words is odd, no bank conflicts
+		float a[SSIM_B + 10], b[SSIM_B + 10], aa[SSIM_B + 10], bb[SSIM_B + 10], ab[SSIM_B + 10];
+#pragma unroll
+		for (int k = 0; k < SSIM_B + 10; k++) {
+			a[k] = ta[ly][lx + k]; b[k] = tb[ly][lx + k];
+			aa[k] = a[k] * a[k]; bb[k] = b[k] * b[k]; ab[k] = a[k] * b[k];   // once per window element, not once per tap
+		}
+#pragma unroll
+		for (int c = 0; c < SSIM_B; c++) {
+			float s1 = 0, s2 = 0, s11 = 0, s22 = 0, s12 = 0;
+#pragma unroll
+			for (int k = 0; k < 11; k++) {
+				const float w = win.g[k];
+				s1 += w * a[c + k]; s2 += w * b[c + k]; s11 += w * aa[c + k]; s22 += w * bb[c + k]; s12 += w * ab[c + k];
+			}
+			hs[0][ly][lx + c] = s1; hs[1][ly][lx + c] = s2; hs[2][ly][lx + c] = s11; hs[3][ly][lx + c] = s22; hs[4][ly][lx + c] = s12;
+		}
+	}
+}
+// Vertical pass: thread (tx, tq) owns the four rows 4 tq .. 4 tq + 3 of column tx; its sliding window of every moment
+template <int NM>
+__device__ __forceinline__ void ssim_load_columns(const float (&hs)[NM][SSIM_HALO][SSIM_T + 1], int tx, int tq, float (&col)[NM][SSIM_B + 10]) {
+#pragma unroll
+	for (int m = 0; m < NM; m++)
+#pragma unroll
+		for (int k = 0; k < SSIM_B + 10; k++) col[m][k] = hs[m][tq * SSIM_B + k][tx];
+}
+// ... and the SSIM value of its row r (utils/loss_utils.py:75-92): A B / (Cc D)
+__device__ __forceinline__ float ssim_value(const float (&col)[5][SSIM_B + 10], int r, const SsimWindow& win, float C1, float C2) {
+	float mu1 = 0, mu2 = 0, e11 = 0, e22 = 0, e12 = 0;
+#pragma unroll
+	for (int k = 0; k < 11; k++) {
+		const float w = win.g[k];
+		mu1 += w * col[0][r + k]; mu2 += w * col[1][r + k];
+		e11 += w * col[2][r + k]; e22 += w * col[3][r + k]; e12 += w * col[4][r + k];
+	}
+	const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+	const float sigma1_sq = e11 - mu1_sq, sigma2_sq = e22 - mu2_sq, sigma12 = e12 - mu12;
+	const float A = 2.f * mu12 + C1, B = 2.f * sigma12 + C2, Cc = mu1_sq + mu2_sq + C1, D = sigma1_sq + sigma2_sq + C2;
+	const float inv = 1.0f / (Cc * D);
+	return A * B * inv;
+}
+#endif
+
+}  // namespace gsr

@@ -11,56 +11,12 @@
 //     by segment table, so the 59 floats per Gaussian + cubemap update in a single launch.
 #include <cstring>
 #include "gsr_internal.hpp"
+#include "gsr_ssim.hpp"
 #include <algorithm>
 
 namespace gsr {
 
-#define SSIM_R 5
-#define SSIM_T 32                          // output tile: 32 x 32 pixels per workgroup, four per thread
-#define SSIM_HALO (SSIM_T + 2 * SSIM_R)   // 42
-#define SSIM_B 4                           // outputs per work item along the filtered direction: 4 + 10 loads instead of 4 x 11
-
-struct SsimWindow { float g[2 * SSIM_R + 1]; };
-
-// utils/loss_utils.py:46-48: exp(-(x - 5)^2 / (2 sigma^2)) as float32, normalised by the float32 sum
-static SsimWindow make_window() {
-	SsimWindow w;
-	float sum = 0.f;
-	for (int i = 0; i < 11; i++) {
-		w.g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
-		sum += w.g[i];
-	}
-	for (int i = 0; i < 11; i++) w.g[i] /= sum;
-	return w;
-}
-
-// Stage the zero-padded halo tiles of up to three planes into LDS.  All of a thread's global loads are issued before the
-// first LDS store (the loop is fully unrolled into registers): with three workgroups per CU a load-store-load-store
-// sequence leaves the kernel waiting on seven dependent HBM round trips per tile.
-#define SSIM_LOADS ((SSIM_HALO * SSIM_HALO + 255) / 256)
-template <int NP>
-__device__ __forceinline__ void ssim_load_tiles(const float* const (&src)[NP], int H, int W, int x0, int y0, float (*const (&dst)[NP])[SSIM_HALO + 1]) {
-	float v[NP][SSIM_LOADS];
-#pragma unroll
-	for (int j = 0; j < SSIM_LOADS; j++) {
-		const int i = threadIdx.x + 256 * j;
-		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
-		const int gx = x0 + lx - SSIM_R, gy = y0 + ly - SSIM_R;
-		const bool in = i < SSIM_HALO * SSIM_HALO && gx >= 0 && gx < W && gy >= 0 && gy < H;
-		const size_t o = in ? (size_t)gy * W + gx : 0;
-#pragma unroll
-		for (int p = 0; p < NP; p++) v[p][j] = in ? src[p][o] : 0.f;
-	}
-#pragma unroll
-	for (int j = 0; j < SSIM_LOADS; j++) {
-		const int i = threadIdx.x + 256 * j;
-		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
-		if (i < SSIM_HALO * SSIM_HALO) {
-#pragma unroll
-			for (int p = 0; p < NP; p++) dst[p][ly][lx] = v[p][j];
-		}
-	}
-}
+// (window, halo staging and the register-blocked separable passes: gsr_ssim.hpp, shared with the evaluation metrics)
 
 // Forward: per-pixel SSIM (utils/loss_utils.py:75-92) and |x - y|, block-reduced into sums[0] (L1) and sums[1] (SSIM);
 // optionally the SSIM map and the three planes d ssim / d mu1, d ssim / d E[x^2], d ssim / d E[xy] for the backward.
@@ -204,10 +160,7 @@ ssim_l1_bwd_kernel(const float* __restrict__ img1, const float* __restrict__ img
 	const int gx = x0 + tx;
 	if (gx >= W) return;
 	float col[3][SSIM_B + 10];
-#pragma unroll
-	for (int m = 0; m < 3; m++)
-#pragma unroll
-		for (int k = 0; k < SSIM_B + 10; k++) col[m][k] = hs[m][tq * SSIM_B + k][tx];
+	ssim_load_columns<3>(hs, tx, tq, col);
 	const float w_l1 = weights[0], w_ssim = weights[1];
 #pragma unroll
 	for (int r = 0; r < SSIM_B; r++) {

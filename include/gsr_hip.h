@@ -408,6 +408,39 @@ int gsr_split_children(int n_children, int scale_dims, int N, const int* parent,
 size_t gsr_knn_scratch_bytes(int P);
 int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Evaluation metrics (metrics.py, eval_mae.py and the presentation steps of render.py:48-62 of the reference).  Added in ABI 102
+ * without a version change, as the two entries above.  Both run on `stream` without host synchronisation, allocate nothing, and
+ * write their results to `row`: four doubles (8-byte aligned) in device memory, one row of a caller-owned [views, 4] table, so
+ * that a test set is read back once.  Block partials are added in a fixed order in double: the row is bitwise reproducible.
+ *
+ * gsr_image_metrics: img (rendered), gt: float[C,H,W].  Both are PRESENTED first, in this order, each step selected per call:
+ *     GSR_PRESENT_CLAMP   img = clamp(img, 0, 1)                                                     (render.py:49)
+ *     alpha / gt_mask     float[H,W], either may be NULL; `background` float[C] is required with them:
+ *                         img = img * a + (1 - a) * background[c], a = clamp(alpha, 0, 1);
+ *                         gt = gt * gt_mask + (1 - gt_mask) * background[c]                          (render.py:52-56)
+ *     GSR_PRESENT_QUANT8  both images: float(uint8(clamp(t * 255 + 0.5, 0, 255))) / 255, what torchvision's save_image followed
+ *                         by to_tensor gives (metrics.py scores PNGs); bit for bit the float32 chain, no fused multiply-add.
+ *   row <- { sum (img - gt)^2, sum |img - gt|, sum of the SSIM map (11x11 window, sigma 1.5, zero padding, C1 = 0.01^2,
+ *   C2 = 0.03^2: utils/loss_utils.py:62-92), C*H*W } of the presented images.  PSNR = 10 log10(row[3] / row[0]).
+ *   scratch: float[scratch_floats], 16-byte aligned, scratch_floats >= gsr_image_metrics_scratch_floats(C,H,W) (0 for a size <= 0).
+ *   img_u8 / gt_u8: optional uint8[C,H,W], the presented images as 8-bit values; only with GSR_PRESENT_QUANT8.
+ *   GSR_E_INVALID: C, H or W <= 0, a NULL image, row or scratch, unknown flags, a uint8 output without GSR_PRESENT_QUANT8, alpha
+ *   or gt_mask without background, scratch too small or misaligned.
+ *
+ * gsr_normal_mae: utils/mae_utils.py:3-29.  pred, gt: float[3,H,W], each divided by its divisor first (1, or the 255 / 65535 of
+ *   compute_mae); cos = dot / (|p| |g| + eps) clamped to [-1, 1], angle = acos in degrees; a pixel is invalid where a norm is
+ *   <= eps or the angle is NaN.  row <- { sum of the angle over valid pixels, valid pixels, invalid pixels, H*W }.
+ *   error_map: optional float[H,W], the angle, NaN at invalid pixels.  scratch as above with gsr_normal_mae_scratch_floats(H,W). */
+#define GSR_PRESENT_CLAMP 1
+#define GSR_PRESENT_QUANT8 2
+size_t gsr_image_metrics_scratch_floats(int C, int H, int W);
+int gsr_image_metrics(const float* img, const float* gt, int C, int H, int W, int flags, const float* alpha,
+                      const float* gt_mask, const float* background, double* row, float* scratch, size_t scratch_floats,
+                      uint8_t* img_u8, uint8_t* gt_u8, void* stream);
+size_t gsr_normal_mae_scratch_floats(int H, int W);
+int gsr_normal_mae(const float* pred, const float* gt, int H, int W, float pred_divisor, float gt_divisor, float eps,
+                   double* row, float* scratch, size_t scratch_floats, float* error_map, void* stream);
+
 /* Normal-consistency term of the training loss (reference train.py:182-189): normal_error = (1 - sum_c rend_normal[c] *
  * surf_normal[c]) [* mask], loss = lambda * mean(normal_error).  rend_normal, surf_normal: [3,H,W]; mask: [H,W] (1,H,W) or NULL.
  * Forward: sum2[0] = sum over pixels of normal_error (sum2[1] = 0), scratch = gsr_normal_loss_scratch_floats() floats.
