@@ -18,6 +18,7 @@ ALLOC_FN = ctypes.CFUNCTYPE(c_void_p, c_void_p, c_int, c_size_t)
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE = 0, 1, 2
 GSR_PRESENT_CLAMP, GSR_PRESENT_QUANT8 = 1, 2     # presentation flags of gsr_image_metrics
+GSR_VIEW_HALF, GSR_VIEW_SOBEL, GSR_VIEW_COLORMAP = 1, 2, 4     # flags of gsr_present_view
 
 
 class GsrError(RuntimeError):
@@ -162,6 +163,12 @@ def _load():
         lib.gsr_normal_mae_scratch_floats.argtypes = [c_int, c_int]
         lib.gsr_normal_mae.restype = c_int
         lib.gsr_normal_mae.argtypes = [P, P, c_int, c_int, c_float, c_float, c_float, P, P, c_size_t, P, P]
+    if hasattr(lib, "gsr_present_view"):
+        # (likewise: a library built before the viewer presentation lacks these two; utils.image_utils then refuses to import)
+        lib.gsr_present_view_scratch_floats.restype = c_size_t
+        lib.gsr_present_view_scratch_floats.argtypes = [c_int, c_int, c_int, c_int]
+        lib.gsr_present_view.restype = c_int
+        lib.gsr_present_view.argtypes = [P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
     return lib
 
 
@@ -202,7 +209,8 @@ EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_b
             "gsr_mark_visible", "gsr_debug_fetch", "gsr_cubemap_forward", "gsr_cubemap_backward", "gsr_deferred_reflection_forward",
             "gsr_deferred_reflection_scratch_floats", "gsr_deferred_reflection_backward", "gsr_ssim_l1_scratch_floats", "gsr_ssim_l1_forward", "gsr_ssim_l1_backward", "gsr_normal_loss_scratch_floats", "gsr_normal_loss_forward", "gsr_normal_loss_backward", "gsr_adam_step", "gsr_adam_step_range", "gsr_densification_stats", "gsr_gather_rows", "gsr_split_children", "gsr_surface_forward", "gsr_surface_backward", "gsr_profile_enable",
             "gsr_profile_collect", "gsr_set_option", "gsr_knn_scratch_bytes", "gsr_knn_mean_dist",
-            "gsr_image_metrics_scratch_floats", "gsr_image_metrics", "gsr_normal_mae_scratch_floats", "gsr_normal_mae"]
+            "gsr_image_metrics_scratch_floats", "gsr_image_metrics", "gsr_normal_mae_scratch_floats", "gsr_normal_mae",
+            "gsr_present_view_scratch_floats", "gsr_present_view"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

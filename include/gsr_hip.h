@@ -441,6 +441,34 @@ size_t gsr_normal_mae_scratch_floats(int H, int W);
 int gsr_normal_mae(const float* pred, const float* gt, int H, int W, float pred_divisor, float gt_divisor, float eps,
                    double* row, float* scratch, size_t scratch_floats, float* error_map, void* stream);
 
+/* Viewer presentation (utils/image_utils.py:33-84 of the reference: render_net_image, colormap, gradient_map; then train.py:334, the
+ * frame as bytes).  Added in ABI 102 without a version change, as the entries above.  Runs on `stream` without host synchronisation
+ * and allocates nothing: one kernel for a mode without a colour map, two (and a 16-byte memset) for one with.
+ *
+ * gsr_present_view: src float[C,H,W], C = 1 or 3.  The steps `flags` selects, in this order:
+ *     GSR_VIEW_HALF      x = (x + 1) / 2                                    (normals: image_utils.py:61)
+ *     GSR_VIEW_SOBEL     gradient_map: per channel the two 3x3 Sobel filters / 4 of the image padded with ZEROS (after the affine
+ *                        above: the border is 0, not 0.5), sqrt(gx^2 + gy^2), then the L2 norm over the channels: one channel
+ *     GSR_VIEW_COLORMAP  colormap on a one-channel result: idx = round_half_even((x - min) / (max - min) * 255) with the global min
+ *                        and max, in float32 with IEEE divide, each operation rounded on its own; the pixel is table[idx].
+ *                        table: float[256,3] in device memory.
+ *   out_f32: float[Cout,H,W], the image as render_net_image / colormap / gradient_map return it (Cout = 3 with a colour map or
+ *     C = 3 without GSR_VIEW_SOBEL, else 1).  out_u8: uint8[H,W,3] = trunc(clamp(image, 0, 1) * 255), interleaved; a one-channel
+ *     result without a colour map is repeated to three channels.  Either may be NULL, not both.
+ *   scratch: needed with GSR_VIEW_COLORMAP only: float[scratch_floats], 16-byte aligned, scratch_floats >=
+ *     gsr_present_view_scratch_floats(C,H,W,flags) (0 without a colour map or for a size <= 0; 4, + H*W with GSR_VIEW_SOBEL: the
+ *     magnitude plane is stored by the first kernel and read by the second, so the pixel that defines the max maps to 255 exactly).
+ *   Defined where the reference is not: max == min gives index 0 everywhere (the reference divides by zero); a NaN gives byte 0 in
+ *     out_u8 (as torch does on the CPU), and under a colour map takes no part in min and max and gets index 0.
+ *   GSR_E_INVALID: C, H or W <= 0, C not 1 or 3, NULL src, both outputs NULL, unknown flags, a colour map on a three-channel result
+ *     or without a table, scratch missing, too small or misaligned. */
+#define GSR_VIEW_HALF 1
+#define GSR_VIEW_SOBEL 2
+#define GSR_VIEW_COLORMAP 4
+size_t gsr_present_view_scratch_floats(int C, int H, int W, int flags);
+int gsr_present_view(const float* src, int C, int H, int W, int flags, const float* table, float* out_f32, uint8_t* out_u8,
+                     float* scratch, size_t scratch_floats, void* stream);
+
 /* Normal-consistency term of the training loss (reference train.py:182-189): normal_error = (1 - sum_c rend_normal[c] *
  * surf_normal[c]) [* mask], loss = lambda * mean(normal_error).  rend_normal, surf_normal: [3,H,W]; mask: [H,W] (1,H,W) or NULL.
  * Forward: sum2[0] = sum over pixels of normal_error (sum2[1] = 0), scratch = gsr_normal_loss_scratch_floats() floats.
