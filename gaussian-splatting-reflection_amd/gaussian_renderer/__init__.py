@@ -31,14 +31,35 @@ class _Block:
     """A small device tensor derived from camera tensors, kept together with the tensors it was built from and their
     version counters.  Holding the sources keeps their storage alive, so a later camera can never be handed the same
     addresses and be mistaken for this one (the reference recomputes everything per call; this only saves the ~10 tiny
-    host-side ops per step)."""
+    host-side ops per step).
+
+    The value is built with torch ops on the stream current at first use, and a later hit may come from any stream: the caller
+    cannot order the two, the cache being invisible to them.  So the block carries an event recorded on the building stream right
+    behind build(), and the handles of the streams already ordered behind it; a hit from another stream makes that stream wait for
+    the event once (no host synchronisation; a hit from an ordered stream costs a current_stream() call and a set lookup)."""
 
     def __init__(self, sources, extra, value):
         self.sources, self.versions, self.extra, self.value = sources, [t._version for t in sources], extra, value
+        self.ready, self.ordered = None, set()
+        if value.is_cuda:
+            built_on = torch.cuda.current_stream(value.device)
+            self.ready = torch.cuda.Event()
+            self.ready.record(built_on)
+            self.ordered.add(built_on.cuda_stream)
 
     def matches(self, sources, extra):
         return (len(sources) == len(self.sources) and all(a is b for a, b in zip(sources, self.sources)) and
                 all(t._version == v for t, v in zip(sources, self.versions)) and extra == self.extra)
+
+    def on_current_stream(self):
+        """The value, ordered behind its construction on the stream that is current now."""
+        if self.ready is not None:
+            cur = torch.cuda.current_stream(self.value.device)
+            if cur.cuda_stream not in self.ordered:
+                cur.wait_event(self.ready)
+                self.value.record_stream(cur)      # (the allocator must not hand the block's memory out again while `cur` still reads it)
+                self.ordered.add(cur.cuda_stream)
+        return self.value
 
 
 _blocks = {}          # kind -> the most recently used _Blocks, newest last
@@ -53,7 +74,7 @@ def _cached_block(kind, sources, extra, build):
         if kept[k].matches(sources, extra):
             hit = kept.pop(k)
             kept.append(hit)
-            return hit.value
+            return hit.on_current_stream()
     value = build()
     kept.append(_Block(list(sources), extra, value))
     if len(kept) > _BLOCKS_KEPT:
