@@ -6,6 +6,7 @@ torch is used for device memory, streams and autograd plumbing only.
 """
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -221,16 +222,21 @@ def set_option(name, value):
 
 
 _side_held = {}          # device index -> [(tensor the side stream of THAT device still reads or writes, stream it was allocated / last used on)]
+_side_held_mu = threading.Lock()     # two host threads: an entry appended to a list another thread's side_join() has just popped would be dropped unjoined
 
 
 def side_hold(*tensors):
     """Keeps device tensors alive that work on the library's side stream still reads (see side_join), and remembers the stream that is
     current now — the one the caching allocator will hand their blocks back to."""
+    entries = []
     for t in tensors:
         if t is None:
             continue
         dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
-        _side_held.setdefault(dev, []).append((t, torch.cuda.current_stream(t.device).cuda_stream))
+        entries.append((dev, (t, torch.cuda.current_stream(t.device).cuda_stream)))
+    with _side_held_mu:
+        for dev, entry in entries:
+            _side_held.setdefault(dev, []).append(entry)
 
 
 def side_join(device=None):
@@ -242,7 +248,8 @@ def side_join(device=None):
         dev = torch.device("cuda", torch.cuda.current_device())
     # always ask the library (a stream-wait on an event that has completed, or was never recorded, costs nothing): a second
     # consumer stream must be ordered behind the tail too, and another device's held tensors are none of this call's business
-    held = _side_held.pop(dev.index, [])
+    with _side_held_mu:
+        held = _side_held.pop(dev.index, [])
     with torch.cuda.device(dev):
         cur = torch.cuda.current_stream(dev).cuda_stream
         check(lib.gsr_side_join(cur), "gsr_side_join")

@@ -14,6 +14,7 @@ checked against live under tests/ (tests/helpers_chain.py).
 import math
 import os
 import sys
+import threading
 
 import numpy as np
 import torch
@@ -68,17 +69,28 @@ _BLOCKS_KEPT = 64     # cameras whose constants are kept per kind: a batch of vi
                       # of idle GPU per view at C4 when only the last camera was remembered, round 2)
 
 
+_blocks_mu = threading.Lock()     # two host threads: the walk below indexes, pops and appends one list; unguarded, a pop by another thread
+                                  # between the match and the pop would hand this thread another camera's block (or an IndexError)
+
+
 def _cached_block(kind, sources, extra, build):
-    kept = _blocks.setdefault(kind, [])
-    for k in range(len(kept) - 1, -1, -1):
-        if kept[k].matches(sources, extra):
-            hit = kept.pop(k)
-            kept.append(hit)
-            return hit.on_current_stream()
-    value = build()
-    kept.append(_Block(list(sources), extra, value))
-    if len(kept) > _BLOCKS_KEPT:
-        del kept[0]
+    hit = None
+    with _blocks_mu:
+        kept = _blocks.setdefault(kind, [])
+        for k in range(len(kept) - 1, -1, -1):
+            if kept[k].matches(sources, extra):
+                hit = kept.pop(k)
+                kept.append(hit)
+                break
+    if hit is not None:
+        return hit.on_current_stream()
+    value = build()      # not under the lock: it may wait for the device.  Two threads that miss on one camera at once each keep a block of their own
+    block = _Block(list(sources), extra, value)
+    with _blocks_mu:
+        kept = _blocks.setdefault(kind, [])
+        kept.append(block)
+        if len(kept) > _BLOCKS_KEPT:
+            del kept[0]
     return value
 
 

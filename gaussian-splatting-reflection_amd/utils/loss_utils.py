@@ -64,7 +64,8 @@ class _SsimL1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_sums, _):
         global _last_sums
-        if _last_sums is not None and _last_sums[4].grad_fn is not None and getattr(_last_sums[4].grad_fn, "kept", None) is ctx.kept:
+        last = _last_sums              # (read once: another host thread may replace or clear it between a test and a use)
+        if last is not None and last[4].grad_fn is not None and getattr(last[4].grad_fn, "kept", None) is ctx.kept:
             _last_sums = None          # consumed: a later l1_loss / ssim call on the same tensors starts a fresh forward (and a fresh graph)
         if not ctx.ran:
             # first pass: autograd's own checks apply (an input modified in place since the forward raises here)
@@ -102,8 +103,9 @@ def _sums(img1, img2):
     What the key cannot see: an image buffer refilled through its raw pointer (this library's own C-ABI writes, `.data` assignments) keeps
     object and version — call clear_cache() (or use photometric_loss, one explicit call) when reusing buffers that way."""
     global _last_sums
-    if _last_sums is not None:
-        r1, v1, r2, v2, s, mode = _last_sums
+    last = _last_sums                  # (read once: another host thread may replace or clear it between the test and the unpacking)
+    if last is not None:
+        r1, v1, r2, v2, s, mode = last
         if r1() is img1 and r2() is img2 and img1._version == v1 and img2._version == v2 and mode == torch.is_grad_enabled():
             return s
     s = _SsimL1.apply(img1, img2, C1, C2, False)[0]
