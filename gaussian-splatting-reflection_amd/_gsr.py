@@ -335,20 +335,26 @@ def check_backward_keywords(grad_sink, accumulate, unused, sinkable, M, unused_n
     return unused
 
 
+def check_sink_tensor(prefix, name, t, shape, dev, aligned):
+    """The check of a caller-owned gradient tensor a backward kernel writes into: contiguous float32 of `shape` on `dev`, and with `aligned`,
+    storage that starts on a 16-byte boundary.  The ValueError's text opens with "<prefix> '<name>':"."""
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f"{prefix} '{name}': expected contiguous float32 {tuple(shape)} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    if aligned and t.data_ptr() % 16:
+        # the kernel stores dL_dsh / dL_drot rows as float4 (include/gsr_hip.h, "alignment"); the C ABI refuses too
+        raise ValueError(f"{prefix} '{name}': storage must be 16-byte aligned (got {t.data_ptr():#x}); pad the slices of a packed buffer "
+                         "to multiples of 4 floats as gsr_dist.FlatGrads does")
+
+
 def grad_allocator(grad_sink, dev, mk0):
     """mk(shape, sink_name=None, **kw) for the outputs of a backward: the caller-owned tensor `grad_sink[sink_name]` where there is one (the
     kernel then writes that gradient straight into it), checked for shape, dtype, device and alignment; otherwise mk0(shape, **kw)."""
     def mk(shape, sink_name=None, **kw):
         t = grad_sink.get(sink_name) if (grad_sink and sink_name is not None) else None
-        if t is not None:
-            if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"grad sink '{sink_name}': expected contiguous float32 {tuple(shape)} on {dev}, got {tuple(t.shape)} {t.dtype}")
-            if t.data_ptr() % 16:
-                # the kernel stores dL_dsh / dL_drot rows as float4 (include/gsr_hip.h, "alignment"); the C ABI refuses too
-                raise ValueError(f"grad sink '{sink_name}': storage must be 16-byte aligned (got {t.data_ptr():#x}); pad the slices of a packed buffer "
-                                 "to multiples of 4 floats as gsr_dist.FlatGrads does")
-            return t
-        return mk0(shape, **kw)
+        if t is None:
+            return mk0(shape, **kw)
+        check_sink_tensor("grad sink", sink_name, t, shape, dev, aligned=True)
+        return t
     return mk
 
 

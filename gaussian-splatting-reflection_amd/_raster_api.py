@@ -7,6 +7,10 @@ they take and which maps they return.  Instead of two hand-written copies, both 
 description of the variant (`Variant`): the order of the positional tensors, which of them may be omitted, how the
 arguments of the `_C` entry points are laid out, and which outputs are differentiable.
 
+`call_forward` / `call_backward` are plain functions of a Variant: everything between named tensors and the `_C` entry points (argument
+packing, sink and `unused` keywords, debug snapshot, which gradients come back as None).  `build_api` adds what is about being an autograd
+node (saving, taps, zero-filling missing upstream gradients); `gaussian_renderer._RasterizeReflect` is a second node over the same two.
+
 Reference surfaces reproduced (argument names, order, defaults, return tuples, exception texts):
   S: submodules/diff-surfel-rasterization/diff_surfel_rasterization/__init__.py:21-240
   G: submodules/diff-gaussian-rasterization/diff_gaussian_rasterization/__init__.py:20-225
@@ -53,17 +57,67 @@ class Variant:
     forward_kwargs: Tuple[Tuple[str, object], ...]     # GaussianRasterizer.forward signature after (means3D, means2D, opacities)
     module_to_apply: Dict[str, str]                    # forward() keyword -> apply() tensor name where they differ
     placeholder: Callable                              # (name, device) -> tensor standing in for an omitted optional input
-    pack_forward: Callable                             # (tensors dict, settings) -> args of _C.rasterize_gaussians
-    split_forward: Callable                            # _C return tuple -> (num_rendered, outputs, buffers, radii)
+    pack_forward: Callable                             # (tensors dict, settings) -> args of _C.rasterize_gaussians (call_forward)
+    split_forward: Callable                            # _C return tuple (without extensions) -> (num_rendered, outputs, buffers, radii)
     nondiff_outputs: Tuple[int, ...]                   # indices of `outputs` marked non-differentiable
     saved: Tuple[str, ...]                             # tensors kept for the backward
-    pack_backward: Callable                            # (saved dict, settings, grad_outputs, num_rendered, buffers, radii) -> _C args
+    pack_backward: Callable                            # (saved dict, settings, grad_outputs, num_rendered, buffers, radii) -> _C args (call_backward)
     grads_of: Callable                                 # _C backward return tuple -> dict tensor name -> gradient
-    optional_grads: Tuple[str, ...]                    # inputs whose gradient is None when they were passed as placeholders
+    optional_grads: Tuple[str, ...]                    # inputs whose gradient call_backward returns as None when they were passed as placeholders
     sinkable: Dict[str, str] = field(default_factory=dict)   # apply() tensor name -> gradient-sink key
     skippable: Dict[str, str] = field(default_factory=dict)  # apply() tensor name -> `unused` key of the _C backward: not computed when the input was a placeholder
     taps: Dict[str, Tuple[int, int, int, str]] = field(default_factory=dict)   # tap name -> (output index, first plane, last plane + 1, _C backward keyword)
-    snapshot_on_debug: bool = False
+    snapshot_on_debug: bool = False                    # call_forward / call_backward write snapshot_fw.dump / snapshot_bw.dump when settings.debug and _C raises
+
+
+def named_tensors(v: Variant, args):
+    """The leading arguments of a Function.apply that takes the variant's positional tensors first (settings excluded), by name."""
+    return dict(zip(v.tensors, args))
+
+
+def call_forward(v: Variant, t, settings, **c_kwargs):
+    """`_C.rasterize_gaussians` on the tensors `t` (by name); `c_kwargs`: its keyword-only extensions.  Returns its raw tuple.  With
+    snapshot_on_debug and settings.debug, a call that raises leaves host copies of its arguments in snapshot_fw.dump (the reference's
+    debug contract)."""
+    c_args = v.pack_forward(t, settings)
+    host_copy = cpu_deep_copy_tuple(c_args) if v.snapshot_on_debug and settings.debug else None     # taken before anything can corrupt the inputs
+    try:
+        return v.c_module.rasterize_gaussians(*c_args, **c_kwargs)
+    except Exception:
+        if host_copy is not None:
+            torch.save(host_copy, "snapshot_fw.dump")
+            print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+        raise
+
+
+def call_backward(v: Variant, saved, settings, grad_outputs, num_rendered, buffers, radii, sink, **c_kwargs):
+    """`_C.rasterize_gaussians_backward` for one forward.  saved: the tensors of `v.saved` by name; grad_outputs: one per forward output,
+    materialised where the output is differentiable; sink: the forward's GradSink or None; c_kwargs: further keywords of the _C entry (tap
+    gradients).  Returns the gradients in `v.tensors` order: None where the kernel wrote the gradient into the sink and where the input
+    was an empty placeholder.  Snapshot as call_forward, into snapshot_bw.dump."""
+    c_args = v.pack_backward(saved, settings, grad_outputs, num_rendered, buffers, radii)
+    sunk = sink.tensors if sink is not None else {}
+    if sunk:
+        c_kwargs.update(grad_sink=sunk, accumulate=sink.accumulate)
+    omitted = lambda name: saved.get(name) is None or saved[name].numel() == 0      # the input was passed as an empty placeholder
+    # their gradients are dropped below anyway: tell the kernel not to write them
+    unused = tuple(key for name, key in v.skippable.items() if omitted(name))
+    if unused:
+        c_kwargs["unused"] = unused
+    host_copy = cpu_deep_copy_tuple(c_args) if v.snapshot_on_debug and settings.debug else None
+    try:
+        g = v.grads_of(v.c_module.rasterize_gaussians_backward(*c_args, **c_kwargs))
+    except Exception:
+        if host_copy is not None:
+            torch.save(host_copy, "snapshot_bw.dump")
+            print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        raise
+    out = []
+    for name in v.tensors:
+        in_sink = name in v.sinkable and v.sinkable[name] in sunk      # already written (or added) into the caller's tensor by the backward kernel
+        dropped = name in v.optional_grads and omitted(name)           # autograd wants None for inputs that were passed as empty placeholders
+        out.append(None if in_sink or dropped else g.get(name))
+    return out
 
 
 def build_api(v: Variant):
@@ -74,25 +128,14 @@ def build_api(v: Variant):
         args = list(args)
         sink = args.pop() if len(args) == n_args + 1 else None      # trailing GradSink (extension) or absent
         settings = args.pop(v.settings_pos)
-        return dict(zip(v.tensors, args)), settings, sink
+        return named_tensors(v, args), settings, sink
 
     class _RasterizeGaussians(torch.autograd.Function):
         @staticmethod
         def forward(ctx, *args):
             t, settings, sink = split_args(args)
             ctx.grad_sink, ctx.n_inputs = sink, len(args)
-            c_args = v.pack_forward(t, settings)
-            if v.snapshot_on_debug and settings.debug:
-                host_copy = cpu_deep_copy_tuple(c_args)          # taken before anything can corrupt the inputs
-                try:
-                    ret = v.c_module.rasterize_gaussians(*c_args)
-                except Exception as ex:
-                    torch.save(host_copy, "snapshot_fw.dump")
-                    print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                    raise ex
-            else:
-                ret = v.c_module.rasterize_gaussians(*c_args)
-            num_rendered, outputs, buffers, radii = v.split_forward(ret)
+            num_rendered, outputs, buffers, radii = v.split_forward(call_forward(v, t, settings))
             ctx.raster_settings, ctx.num_rendered = settings, num_rendered
             ctx.save_for_backward(*[t[k] for k in v.saved], radii, *buffers)
             ctx.mark_non_differentiable(*[outputs[i] for i in v.nondiff_outputs])
@@ -110,7 +153,6 @@ def build_api(v: Variant):
 
         @staticmethod
         def backward(ctx, *grad_outputs):
-            settings = ctx.raster_settings
             kept = ctx.saved_tensors
             saved = dict(zip(v.saved, kept[:len(v.saved)]))
             radii, buffers = kept[len(v.saved)], kept[len(v.saved) + 1:]
@@ -118,33 +160,7 @@ def build_api(v: Variant):
             grad_outputs = grad_outputs[:len(ctx.out_meta)]
             grad_outputs = [torch.zeros(m[0], dtype=m[1], device=m[2]) if (g is None and i not in v.nondiff_outputs) else g
                             for i, (g, m) in enumerate(zip(grad_outputs, ctx.out_meta))]
-            c_args = v.pack_backward(saved, settings, grad_outputs, ctx.num_rendered, buffers, radii)
-            sink_kw = {"grad_sink": ctx.grad_sink.tensors, "accumulate": ctx.grad_sink.accumulate} if (ctx.grad_sink and ctx.grad_sink.tensors) else {}
-            sink_kw.update(tap_grads)
-            # gradients of inputs that were passed as empty placeholders are dropped below anyway: tell the kernel not to write them
-            unused = tuple(key for name, key in v.skippable.items() if saved.get(name) is None or saved[name].numel() == 0)
-            if unused:
-                sink_kw["unused"] = unused
-            if v.snapshot_on_debug and settings.debug:
-                host_copy = cpu_deep_copy_tuple(c_args)
-                try:
-                    ret = v.c_module.rasterize_gaussians_backward(*c_args, **sink_kw)
-                except Exception as ex:
-                    torch.save(host_copy, "snapshot_bw.dump")
-                    print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                    raise ex
-            else:
-                ret = v.c_module.rasterize_gaussians_backward(*c_args, **sink_kw)
-            g = v.grads_of(ret)
-            sink = ctx.grad_sink.tensors if ctx.grad_sink is not None else {}
-            out = []
-            for name in v.tensors:
-                grad = g.get(name)
-                if name in v.sinkable and v.sinkable[name] in sink:
-                    grad = None            # already written (or added) into the caller's sink tensor by the backward kernel
-                elif name in v.optional_grads and (saved.get(name) is None or saved[name].numel() == 0):
-                    grad = None            # autograd wants None for inputs that were passed as empty placeholders
-                out.append(grad)
+            out = call_backward(v, saved, ctx.raster_settings, grad_outputs, ctx.num_rendered, buffers, radii, ctx.grad_sink, **tap_grads)
             out.insert(v.settings_pos, None)
             out += [None] * (ctx.n_inputs - len(out))     # the trailing GradSink argument, when present
             return tuple(out)

@@ -22,7 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import _gsr  # noqa: E402
 from _gsr import check, lib, ptr, stream_ptr  # noqa: E402
-from _raster_api import GradSink  # noqa: E402
+from _raster_api import GradSink, call_backward, call_forward, named_tensors  # noqa: E402
 import diff_surfel_rasterization as _dsr  # noqa: E402
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer  # noqa: E402
 
@@ -188,9 +188,9 @@ def _reflection_backward(saved, grads, sink, sort_keys, scratch=None):
     need_both = "=True needs both 'cubemap' and 'fail' tensors (accumulate / async_tail need both 'cubemap' and 'fail' tensors)"
     if accumulate and not (sunk_cm and sunk_fail):
         raise ValueError("reflection grad sink: accumulate" + need_both)
-    for t, like, name in ((g_cm, cm, "cubemap"), (g_fail, fv, "fail")):
-        if t is not None and (tuple(t.shape) != tuple(like.shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != like.device):
-            raise ValueError(f"reflection grad sink '{name}': expected contiguous float32 {tuple(like.shape)} on {like.device}")
+    for name, t, like in (("cubemap", g_cm, cm), ("fail", g_fail, fv)):
+        if t is not None:      # (the unpack kernel writes these planes element by element: no alignment to ask for)
+            _gsr.check_sink_tensor("reflection grad sink", name, t, like.shape, like.device, aligned=False)
     if async_tail and not (sunk_cm and sunk_fail):
         raise ValueError("reflection grad sink: async_tail" + need_both)
     g_cm = torch.empty_like(cm) if g_cm is None else g_cm
@@ -248,43 +248,43 @@ class _RasterizeReflect(torch.autograd.Function):
     the pixel gradients reach the tile backward as pointers).  The reflection backward is NOT folded into the tile backward: its
     texel-gradient tail (sort by texel, run combine) needs every pixel's record early so that it hides beside that kernel — as a prologue
     of the tile backward the records are complete only when it ends and the tail is exposed (built and measured in round 4).
+    The rasterizer's side of both directions is _raster_api.call_forward / call_backward, which diff_surfel_rasterization's own node runs too
+    (argument packing, sink and `unused` keywords, debug snapshot, None for sunk and placeholder gradients).
     apply(*rasterizer tensors in diff_surfel_rasterization's order, cubemap, fail_value, cam_block, settings, raster_sink, refl_sink)
     -> (final, refl_color, normal_world, base_color, radii, allmap, refl_strength_map, gaussian_weights)."""
-    V = _dsr._VARIANT
     probe = None        # tests only: a dict that receives clones of the pixel gradients the reflection backward hands the rasterizer backward
 
     @staticmethod
     def forward(ctx, *args):
-        v = _RasterizeReflect.V
-        n = len(v.tensors)
-        t = dict(zip(v.tensors, args[:n]))
-        cubemap, fail_value, cam, settings, raster_sink, refl_sink = args[n:]
+        v = GaussianRasterizer.variant
+        t = named_tensors(v, args)
+        cubemap, fail_value, cam, settings, raster_sink, refl_sink = args[len(v.tensors):]
         cm, fv = cubemap.float().contiguous(), fail_value.float().contiguous()
         if cm.dim() != 4 or cm.shape[1] != 3:
             raise RuntimeError("rasterize_reflect: the cubemap must be (6, 3, L, L)")
-        want_keys = REFLECTION_BACKWARD_BINNED and REFLECTION_FORWARD_KEYS and any(ctx.needs_input_grad[:n + 2])
+        want_keys = REFLECTION_BACKWARD_BINNED and REFLECTION_FORWARD_KEYS and any(ctx.needs_input_grad[:len(v.tensors) + 2])
         # With an asynchronous tail the keys are sorted HERE, on the side stream behind the forward's tile kernel: the sort then runs beside
         # whatever follows the forward (the loss, the start of the backward) instead of racing the tile backward for CUs
         early = want_keys and refl_sink is not None and refl_sink.async_tail and bool(refl_sink.tensors)
-        ret = _dsr._C.rasterize_gaussians(*v.pack_forward(t, settings), refl=dict(cam=cam, cubemap=cm, fail_value=fv, keys=want_keys, early_sort=early))
-        (num_rendered, color, others, radii, geom, binning, img, refl_map, weights, final, refl_color, normal_world, rgba, keys, scratch) = ret
+        ret = call_forward(v, t, settings, refl=dict(cam=cam, cubemap=cm, fail_value=fv, keys=want_keys, early_sort=early))
+        num_rendered, (color, radii, others, refl_map, weights), buffers, _ = v.split_forward(ret[:9])
+        final, refl_color, normal_world, rgba, keys, scratch = ret[9:]       # what `refl=` adds (diff_surfel_rasterization._C.rasterize_gaussians)
         if scratch is not None:
             _gsr.side_hold(scratch, keys)       # the side stream reads / writes them from now on (until side_join)
-        ctx.raster_settings, ctx.num_rendered, ctx.n_tensors = settings, num_rendered, n
+        ctx.raster_settings, ctx.num_rendered = settings, num_rendered
         ctx.raster_sink, ctx.refl_sink, ctx.sort_keys, ctx.scratch = raster_sink, refl_sink, keys, scratch
-        ctx.save_for_backward(*[t[k] for k in v.saved], radii, geom, binning, img, color, others, refl_map, cm, fv, cam, rgba)
+        ctx.save_for_backward(*[t[k] for k in v.saved], radii, *buffers, color, others, refl_map, cm, fv, cam, rgba)
         ctx.mark_non_differentiable(radii, weights)
         ctx.set_materialize_grads(False)
         return final, refl_color, normal_world, color, radii, others, refl_map, weights
 
     @staticmethod
     def backward(ctx, g_final, g_refl_color, g_normal_world, g_color, _g_radii, g_others, g_refl_map, _g_weights):
-        v = _RasterizeReflect.V
+        v = GaussianRasterizer.variant
         kept = ctx.saved_tensors
         ns = len(v.saved)
         saved = dict(zip(v.saved, kept[:ns]))
         radii, geom, binning, img, color, others, refl_map, cm, fv, cam, rgba = kept[ns:]
-        settings = ctx.raster_settings
         cont = lambda g: None if g is None else g.float().contiguous()
         # ---- 1. reflection backward (pixel kernel on this stream, texel-gradient tail beside what follows); others[2:5] is contiguous
         g_nv, g_base, g_s, g_cm, g_fail = _reflection_backward((others[2:5], color, refl_map, cm, fv, cam, rgba), (g_final, g_refl_color, g_normal_world),
@@ -300,24 +300,9 @@ class _RasterizeReflect(torch.autograd.Function):
             g_others = torch.zeros_like(others)
         if _RasterizeReflect.probe is not None:
             _RasterizeReflect.probe.update(g_normal_view=g_nv.clone(), g_base=g_base.clone(), g_strength=g_s.clone())
-        c_args = v.pack_backward(saved, settings, [g_base, None, g_others, g_s, None], ctx.num_rendered, (geom, binning, img), radii)
-        kw = {"extra_normal_grad": g_nv}
-        sink = ctx.raster_sink.tensors if (ctx.raster_sink is not None and ctx.raster_sink.tensors) else {}
-        if sink:
-            kw.update(grad_sink=sink, accumulate=ctx.raster_sink.accumulate)
-        unused = tuple(key for name, key in v.skippable.items() if saved.get(name) is None or saved[name].numel() == 0)
-        if unused:
-            kw["unused"] = unused
-        g = v.grads_of(_dsr._C.rasterize_gaussians_backward(*c_args, **kw))
-        out = []
-        for name in v.tensors:
-            grad = g.get(name)
-            if name in v.sinkable and v.sinkable[name] in sink:
-                grad = None            # already written (or added) into the caller's sink tensor by the backward kernel
-            elif name in v.optional_grads and (saved.get(name) is None or saved[name].numel() == 0):
-                grad = None
-            out.append(grad)
-        return tuple(out) + (g_cm, g_fail, None, None, None, None)
+        grads = call_backward(v, saved, ctx.raster_settings, [g_base, None, g_others, g_s, None], ctx.num_rendered, (geom, binning, img), radii,
+                              ctx.raster_sink, extra_normal_grad=g_nv)
+        return tuple(grads) + (g_cm, g_fail, None, None, None, None)
 
 
 def rasterize_reflect(rasterizer, env_map, world_view_transform, HWK, R, T, means3D, means2D, opacities, shs=None, colors_precomp=None,
@@ -334,7 +319,7 @@ def rasterize_reflect(rasterizer, env_map, world_view_transform, HWK, R, T, mean
                             rotations=rotations, cov3D_precomp=cov3D_precomp, env_scope_mask=env_scope_mask)
     cam = _cam_block(world_view_transform, HWK, R, T)
     rsink = GradSink(refl_grad_sink, accumulate, async_tail) if refl_grad_sink else None
-    return _RasterizeReflect.apply(*[t[name] for name in _dsr._VARIANT.tensors], env_map.params['Cubemap_texture'], env_map.params['Cubemap_failv'], cam,
+    return _RasterizeReflect.apply(*[t[name] for name in rasterizer.variant.tensors], env_map.params['Cubemap_texture'], env_map.params['Cubemap_failv'], cam,
                                    rasterizer.raster_settings, rasterizer._grad_sink, rsink)
 
 

@@ -168,3 +168,178 @@ def test_surfel_backward_takes_an_empty_scene_with_sh_input(hip_lib_built):
         _C.rasterize_gaussians_backward(*args(torch.empty(0, 16, 3)), unused=("colors",), grad_sink={"shs": torch.empty(0, 16, 3)})
     with pytest.raises(ValueError, match="'colors' needs shs as the colour input"):
         _C.rasterize_gaussians_backward(*args(z), unused=("colors",))
+
+
+# ------------------------------------------------------------------ _raster_api.call_forward / call_backward over a fake _C module
+class _FakeC:
+    """Stands in for a package's `_C`: CPU tensors in, tensors of the right arity out, every call recorded."""
+    NAMES = ("means3D", "means2D", "sh", "colors_precomp", "opacities", "scales", "cov3Ds_precomp")
+
+    def __init__(self, P=3, fail=None):
+        self.calls, self.fail = [], fail
+        shapes = dict(means3D=(P, 3), means2D=(P, 3), sh=(P, 1, 3), colors_precomp=(P, 3), opacities=(P, 1), scales=(P, 2), cov3Ds_precomp=(P, 9))
+        self.grads = {n: torch.full(shapes[n], float(i + 1)) for i, n in enumerate(self.NAMES)}
+        self.P = P
+
+    def rasterize_gaussians(self, *args, **kw):
+        self.calls.append(("fw", args, kw))
+        if self.fail == "fw":
+            raise RuntimeError("fake forward failed")
+        z = torch.zeros(4, dtype=torch.uint8)
+        return 7, torch.ones(3, 2, 2), torch.ones(self.P, dtype=torch.int32), z, z.clone(), z.clone()
+
+    def rasterize_gaussians_backward(self, *args, **kw):
+        self.calls.append(("bw", args, kw))
+        if self.fail == "bw":
+            raise RuntimeError("fake backward failed")
+        return tuple(self.grads[n] for n in self.NAMES)
+
+
+def _fake_variant(c, snapshot_on_debug=True):
+    from _raster_api import Variant
+    names = _FakeC.NAMES
+
+    def split_forward(ret):
+        n, color, radii, geom, binning, img = ret
+        return n, (color, radii), (geom, binning, img), radii
+    return Variant(
+        c_module=c, extra_settings=(), tensors=names, settings_pos=4, forward_kwargs=(), module_to_apply={},
+        placeholder=lambda name, device: torch.empty(0), pack_forward=lambda t, s: tuple(t[n] for n in names) + (s.debug,),
+        split_forward=split_forward, nondiff_outputs=(1,), saved=("means3D", "sh", "colors_precomp", "scales", "cov3Ds_precomp"),
+        pack_backward=lambda saved, s, grads, num_rendered, buffers, radii: (saved["means3D"], grads[0], num_rendered, radii) + tuple(buffers),
+        grads_of=lambda ret: dict(zip(names, ret)), optional_grads=("sh", "colors_precomp", "scales", "cov3Ds_precomp"),
+        sinkable={"means3D": "means3D", "sh": "shs", "opacities": "opacities"},
+        skippable={"colors_precomp": "colors", "cov3Ds_precomp": "cov3D"}, snapshot_on_debug=snapshot_on_debug)
+
+
+def _fake_inputs(c, omitted):
+    """The fake variant's tensors by name (P = 3), an empty placeholder for each name in `omitted`; all require grad."""
+    return {n: (torch.empty(0) if n in omitted else torch.rand(c.grads[n].shape)).requires_grad_(True) for n in _FakeC.NAMES}
+
+
+# (inputs passed as empty placeholders, sink keys, accumulate) -> (the `unused` keyword or None, tensor names whose gradient is None)
+_PLUMBING_CASES = [
+    (("colors_precomp", "scales"), None, False, ("colors",), {"colors_precomp", "scales"}),
+    (("sh", "scales"), None, False, None, {"sh", "scales"}),
+    (("colors_precomp", "cov3Ds_precomp"), ("means3D", "shs"), True, ("colors", "cov3D"), {"colors_precomp", "cov3Ds_precomp", "means3D", "sh"}),
+    (("sh", "cov3Ds_precomp"), (), False, ("cov3D",), {"sh", "cov3Ds_precomp"}),          # a sink without tensors (taps only)
+]
+
+
+def _check_backward_call(c, sink_keys, accumulate, unused, sink_tensors):
+    kind, _, kw = c.calls[-1]
+    assert kind == "bw"
+    assert kw.get("unused") == unused and ("unused" in kw) == (unused is not None)
+    if sink_keys:
+        assert kw["grad_sink"] == sink_tensors and kw["accumulate"] is accumulate
+    else:
+        assert "grad_sink" not in kw and "accumulate" not in kw
+
+
+@pytest.mark.parametrize("omitted,sink_keys,accumulate,unused,none_grads", _PLUMBING_CASES)
+def test_call_backward_keywords_and_gradient_filter(omitted, sink_keys, accumulate, unused, none_grads):
+    from _raster_api import GradSink, build_api, call_backward
+    c = _FakeC()
+    v = _fake_variant(c)
+    Settings, _, rasterize_gaussians, _ = build_api(v)
+    settings = _settings(Settings)
+    sink_tensors = {k: torch.zeros(1) for k in sink_keys or ()}
+    sink = None if sink_keys is None else GradSink(sink_tensors, accumulate)
+    # through the autograd node of build_api
+    t = _fake_inputs(c, omitted)
+    args = [t[n] for n in v.tensors]
+    args.insert(v.settings_pos, settings)
+    color, radii = rasterize_gaussians(*args, grad_sink=sink)
+    assert c.calls[-1][0] == "fw" and c.calls[-1][2] == {} and not radii.requires_grad
+    color.sum().backward()
+    _check_backward_call(c, sink_keys, accumulate, unused, sink_tensors)
+    for n in v.tensors:
+        assert (t[n].grad is None) if n in none_grads else torch.equal(t[n].grad, c.grads[n]), n
+    # the function alone
+    saved = {n: t[n].detach() for n in v.saved}
+    z = torch.zeros(4, dtype=torch.uint8)
+    out = call_backward(v, saved, settings, [torch.ones(3, 2, 2), None], 7, (z, z, z), radii, sink, extra_normal_grad="tap")
+    _check_backward_call(c, sink_keys, accumulate, unused, sink_tensors)
+    assert c.calls[-1][2]["extra_normal_grad"] == "tap" and c.calls[-1][1][2] == 7
+    assert isinstance(out, list) and len(out) == len(v.tensors)
+    for n, g in zip(v.tensors, out):
+        assert (g is None) if n in none_grads else (g is c.grads[n]), n
+
+
+@pytest.mark.parametrize("debug,snapshot_on_debug", [(True, True), (False, True), (True, False)])
+@pytest.mark.parametrize("fail", ["fw", "bw"])
+def test_debug_snapshot_is_written_by_the_shared_calls(tmp_path, monkeypatch, fail, debug, snapshot_on_debug):
+    """settings.debug with Variant.snapshot_on_debug: a _C call that raises leaves host copies of its arguments in snapshot_fw.dump /
+    snapshot_bw.dump in the working directory and the exception propagates — through the autograd node and through the functions alone."""
+    from _raster_api import build_api, call_backward, call_forward
+    monkeypatch.chdir(tmp_path)
+    c = _FakeC(fail=fail)
+    v = _fake_variant(c, snapshot_on_debug)
+    Settings, _, rasterize_gaussians, _ = build_api(v)
+    settings = _settings(Settings)._replace(debug=debug)
+    t = _fake_inputs(c, ("colors_precomp", "cov3Ds_precomp"))
+    args = [t[n] for n in v.tensors]
+    args.insert(v.settings_pos, settings)
+    dump = tmp_path / ("snapshot_%s.dump" % fail)
+    z = torch.zeros(4, dtype=torch.uint8)
+    direct = ((lambda: call_forward(v, t, settings)) if fail == "fw" else
+              (lambda: call_backward(v, {n: t[n].detach() for n in v.saved}, settings, [torch.ones(3, 2, 2), None], 7, (z, z, z), z, None)))
+    through_node = (lambda: rasterize_gaussians(*args)) if fail == "fw" else (lambda: rasterize_gaussians(*args)[0].sum().backward())
+    for run in (through_node, direct):
+        with pytest.raises(RuntimeError, match="fake (forward|backward) failed"):
+            run()
+        assert dump.exists() == (debug and snapshot_on_debug)
+        assert sorted(p.name for p in tmp_path.iterdir()) == ([dump.name] if debug and snapshot_on_debug else [])
+        if dump.exists():
+            kept = torch.load(dump)
+            assert len(kept) == len(c.calls[-1][1]) and torch.equal(kept[0], t["means3D"].detach())
+            dump.unlink()
+
+
+def test_sink_tensor_check_is_one_helper(hip_lib_built):
+    """_gsr.check_sink_tensor: shape, float32, contiguous, device, and the 16-byte alignment as a switch; every refusal is a ValueError that
+    names the sink.  grad_allocator asks for alignment, the reflection's sinks do not."""
+    import _gsr
+    cpu = torch.device("cpu")
+    good = torch.zeros(3, 4)
+    misaligned = torch.zeros(13)[1:].view(3, 4)
+    assert misaligned.is_contiguous() and misaligned.data_ptr() % 16 == 4
+    _gsr.check_sink_tensor("grad sink", "rotations", good, (3, 4), cpu, aligned=True)
+    bad = {"shape": torch.zeros(4, 3), "dtype": torch.zeros(3, 4, dtype=torch.float64), "view": torch.zeros(4, 3).T,
+           "device": torch.zeros(3, 4, device="meta")}
+    assert not bad["view"].is_contiguous() and bad["view"].shape == (3, 4)
+    for aligned in (True, False):
+        for t in bad.values():
+            with pytest.raises(ValueError, match=r"^reflection grad sink 'rotations': expected contiguous float32 \(3, 4\) on cpu"):
+                _gsr.check_sink_tensor("reflection grad sink", "rotations", t, (3, 4), cpu, aligned=aligned)
+    with pytest.raises(ValueError, match=r"^grad sink 'rotations': storage must be 16-byte aligned"):
+        _gsr.check_sink_tensor("grad sink", "rotations", misaligned, (3, 4), cpu, aligned=True)
+    _gsr.check_sink_tensor("grad sink", "rotations", misaligned, (3, 4), cpu, aligned=False)
+    # grad_allocator: the sink tensor itself where there is one, checked with alignment on; mk0 otherwise
+    mk = _gsr.grad_allocator({"rotations": good, "shs": misaligned}, cpu, torch.empty)
+    assert mk((3, 4), "rotations") is good and mk((3, 4), "scales").shape == (3, 4) and mk((2,)).shape == (2,)
+    with pytest.raises(ValueError, match="^grad sink 'shs': storage must be 16-byte aligned"):
+        mk((3, 4), "shs")
+    with pytest.raises(ValueError, match="^grad sink 'rotations': expected contiguous float32"):
+        mk((4, 4), "rotations")
+
+
+def test_reflection_sink_checks_keep_their_order(hip_lib_built):
+    """_reflection_backward refuses a bad sink before any library call (CPU tensors get that far): the accumulate check, then the tensor
+    checks without an alignment requirement, then the async_tail check."""
+    import gaussian_renderer as GR
+    from _raster_api import GradSink
+    img = torch.zeros(3, 2, 2)
+    cm, fv = torch.zeros(6, 3, 2, 2), torch.zeros(3)
+    saved = (img, img, torch.zeros(1, 2, 2), cm, fv, torch.zeros(33), torch.zeros(96))
+    run = lambda tensors, **kw: GR._reflection_backward(saved, (img, None, None), GradSink(tensors, **kw), None)
+    with pytest.raises(ValueError, match="^reflection grad sink: accumulate=True needs both"):
+        run({"cubemap": torch.zeros(5)}, accumulate=True, async_tail=True)
+    with pytest.raises(ValueError, match="^reflection grad sink 'cubemap': expected contiguous float32"):
+        run({"cubemap": torch.zeros(5)}, async_tail=True)
+    with pytest.raises(ValueError, match="^reflection grad sink 'fail': expected contiguous float32"):
+        run({"cubemap": torch.zeros_like(cm), "fail": torch.zeros(3, dtype=torch.float64)}, accumulate=True, async_tail=True)
+    misaligned_cm = torch.zeros(cm.numel() + 1)[1:].view(cm.shape)
+    assert misaligned_cm.data_ptr() % 16 == 4
+    with pytest.raises(ValueError, match="^reflection grad sink: async_tail=True needs both"):
+        run({"cubemap": misaligned_cm}, async_tail=True)          # the misaligned plane passed its check
