@@ -61,6 +61,18 @@ static int g_opt_cull = 1;
 int option_cull() { return g_opt_cull; }
 static int g_opt_dev = 0;
 int option_dev() { return g_opt_dev; }
+unsigned long long* dev_pair_counter() {
+	static std::mutex mu;
+	static unsigned long long* words[64];
+	int dev = 0;
+	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+	std::lock_guard<std::mutex> lk(mu);
+	if (!words[dev]) {
+		if (hipMalloc((void**)&words[dev], sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); words[dev] = nullptr; return nullptr; }
+		if (hipMemset(words[dev], 0, sizeof(unsigned long long)) != hipSuccess) return nullptr;
+	}
+	return words[dev];
+}
 static int g_opt_emit_items = 0;   // 0: by the Gaussian count (EMIT_ITEMS2_FROM); 1 / 2: forced (tests)
 static int g_opt_mailbox = 1;
 static int option_mailbox() { return g_opt_mailbox; }
@@ -815,6 +827,11 @@ extern "C" int gsr_debug_fetch(int variant, const char* name, int P, int R, int 
 		return 0;
 	};
 	std::string n(name);
+	if (n == "pairs") {   // the development counter of evaluated pairs (one 64-bit word; the buffers are not read)
+		const unsigned long long* word = dev_pair_counter();
+		if (!word) { set_error("gsr_debug_fetch: no pair counter"); return GSR_E_HIP; }
+		return d2d(word, sizeof(unsigned long long));
+	}
 	if (n == "depths") return d2d(g.depths, (size_t)P * 4);
 	if (n == "means2D") return gather(0, 2);     // the first two floats of the render record of both variants (not kept as an array of its own since round 4)
 
@@ -850,6 +867,7 @@ extern "C" int gsr_debug_fetch(int variant, const char* name, int P, int R, int 
 	if (n == "transMat" && variant == 0) return pick({2, 4, 6, 3, 5, 7, 8, 9, 10});
 	if (n == "cov3D" && variant == 1) { set_error("gsr_debug_fetch: the 3D covariance is not kept by the forward (round 4: the backward recomputes it)"); return GSR_E_INVALID; }
 	if (n == "point_list") return d2d(b.point_list, (size_t)R * 4);
+	if (n == "blend_mask") return d2d(b.blend_mask, 16 * b.mask_stride * sizeof(unsigned long long));   // (a training forward's: see BinningState for the layouts)
 	if (n == "keys") {   // reference-format sorted keys, rebuilt (the product path sorts tile ids only)
 		if (R == 0) return 0;
 		rebuild_keys_kernel<<<(R + 255) / 256, 256, 0, stream>>>(R, b.tile_keys, b.point_list, g.depths, (uint64_t*)dst);

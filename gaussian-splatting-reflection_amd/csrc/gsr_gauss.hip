@@ -218,7 +218,7 @@ __device__ __forceinline__ lmask gauss_pair(float4 r0, float conz, float opac, f
 // gsr_surfel.hip for the design: one wave = one 8x8 pixel block, ballot-compacted private work list from
 // conservative cull bounds, per-Gaussian record through the scalar memory path, no workgroup barriers).
 #define G_SUB 16      // hits between two flushes of the backward's gradient slab (power of two)
-template <bool INVDEPTH>
+template <bool INVDEPTH, bool COUNT = false>
 // The vote tests the cull ellipse against the box of the wave's pixel CENTRES, and alpha >= 1/255 is exactly q <= q_max for
 // this variant (the screen-space blur is part of the conic), so the 5 % + 0.1 margin on q_max already makes the record
 // conservative; CULL_PAD only covers the float rounding of the edge minimisation.
@@ -227,7 +227,7 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
                              const float4* __restrict__ rec, const float4* __restrict__ bbox, int cull, const float* __restrict__ bg,
                              float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
                              float* __restrict__ out_normal, float* __restrict__ out_refl, float* __restrict__ out_invdepth,
-                             unsigned long long* __restrict__ blend_mask, size_t mask_stride) {
+                             unsigned long long* __restrict__ blend_mask, size_t mask_stride, PairCount<COUNT> pairs) {
 	const uint32_t slot = xcd_slot(blockIdx.x);   // dispatch slot -> (tile, quadrant), longest lists first
 	if (slot >= (uint32_t)ntiles * 4u) return;
 	const TileBlock blk = tile_block(tile_order, slot, tiles_x);
@@ -239,12 +239,14 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 	const float pixx = (float)px, pixy = (float)py;
 	const uint2 range = ranges[tile];
 	const int count = (int)(range.y - range.x);
-	const float qx0 = (float)bx0, qy0 = (float)by0, qx1 = qx0 + 7.0f, qy1 = qy0 + 7.0f;
+	const float qx0 = (float)bx0, qy0 = (float)by0;
 
 	__shared__ uint32_t s_hid[WBATCH];
 	__shared__ uint32_t s_hj[WBATCH];
 
 	lmask done = ~LMASK(px < W) | ~LMASK(py < H);   // lanes outside the image never blend
+	LiveBox<false> box(qx0, qy0);                   // what the vote tests against: the block's pixels that are still alive
+	uint32_t npairs = 0;                            // (COUNT) pairs this wave evaluated
 	float T = 1.0f;
 	uint32_t last_contributor = 0;
 	float C0 = 0, C1 = 0, C2 = 0, N0 = 0, N1 = 0, N2 = 0, RS = 0, ID = 0;
@@ -255,10 +257,11 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 		const int nb = min(WBATCH, count - base);
 		bool hit = lane < nb;
 		uint32_t id = 0;
+		if (!pairs.whole_block()) box.refresh(done, qx0, qy0);
 		if (hit) {
 			id = point_list[range.x + (uint32_t)(base + lane)];
 			if (cull) {
-				hit = cull_hit(bbox[2 * id], bbox[2 * id + 1], qx0 - CULL_PAD, qx1 + CULL_PAD, qy0 - CULL_PAD, qy1 + CULL_PAD);
+				hit = cull_hit(bbox[2 * id], bbox[2 * id + 1], box.x0, box.x1, box.y0, box.y1);
 			}
 		}
 		const unsigned long long mm = __ballot(hit);
@@ -274,6 +277,7 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 		auto fetch = [&](int k) { return fetch_rec<G_REC_F4>(rec, hid, k); };
 		auto blend = [&](int k, const Rec& R, auto&& prefetch_next) -> bool {   // true: every pixel of the block has retired
 			const uint32_t contributor = (uint32_t)(base + (int)__builtin_amdgcn_readlane(hj, k) + 1);
+			if constexpr (COUNT) npairs++;
 			// straight-line for all 64 lanes: a rejected pair blends with weight 0 (see surfel_render_fwd_wave_kernel)
 			float dx, dy, G, alpha;
 			const lmask live = gauss_pair(R.f[0], R.f[1].x, R.f[1].y, pixx, pixy, dx, dy, G, alpha) & ~done;
@@ -305,6 +309,9 @@ gauss_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* _
 		// the batch's blend mask (bit = position in the batch): the backward tile kernel walks exactly these entries
 		const lmask blended = __ballot(hit && ((blendk >> kown) & 1ull) != 0ull);
 		if (lane == 0) blend_mask[(size_t)quad * mask_stride + batch0 + (size_t)(base / WBATCH)] = blended;
+	}
+	if constexpr (COUNT) {
+		if (lane == 0) atomicAdd(pairs.word, (unsigned long long)npairs);
 	}
 	if (inside) {
 		const size_t HW = (size_t)H * W;
@@ -753,9 +760,17 @@ extern "C" int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, in
 	const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
 	{
 		StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
-		auto kern = out_invdepth ? gauss_render_fwd_wave_kernel<true> : gauss_render_fwd_wave_kernel<false>;
-		kern<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(), background,
-		                                img.final_T, img.n_contrib, out_color, out_normal_map, out_refl_strength_map, out_invdepth, bin.blend_mask, bin.mask_stride);
+		auto launch = [&](auto kern, auto pairs) {
+			kern<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(), background,
+			                                img.final_T, img.n_contrib, out_color, out_normal_map, out_refl_strength_map, out_invdepth, bin.blend_mask, bin.mask_stride, pairs);
+		};
+		if (option_dev() & 2) {   // development: the instances that count their evaluated pairs
+			unsigned long long* word = dev_pair_counter();
+			if (!word) { set_error("gsr_gauss_forward: no pair counter"); return GSR_E_HIP; }
+			launch(out_invdepth ? gauss_render_fwd_wave_kernel<true, true> : gauss_render_fwd_wave_kernel<false, true>, PairCount<true>{word, option_dev() & 4});
+		} else {
+			launch(out_invdepth ? gauss_render_fwd_wave_kernel<true> : gauss_render_fwd_wave_kernel<false>, PairCount<false>{});
+		}
 	}
 	GSR_LAUNCH_CHECK(debug, stream);
 	return R;

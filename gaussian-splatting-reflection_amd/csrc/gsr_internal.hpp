@@ -197,7 +197,10 @@ static inline int backward_prologue(const char* entry, const char* func, const W
 }
 
 int option_cull();   // 1 (default): per-wave bounding-box culling in the tile kernels; 0: evaluate every list entry
-int option_dev();    // development ablation bits (0 in production): 1 = skip the gradient atomics of the surfel backward
+int option_dev();    // development bits (0 in production): 1 = skip the gradient atomics of the surfel backward; 2 = the forward tile kernels add
+                     // the (wave, entry) pairs they evaluate to the current device's word (dev_pair_counter; gsr_debug_fetch("pairs") reads it); 4 = with 2, the vote
+                     // tests against the whole 8x8 block, not against its live pixels (the count the live box is compared with)
+unsigned long long* dev_pair_counter();   // device address of that word: allocated and zeroed at its first use, never reset; NULL on failure
 size_t sort_temp_bytes(size_t R, int end_bit);
 int run_tile_order(const ImageState& img, size_t tiles, hipStream_t stream);
 uint32_t higher_msb(uint32_t n);

@@ -439,14 +439,14 @@ __device__ __forceinline__ const SurfelReflFwd& refl_args(const SurfelEvalFwd& a
 // out_others planes 0 and 5..7 and the reflection sort keys.  What is left — vote, compaction, the blending of colour, T, normal and reflection
 // strength in the same expressions and order, the same early exit, the reflection epilogue — gives bit-identical colour, alpha, normal and
 // reflection planes (each pixel's accumulation runs sequentially over the tile's list in both instances).
-template <bool REFL, bool TRAIN>
+template <bool REFL, bool TRAIN, bool COUNT = false>
 __global__ void __launch_bounds__(64) GSR_FWD_ATTR
 surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ point_list, int W, int H, int tiles_x, int ntiles,
                               const float4* __restrict__ rec, const float4* __restrict__ bbox, int cull, const float* __restrict__ bg,
                               float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
                               float* __restrict__ out_others, float* __restrict__ out_refl, float* __restrict__ gaussian_weights,
                               unsigned long long* __restrict__ blend_mask, size_t mask_stride,
-                              std::conditional_t<TRAIN, SurfelReflFwd, SurfelEvalFwd> args) {
+                              std::conditional_t<TRAIN, SurfelReflFwd, SurfelEvalFwd> args, PairCount<COUNT> pairs) {
 	const SurfelReflFwd& rf = refl_args(args);
 	const uint32_t slot = xcd_slot(blockIdx.x);   // dispatch slot -> (tile, quadrant), longest lists first
 	if (slot >= (uint32_t)ntiles * 4u) return;
@@ -460,13 +460,15 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 	const v2f pix = mk2((float)px, (float)py);
 	const uint2 range = ranges[tile];
 	const int count = (int)(range.y - range.x);
-	const float qx0 = (float)bx0, qy0 = (float)by0, qx1 = qx0 + 7.0f, qy1 = qy0 + 7.0f;
+	const float qx0 = (float)bx0, qy0 = (float)by0;
 
 	__shared__ uint32_t s_hid[WBATCH];
 	__shared__ uint32_t s_hc[TRAIN ? WBATCH : 1];
 	__shared__ float4 s_wmax[TRAIN ? WBATCH : 1];   // [hit][16-lane row = 4x4 sub-block]: row maxima of the blend weight
 
 	lmask done = ~LMASK(px < W) | ~LMASK(py < H);  // lanes outside the image never blend
+	LiveBox<true> box(qx0, qy0);                   // what the vote tests against: the block's pixels that are still alive
+	uint32_t npairs = 0;                           // (COUNT) pairs this wave evaluated
 	SurfelFwdPix st;
 	st.T = 1.0f;
 	st.C2 = st.M2 = st.distortion = st.median_depth = st.maskacc = 0.f;
@@ -484,11 +486,12 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 		// ---- 1. vote
 		bool hit = lane < nb;
 		uint32_t id = 0;
+		if (!pairs.whole_block()) box.refresh(done, qx0, qy0);
 		if (hit) {
 			id = point_list[range.x + (uint32_t)(base + lane)];
 			if (cull) {
 				// (the cull record itself is already dilated by half a pixel)
-				hit = cull_hit(bbox[2 * id], bbox[2 * id + 1], qx0 - CULL_PAD, qx1 + CULL_PAD, qy0 - CULL_PAD, qy1 + CULL_PAD);
+				hit = cull_hit(bbox[2 * id], bbox[2 * id + 1], box.x0, box.x1, box.y0, box.y1);
 			}
 		}
 		const unsigned long long mm = __ballot(hit);
@@ -520,24 +523,28 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k);
 				if (k + 1 < nh) B = fetch(k + 1);
 				any |= surfel_fwd_pair<TRAIN>(A, pix, c, med_live, st, done, w0, grazed);
+				if constexpr (COUNT) npairs++;
 				stop = done == ~0ull || k + 1 >= nh;
 			}
 			if (!stop) {
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k + 1);
 				if (k + 2 < nh) A = fetch(k + 2);
 				any |= surfel_fwd_pair<TRAIN>(B, pix, c, med_live, st, done, w1, grazed);
+				if constexpr (COUNT) npairs++;
 				stop = done == ~0ull || k + 2 >= nh;
 			}
 			if (!stop) {
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k + 2);
 				if (k + 3 < nh) B = fetch(k + 3);
 				any |= surfel_fwd_pair<TRAIN>(A, pix, c, med_live, st, done, w2, grazed);
+				if constexpr (COUNT) npairs++;
 				stop = done == ~0ull || k + 3 >= nh;
 			}
 			if (!stop) {
 				const uint32_t c = __builtin_amdgcn_readlane(hc, k + 3);
 				if (k + 4 < nh) A = fetch(k + 4);
 				any |= surfel_fwd_pair<TRAIN>(B, pix, c, med_live, st, done, w3, grazed);
+				if constexpr (COUNT) npairs++;
 				stop = done == ~0ull;
 			}
 			if constexpr (TRAIN) {
@@ -573,6 +580,9 @@ surfel_render_fwd_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* 
 			blend_mask[(batch0 + (size_t)(base / WBATCH)) * 16u + quad * 4u + (uint32_t)lane] = mine;
 		}
 		__syncthreads();
+	}
+	if constexpr (COUNT) {
+		if (lane == 0) atomicAdd(pairs.word, (unsigned long long)npairs);
 	}
 	if (inside) {
 		const size_t HW = (size_t)H * W;
@@ -1280,10 +1290,18 @@ static int surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, in
 	{ StageTimer st_(GSR_STAGE_RENDER_FWD, stream);
 		const int nunits = (int)xcd_grid((uint32_t)ntiles * 4u);
 		const auto args = [&] { if constexpr (TRAIN) return rf; else return SurfelEvalFwd{rf, out_alpha, out_normal_view}; }();
-		auto render = refl ? surfel_render_fwd_wave_kernel<true, TRAIN> : surfel_render_fwd_wave_kernel<false, TRAIN>;
-		render<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(),
-		                                  background, TRAIN ? img.final_T : nullptr, TRAIN ? img.n_contrib : nullptr, out_color, out_others,
-		                                  out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, args); }
+		auto launch = [&](auto render, auto pairs) {
+			render<<<nunits, 64, 0, stream>>>(img.ranges, img.tile_order, bin.point_list, width, height, tiles_x, ntiles, geom.rec, geom.bbox, option_cull(),
+			                                  background, TRAIN ? img.final_T : nullptr, TRAIN ? img.n_contrib : nullptr, out_color, out_others,
+			                                  out_refl_strength_map, gaussian_weights, bin.blend_mask, bin.mask_stride, args, pairs);
+		};
+		if (option_dev() & 2) {   // development: the instances that count their evaluated pairs
+			unsigned long long* word = dev_pair_counter();
+			if (!word) { set_error("gsr_surfel_forward: no pair counter"); return GSR_E_HIP; }
+			launch(refl ? surfel_render_fwd_wave_kernel<true, TRAIN, true> : surfel_render_fwd_wave_kernel<false, TRAIN, true>, PairCount<true>{word, option_dev() & 4});
+		} else {
+			launch(refl ? surfel_render_fwd_wave_kernel<true, TRAIN> : surfel_render_fwd_wave_kernel<false, TRAIN>, PairCount<false>{});
+		} }
 		GSR_LAUNCH_CHECK(debug, stream);
 	}
 	// one exit for both paths: with scratch the training forward also sorts the keys it wrote, whatever P (include/gsr_hip.h)

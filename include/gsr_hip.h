@@ -235,7 +235,11 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
  * Names: "depths" f32[P], "means2D" f32[P,2], "tiles_touched" u32[P], "point_offsets" u32[P],
  * "clamped" u8[P,3], "rgb" f32[P,3], "geom4" f32[P,4] (conic_opacity / normal_opacity),
  * "transMat" f32[P,9] (S), "cov3D" f32[P,6] (G), "point_list" u32[R], "keys" u64[R],
- * "ranges" u32[tiles,2], "final_T" f32[planes,H,W], "n_contrib" u32[planes,H,W]. */
+ * "ranges" u32[tiles,2], "final_T" f32[planes,H,W], "n_contrib" u32[planes,H,W], "blend_mask" u64[16 * (R / 64 + tiles + 1)] (the
+ * entries of each 64-entry batch that blended: S [batch][quadrant][4x4 sub-block], G [quadrant][batch] in the first quarter; batch b of tile
+ * t is batch index ranges[t][0] / 64 + t + b).
+ * "pairs" u64[1] reads no workspace (the buffers may be NULL): the running number of (wave, list entry) pairs the forward tile kernels have
+ * evaluated on the current device while the "dev" option had bit 2 set (gsr_set_option); it is never reset, so take differences. */
 int gsr_debug_fetch(int variant, const char* name, int P, int R, int width, int height, const void* geom_buffer,
                     const void* binning_buffer, const void* image_buffer, void* dst, void* stream);
 
@@ -527,8 +531,10 @@ int gsr_adam_step_range(float* param, const float* grad, float* exp_avg, float* 
 #define GSR_STAGE_REFL_BWD_TAIL 17   /* texel-gradient tail of the reflection backward (sort + run combine + unpack); on the side stream with async_tail */
 #define GSR_STAGE_COUNT 18
 /* Test/diagnostic switches.  "cull" (default 1): per-wave footprint culling inside the tile kernels (each wave votes
- * which list entries can reach its 8x8 pixel block at all); outputs are bit-identical with 0 and 1, it only skips
- * (wave, Gaussian) pairs that cannot blend.  "dev" (default 0): development ablation bits, not for production.  "emit_items" (default 0 =
+ * which list entries can reach the pixels of its 8x8 block that have not retired yet); outputs are bit-identical with 0 and 1, it only skips
+ * (wave, Gaussian) pairs that cannot blend.  "dev" (default 0): development bits, not for production (1: the surfel backward skips its gradient atomics; 2: the
+ * forward tile kernels run as instances that count their evaluated pairs, see gsr_debug_fetch "pairs"; 4: with 2, those instances vote against
+ * the whole block instead of its live pixels).  "emit_items" (default 0 =
  * chosen by the Gaussian count): 1 / 2 force the Gaussians per thread of key emission (tests).  "mailbox", "sort_driver" (default 1): 0 = the
  * round-2 read-back of num_rendered / the public rocPRIM sort entry points. */
 int gsr_set_option(const char* name, int value);
