@@ -298,11 +298,16 @@ def require_cuda(t, name):
         raise RuntimeError(f"{name} must be a CUDA tensor")
 
 
-def f32c(t, name):
-    """Contiguous float32 view (reference: `.contiguous().data<float>()` throws on other dtypes)."""
+def f32c(t, name, aligned=False):
+    """Contiguous float32 view (reference: `.contiguous().data<float>()` throws on other dtypes).  aligned: on a 16-byte boundary as well —
+    a contiguous view at an odd offset of a packed buffer (the SH coefficients of one flat parameter buffer) is copied, where the library
+    would refuse it (include/gsr_hip.h, "alignment")."""
     if t.numel() and t.dtype != torch.float32:
         raise RuntimeError(f"expected scalar type Float but found {t.dtype} for {name}")
-    return t.contiguous()
+    t = t.contiguous()
+    if aligned and t.numel() and t.data_ptr() % 16:
+        t = t.clone()
+    return t
 
 
 # ------------------------------------------------------------------ what the two rasterizer bindings share
@@ -363,9 +368,9 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     if PYBIND is not None:
         return PYBIND.mark_visible(means3D, viewmatrix, projmatrix)
     P = means3D.size(0)
+    m3, vm, pm = f32c(means3D, "means3D"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix")     # dtype checks in front of the allocation
     present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
     if P != 0:
-        m3, vm, pm = f32c(means3D, "means3D"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix")
         with torch.cuda.device(means3D.device):
             check(lib.gsr_mark_visible(P, ptr(m3), ptr(vm), ptr(pm), ptr(present), stream_ptr(means3D.device)), "gsr_mark_visible")
     return present

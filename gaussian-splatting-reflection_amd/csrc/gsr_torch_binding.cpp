@@ -35,14 +35,17 @@ void* resize_cb(void* user, int which, size_t bytes) {   // replaces resizeFunct
 	return ws->bufs[which].data_ptr();
 }
 
-// contiguous float view; an empty tensor maps to NULL (the reference's `.contiguous().data<float>()` is nullptr then)
+// contiguous float view; an empty tensor maps to NULL (the reference's `.contiguous().data<float>()` is nullptr then).  aligned16: on a
+// 16-byte boundary as well (the SH coefficients: a contiguous view at an odd offset of a packed buffer is copied, where the library
+// would refuse it)
 struct FloatArg {
 	torch::Tensor keep;
 	const float* p;
-	FloatArg(const torch::Tensor& t, const char* name) : p(nullptr) {
+	FloatArg(const torch::Tensor& t, const char* name, bool aligned16 = false) : p(nullptr) {
 		if (t.numel() == 0) return;
 		TORCH_CHECK(t.scalar_type() == torch::kFloat32, "expected scalar type Float but found ", t.scalar_type(), " for ", name);
 		keep = t.contiguous();
+		if (aligned16 && (reinterpret_cast<uintptr_t>(keep.data_ptr()) & 15) != 0) keep = keep.clone();
 		p = keep.data_ptr<float>();
 	}
 };
@@ -67,10 +70,6 @@ SurfelForward(const torch::Tensor& background, const torch::Tensor& means3D, con
 	REQUIRE_CUDA(rotations); REQUIRE_CUDA(transMat_precomp); REQUIRE_CUDA(viewmatrix); REQUIRE_CUDA(projmatrix); REQUIRE_CUDA(sh); REQUIRE_CUDA(campos);
 	const int P = (int)means3D.size(0), H = image_height, W = image_width;
 	const DeviceGuard guard(means3D.device());
-	auto f = means3D.options().dtype(torch::kFloat32);
-	auto out_color = torch::empty({3, H, W}, f), out_others = torch::empty({8, H, W}, f), out_refl = torch::empty({1, H, W}, f);
-	auto radii = torch::empty({P}, means3D.options().dtype(torch::kInt32)), gw = torch::empty({P}, f);
-	Workspace ws(means3D);
 	const int M = sh.numel() ? (int)sh.size(1) : 0;
 	torch::Tensor mask;
 	const uint8_t* mask_p = nullptr;
@@ -79,9 +78,14 @@ SurfelForward(const torch::Tensor& background, const torch::Tensor& means3D, con
 		mask = env_scope_mask.contiguous();
 		mask_p = reinterpret_cast<const uint8_t*>(mask.data_ptr<bool>());
 	}
-	FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh"), col(colors, "colors"), refl(refl_strengths, "refl_strengths"),
+	FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh", true), col(colors, "colors"), refl(refl_strengths, "refl_strengths"),
 	    opa(opacity, "opacity"), sca(scales, "scales"), rot(rotations, "rotations"), tm(transMat_precomp, "transMat_precomp"),
 	    vm(viewmatrix, "viewmatrix"), pm(projmatrix, "projmatrix"), cp(campos, "campos");
+	// (outputs only once every input has passed its dtype check: a refused call allocates nothing on the device)
+	auto f = means3D.options().dtype(torch::kFloat32);
+	auto out_color = torch::empty({3, H, W}, f), out_others = torch::empty({8, H, W}, f), out_refl = torch::empty({1, H, W}, f);
+	auto radii = torch::empty({P}, means3D.options().dtype(torch::kInt32)), gw = torch::empty({P}, f);
+	Workspace ws(means3D);
 	const int rendered = gsr_surfel_forward(resize_cb, &ws, P, degree, M, bg.p, W, H, m3.p, mask_p, shc.p, col.p, refl.p, opa.p, sca.p, scale_modifier, rot.p,
 	                                        tm.p, vm.p, pm.p, cp.p, tan_fovx, tan_fovy, prefiltered, out_color.data_ptr<float>(),
 	                                        out_others.data_ptr<float>(), out_refl.data_ptr<float>(), radii.data_ptr<int>(), gw.data_ptr<float>(),
@@ -111,7 +115,7 @@ SurfelBackward(const torch::Tensor& background, const torch::Tensor& means3D, co
 	     dL_drefl = mk({P, 1});
 	if (P != 0) {
 		torch::Tensor grefl_t = dL_dout_refl_strength_map.numel() ? dL_dout_refl_strength_map : torch::zeros({1, H, W}, f);
-		FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh"), col(colors, "colors"), refl(refl_strengths, "refl_strengths"),
+		FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh", true), col(colors, "colors"), refl(refl_strengths, "refl_strengths"),
 		    sca(scales, "scales"), rot(rotations, "rotations"), tm(transMat_precomp, "transMat_precomp"), vm(viewmatrix, "viewmatrix"),
 		    pm(projmatrix, "projmatrix"), cp(campos, "campos"), gcol(dL_dout_color, "dL_dout_color"), goth(dL_dout_others, "dL_dout_others"),
 		    grefl(grefl_t, "dL_dout_refl_strength_map");
@@ -139,14 +143,15 @@ GaussForward(const torch::Tensor& background, const torch::Tensor& means3D, cons
 	REQUIRE_CUDA(means3D);
 	const int P = (int)means3D.size(0), H = image_height, W = image_width;
 	const DeviceGuard guard(means3D.device());
+	const int M = sh.numel() ? (int)sh.size(1) : 0;
+	FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh", true), col(colors, "colors"), nrm(normals, "normals"),
+	    refl(refl_strengths, "refl_strengths"), opa(opacity, "opacity"), sca(scales, "scales"), rot(rotations, "rotations"), cov(cov3D_precomp, "cov3D_precomp"),
+	    vm(viewmatrix, "viewmatrix"), pm(projmatrix, "projmatrix"), cp(campos, "campos");
+	// (outputs only once every input has passed its dtype check, as in SurfelForward)
 	auto f = means3D.options().dtype(torch::kFloat32);
 	auto out_color = torch::empty({3, H, W}, f), out_normal = torch::empty({3, H, W}, f), out_inv = torch::empty({1, H, W}, f), out_refl = torch::empty({1, H, W}, f);
 	auto radii = torch::empty({P}, means3D.options().dtype(torch::kInt32));
 	Workspace ws(means3D);
-	const int M = sh.numel() ? (int)sh.size(1) : 0;
-	FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh"), col(colors, "colors"), nrm(normals, "normals"),
-	    refl(refl_strengths, "refl_strengths"), opa(opacity, "opacity"), sca(scales, "scales"), rot(rotations, "rotations"), cov(cov3D_precomp, "cov3D_precomp"),
-	    vm(viewmatrix, "viewmatrix"), pm(projmatrix, "projmatrix"), cp(campos, "campos");
 	const int rendered = gsr_gauss_forward(resize_cb, &ws, P, degree, M, bg.p, W, H, m3.p, shc.p, col.p, nrm.p, refl.p, opa.p, sca.p, scale_modifier, rot.p, cov.p,
 	                                       vm.p, pm.p, cp.p, tan_fovx, tan_fovy, prefiltered, out_color.data_ptr<float>(), out_normal.data_ptr<float>(),
 	                                       out_refl.data_ptr<float>(), out_inv.data_ptr<float>(), antialiasing, radii.data_ptr<int>(), debug,
@@ -179,7 +184,7 @@ GaussBackward(const torch::Tensor& background, const torch::Tensor& means3D, con
 	auto dL_dinvdepths = has_inv ? mk({P, 1}) : torch::zeros({0, 1}, f);
 	if (P != 0) {
 		torch::Tensor grefl_t = has_refl ? dL_dout_refl_strength_map : torch::zeros({1, H, W}, f);
-		FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh"), col(colors, "colors"), nrm(normals, "normals"),
+		FloatArg bg(background, "background"), m3(means3D, "means3D"), shc(sh, "sh", true), col(colors, "colors"), nrm(normals, "normals"),
 		    refl(refl_strengths, "refl_strengths"), opa(opacities, "opacities"), sca(scales, "scales"), rot(rotations, "rotations"),
 		    cov(cov3D_precomp, "cov3D_precomp"), vm(viewmatrix, "viewmatrix"), pm(projmatrix, "projmatrix"), cp(campos, "campos"),
 		    gcol(dL_dout_color, "dL_dout_color"), gnrm(dL_dout_normal_map, "dL_dout_normal_map"), grefl(grefl_t, "dL_dout_refl_strength_map"),
@@ -200,10 +205,10 @@ GaussBackward(const torch::Tensor& background, const torch::Tensor& means3D, con
 
 torch::Tensor MarkVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix, torch::Tensor& projmatrix) {
 	const int P = (int)means3D.size(0);
+	const DeviceGuard guard(means3D.device());
+	FloatArg m3(means3D, "means3D"), vm(viewmatrix, "viewmatrix"), pm(projmatrix, "projmatrix");     // dtype checks in front of the allocation
 	auto present = torch::zeros({P}, means3D.options().dtype(torch::kBool));
 	if (P != 0) {
-		const DeviceGuard guard(means3D.device());
-		FloatArg m3(means3D, "means3D"), vm(viewmatrix, "viewmatrix"), pm(projmatrix, "projmatrix");
 		check(gsr_mark_visible(P, m3.p, vm.p, pm.p, reinterpret_cast<uint8_t*>(present.data_ptr<bool>()), current_stream(means3D)), "gsr_mark_visible");
 	}
 	return present;

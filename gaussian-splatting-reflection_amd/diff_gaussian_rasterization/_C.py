@@ -21,7 +21,7 @@ SINKABLE = frozenset(("means3D", "shs", "opacities", "scales", "rotations", "ref
 def _inputs(background, means3D, sh, colors, normals, refl_strengths, opacity, opacity_name, scales, rotations, cov3D_precomp, viewmatrix,
             projmatrix, campos):
     """The contiguous float32 inputs of both directions in the order of the C entries.  opacity_name: what the caller's signature calls it."""
-    return [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh"), f32c(colors, "colors"), f32c(normals, "normals"),
+    return [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh", aligned=True), f32c(colors, "colors"), f32c(normals, "normals"),
             f32c(refl_strengths, "refl_strengths"), f32c(opacity, opacity_name), f32c(scales, "scales"), f32c(rotations, "rotations"),
             f32c(cov3D_precomp, "cov3D_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"), f32c(campos, "campos")]
 
@@ -38,6 +38,10 @@ def rasterize_gaussians(background, means3D, colors, normals, refl_strengths, op
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if not means3D.is_cuda:
         raise RuntimeError("means3D must be a CUDA tensor")
+    # the dtype checks come first: a refused call has allocated nothing on the device (as variant S, _forward_inputs)
+    keep = _inputs(background, means3D, sh, colors, normals, refl_strengths, opacity, "opacity", scales, rotations, cov3D_precomp, viewmatrix,
+                   projmatrix, campos)
+    bg, m3, shc, col, nrm, refl, opa, sca, rot, cov, vm, pm, cp = keep
     P, H, W = means3D.size(0), int(image_height), int(image_width)
     dev = means3D.device
     fopts = dict(dtype=torch.float32, device=dev)
@@ -48,9 +52,6 @@ def rasterize_gaussians(background, means3D, colors, normals, refl_strengths, op
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     ws = _gsr.Workspace(dev)
     M = _gsr.sh_coeffs(sh, empty_scene_counts=False)
-    keep = _inputs(background, means3D, sh, colors, normals, refl_strengths, opacity, "opacity", scales, rotations, cov3D_precomp, viewmatrix,
-                   projmatrix, campos)
-    bg, m3, shc, col, nrm, refl, opa, sca, rot, cov, vm, pm, cp = keep
     with torch.cuda.device(dev):
         rendered = check(lib.gsr_gauss_forward(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(shc), ptr(col), ptr(nrm), ptr(refl),
                                                ptr(opa), ptr(sca), float(scale_modifier), ptr(rot), ptr(cov), ptr(vm), ptr(pm), ptr(cp),

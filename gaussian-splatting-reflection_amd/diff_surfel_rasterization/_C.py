@@ -30,7 +30,7 @@ def _forward_inputs(background, means3D, colors, refl_strengths, opacity, scales
                     ("opacity", opacity), ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
                     ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh), ("campos", campos)):
         require_cuda(t, name)
-    keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh"), f32c(colors, "colors"),
+    keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh", aligned=True), f32c(colors, "colors"),
             f32c(refl_strengths, "refl_strengths"), f32c(opacity, "opacity"), f32c(scales, "scales"), f32c(rotations, "rotations"),
             f32c(transMat_precomp, "transMat_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"),
             f32c(campos, "campos")]
@@ -186,7 +186,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, refl_streng
     if dL_dout_refl_strength_map is None or dL_dout_refl_strength_map.numel() == 0:
         dL_dout_refl_strength_map = torch.zeros((1, H, W), **o)
     if P != 0:
-        keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh"), f32c(colors, "colors"),
+        keep = [f32c(background, "background"), f32c(means3D, "means3D"), f32c(sh, "sh", aligned=True), f32c(colors, "colors"),
                 f32c(refl_strengths, "refl_strengths"), f32c(scales, "scales"), f32c(rotations, "rotations"),
                 f32c(transMat_precomp, "transMat_precomp"), f32c(viewmatrix, "viewmatrix"), f32c(projmatrix, "projmatrix"),
                 f32c(campos, "campos"), f32c(dL_dout_color, "dL_dout_color"), f32c(dL_dout_others, "dL_dout_others"),

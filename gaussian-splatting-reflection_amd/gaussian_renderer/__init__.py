@@ -118,9 +118,12 @@ def _ray_block(view):
     W, H = int(view.image_width), int(view.image_height)
 
     def build():
-        c2w = (wvt.T).inverse()
+        # from contiguous copies: the reference's cameras hold `.transpose(0, 1)` views, and torch's inverse and matrix product round
+        # differently for another memory layout of the same matrix (surf_normal moved by 7e-6)
+        wv, fp = wvt.contiguous(), fpt.contiguous()
+        c2w = (wv.T).inverse()
         ndc2pix = torch.tensor([[W / 2, 0, 0, W / 2], [0, H / 2, 0, H / 2], [0, 0, 0, 1]], dtype=torch.float32, device=wvt.device).T
-        intrins = ((c2w.T @ fpt) @ ndc2pix)[:3, :3].T
+        intrins = ((c2w.T @ fp) @ ndc2pix)[:3, :3].T
         M = intrins.inverse().T @ c2w[:3, :3].T
         return torch.cat([M.reshape(-1), c2w[:3, 3].reshape(-1)]).float().contiguous()
     return _cached_block("ray", (wvt, fpt), (W, H), build)
@@ -262,7 +265,9 @@ class _RasterizeReflect(torch.autograd.Function):
         cm, fv = cubemap.float().contiguous(), fail_value.float().contiguous()
         if cm.dim() != 4 or cm.shape[1] != 3:
             raise RuntimeError("rasterize_reflect: the cubemap must be (6, 3, L, L)")
-        want_keys = REFLECTION_BACKWARD_BINNED and REFLECTION_FORWARD_KEYS and any(ctx.needs_input_grad[:len(v.tensors) + 2])
+        # the keys serve the texel-gradient tail alone: with the cubemap and the fail value frozen (the reference's initial stage) nothing
+        # reads that gradient, so the forward does not spend the H * W words on them
+        want_keys = REFLECTION_BACKWARD_BINNED and REFLECTION_FORWARD_KEYS and any(ctx.needs_input_grad[len(v.tensors):len(v.tensors) + 2])
         # With an asynchronous tail the keys are sorted HERE, on the side stream behind the forward's tile kernel: the sort then runs beside
         # whatever follows the forward (the loss, the start of the backward) instead of racing the tile backward for CUs
         early = want_keys and refl_sink is not None and refl_sink.async_tail and bool(refl_sink.tensors)
@@ -273,6 +278,7 @@ class _RasterizeReflect(torch.autograd.Function):
             _gsr.side_hold(scratch, keys)       # the side stream reads / writes them from now on (until side_join)
         ctx.raster_settings, ctx.num_rendered = settings, num_rendered
         ctx.raster_sink, ctx.refl_sink, ctx.sort_keys, ctx.scratch = raster_sink, refl_sink, keys, scratch
+        ctx.passes = 0      # backward passes made through this node (retain_graph=True allows more than one)
         ctx.save_for_backward(*[t[k] for k in v.saved], radii, *buffers, color, others, refl_map, cm, fv, cam, rgba)
         ctx.mark_non_differentiable(radii, weights)
         ctx.set_materialize_grads(False)
@@ -286,6 +292,15 @@ class _RasterizeReflect(torch.autograd.Function):
         saved = dict(zip(v.saved, kept[:ns]))
         radii, geom, binning, img, color, others, refl_map, cm, fv, cam, rgba = kept[ns:]
         cont = lambda g: None if g is None else g.float().contiguous()
+        if ctx.scratch is not None and ctx.passes:
+            # A further pass through a retained graph takes the scratch the forward sorted into once more.  The sorted keys and the pixel
+            # list in it are only ever read (the backward writes the staging texels, the fail-value slot, the footprint records and the
+            # unsorted key slots of it, csrc/gsr_cubemap.hip), so they are still valid; but the previous pass's tail may still be reading the
+            # footprint records and adding to the staging texels on the side stream while this pass's fill and pixel kernel, on this stream,
+            # overwrite them: order this stream behind that tail first
+            with torch.cuda.device(cam.device):
+                check(lib.gsr_side_join(stream_ptr(cam.device)), "gsr_side_join")
+        ctx.passes += 1
         # ---- 1. reflection backward (pixel kernel on this stream, texel-gradient tail beside what follows); others[2:5] is contiguous
         g_nv, g_base, g_s, g_cm, g_fail = _reflection_backward((others[2:5], color, refl_map, cm, fv, cam, rgba), (g_final, g_refl_color, g_normal_world),
                                                                ctx.refl_sink, ctx.sort_keys, ctx.scratch)

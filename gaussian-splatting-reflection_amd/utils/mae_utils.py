@@ -8,12 +8,14 @@
 """
 import torch
 
+from _gsr import f32c
 from gsr_eval import MetricsTable
 
 
 def angular_error_map(pred, gt, eps=1e-8):
     """pred, gt: [3, H, W] float32 on the device.  Returns [H, W]: the angle between them in degrees, NaN where a norm is <= eps or the
     angle is NaN (utils/mae_utils.py:3-29)."""
+    f32c(pred, "pred"), f32c(gt, "gt")       # the dtype errors of normals(), in front of the allocations below
     out = torch.empty(pred.shape[1:], dtype=torch.float32, device=pred.device)
     MetricsTable(1, pred.device).normals(0, pred, gt, eps=eps, error_map=out)
     return out
