@@ -170,6 +170,17 @@ def _load():
         lib.gsr_present_view_scratch_floats.argtypes = [c_int, c_int, c_int, c_int]
         lib.gsr_present_view.restype = c_int
         lib.gsr_present_view.argtypes = [P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
+    if hasattr(lib, "gsr_photometric_forward"):
+        # (likewise: a library built before the composited loss and the SSIM-map gradient lacks these four; utils.loss_utils then
+        # refuses to import)
+        lib.gsr_photometric_scratch_floats.restype = c_size_t
+        lib.gsr_photometric_scratch_floats.argtypes = [c_int, c_int, c_int]
+        lib.gsr_photometric_forward.restype = c_int
+        lib.gsr_photometric_forward.argtypes = [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P]
+        lib.gsr_photometric_backward.restype = c_int
+        lib.gsr_photometric_backward.argtypes = [P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P]
+        lib.gsr_ssim_map_backward.restype = c_int
+        lib.gsr_ssim_map_backward.argtypes = [P, P, c_int, c_int, c_int, P, P, P, P, P, P]
     return lib
 
 
@@ -211,7 +222,8 @@ EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_b
             "gsr_deferred_reflection_scratch_floats", "gsr_deferred_reflection_backward", "gsr_ssim_l1_scratch_floats", "gsr_ssim_l1_forward", "gsr_ssim_l1_backward", "gsr_normal_loss_scratch_floats", "gsr_normal_loss_forward", "gsr_normal_loss_backward", "gsr_adam_step", "gsr_adam_step_range", "gsr_densification_stats", "gsr_gather_rows", "gsr_split_children", "gsr_surface_forward", "gsr_surface_backward", "gsr_profile_enable",
             "gsr_profile_collect", "gsr_set_option", "gsr_knn_scratch_bytes", "gsr_knn_mean_dist",
             "gsr_image_metrics_scratch_floats", "gsr_image_metrics", "gsr_normal_mae_scratch_floats", "gsr_normal_mae",
-            "gsr_present_view_scratch_floats", "gsr_present_view"]
+            "gsr_present_view_scratch_floats", "gsr_present_view",
+            "gsr_photometric_scratch_floats", "gsr_photometric_forward", "gsr_photometric_backward", "gsr_ssim_map_backward"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

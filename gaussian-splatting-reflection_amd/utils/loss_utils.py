@@ -2,9 +2,11 @@
 
 Same names and call shapes as the reference module: `l1_loss`, `l2_loss`, `ssim`, `fast_ssim`, `FusedSSIMMap`
 (utils/loss_utils.py:24-97), plus `photometric_loss`, the fused form of train.py:167-173
-`(1 - lambda_dssim) * l1_loss + lambda_dssim * (1 - ssim)` that runs ONE forward and ONE backward kernel.
-All of them call libgsr_hip.so (gsr_ssim_l1_forward / gsr_ssim_l1_backward, include/gsr_hip.h); there is no
-torch-conv fallback.  Only the reference's window (size 11, sigma 1.5, zero padding 5) is implemented.
+`(1 - lambda_dssim) * l1_loss + lambda_dssim * (1 - ssim)` that runs ONE forward and ONE backward kernel, also on the
+composites of train.py:158-159 (`alpha=`, `gt_alpha_mask=`, `background=`), which the kernels form while they load.
+All of them call libgsr_hip.so (gsr_ssim_l1_forward / _backward, gsr_photometric_forward / _backward,
+gsr_ssim_map_backward, include/gsr_hip.h); there is no torch-conv fallback.  Only the reference's window (size 11,
+sigma 1.5, zero padding 5) is implemented.
 """
 import weakref
 
@@ -12,18 +14,21 @@ import torch
 
 from _gsr import check, f32c, lib, ptr, require_cuda, stream_ptr
 
+if not hasattr(lib, "gsr_photometric_forward"):
+    raise ImportError("libgsr_hip.so does not export gsr_photometric_forward: it was built before the composited loss "
+                      "(csrc/gsr_loss.hip); rebuild with csrc/build.py --force")
+
 C1 = 0.01 ** 2
 C2 = 0.03 ** 2
 
 
 def _chw(img, name):
+    """The image as contiguous float32 planes [B*C, H, W]: the kernels treat every plane on its own, so a batch is more planes."""
     require_cuda(img, name)
     if img.dim() == 4:
-        if img.size(0) != 1:
-            raise ValueError(f"{name}: batched input is supported for batch size 1 only, got {tuple(img.shape)}")
-        img = img[0]
+        img = img.reshape(img.size(0) * img.size(1), img.size(2), img.size(3))
     if img.dim() != 3:
-        raise ValueError(f"{name}: expected (C,H,W) or (1,C,H,W), got {tuple(img.shape)}")
+        raise ValueError(f"{name}: expected (C,H,W) or (B,C,H,W), got {tuple(img.shape)}")
     return f32c(img, name)
 
 
@@ -134,7 +139,11 @@ def ssim(img1, img2, window_size=11, size_average=True):
     if window_size != 11:
         raise NotImplementedError("only the reference's 11x11 window is implemented on the HIP path")
     if not size_average:
-        raise NotImplementedError("size_average=False is not used by the reference's train loop and is not implemented")
+        # the per-image mean `ssim_map.mean(1).mean(1).mean(1)` of a batch [B,C,H,W] (a [C,H,W] image counts as a batch of one)
+        smap = FusedSSIMMap.apply(C1, C2, img1, img2)
+        if smap.dim() == 3:
+            smap = smap[None]
+        return smap.mean(1).mean(1).mean(1)
     return _sums(img1, img2)[1] / img1.numel()
 
 
@@ -144,22 +153,131 @@ def fast_ssim(img1, img2):
 
 
 class FusedSSIMMap(torch.autograd.Function):
-    """utils/loss_utils.py:24-38: returns the per-pixel SSIM map; its gradient needs the map's upstream gradient per
-    pixel, which the fused kernels do not take (they differentiate the SUM of the map).  Kept for name parity: forward
-    only."""
+    """utils/loss_utils.py:24-38: the per-pixel SSIM map of [C,H,W] or [B,C,H,W] images, differentiable w.r.t. img1 under any
+    reduction of the map (gsr_ssim_map_backward takes the map's upstream gradient per pixel); img2 gets no gradient."""
 
     @staticmethod
     def forward(ctx, c1, c2, img1, img2):
-        return _SsimL1.apply(img1.detach(), img2, c1, c2, True)[1].view(img1.shape)
+        x, y = _chw(img1, "img1"), _chw(img2, "img2")
+        if img1.shape != img2.shape:
+            raise ValueError(f"image shapes differ: {tuple(img1.shape)} vs {tuple(img2.shape)}")
+        P, H, W = x.shape
+        dev = x.device
+        need_grad = ctx.needs_input_grad[2]
+        sums = torch.empty(2, dtype=torch.float32, device=dev)
+        smap = torch.empty((P, H, W), dtype=torch.float32, device=dev)
+        maps = torch.empty((3, P, H, W), dtype=torch.float32, device=dev) if need_grad else None
+        scratch = torch.empty(max(1, int(lib.gsr_ssim_l1_scratch_floats(P, H, W))), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.gsr_ssim_l1_forward(ptr(x), ptr(y), P, H, W, float(c1), float(c2), ptr(sums), ptr(scratch), ptr(smap),
+                                          ptr(maps[0]) if need_grad else None, ptr(maps[1]) if need_grad else None,
+                                          ptr(maps[2]) if need_grad else None, stream_ptr(dev)), "gsr_ssim_l1_forward")
+        if need_grad:
+            ctx.save_for_backward(x, y, maps)
+        return smap.view(img1.shape)
 
     @staticmethod
     def backward(ctx, opt_grad):
-        raise NotImplementedError("per-pixel SSIM-map gradients are not implemented; use ssim()/fast_ssim()/photometric_loss()")
+        x, y, maps = ctx.saved_tensors
+        P, H, W = x.shape
+        if P == 0 or H == 0 or W == 0:
+            return None, None, torch.zeros_like(opt_grad), None
+        g = f32c(opt_grad, "grad_map")
+        grad = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            check(lib.gsr_ssim_map_backward(ptr(x), ptr(y), P, H, W, ptr(g), ptr(maps[0]), ptr(maps[1]), ptr(maps[2]), ptr(grad),
+                                            stream_ptr(x.device)), "gsr_ssim_map_backward")
+        return None, None, grad.view(opt_grad.shape), None
 
 
-def photometric_loss(image, gt_image, lambda_dssim=0.2):
-    """train.py:167-173: (1 - lambda) * L1 + lambda * (1 - SSIM), one fused forward and one fused backward kernel."""
-    s = _sums(image, gt_image)
+def _hw_plane(t, name, H, W, dev):
+    """alpha / gt_alpha_mask as a float32 [H, W] plane on the image's device ([1, H, W] accepted; bool and uint8 masks converted)."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.device != dev:
+        raise ValueError(f"{name}: expected a tensor on {dev}, got {t.device if torch.is_tensor(t) else type(t).__name__}")
+    if t.dim() == 3 and t.size(0) == 1:
+        t = t[0]
+    if tuple(t.shape) != (H, W):
+        raise ValueError(f"{name}: expected ({H},{W}) or (1,{H},{W}), got {tuple(t.shape)}")
+    if t.dtype in (torch.bool, torch.uint8):
+        t = t.to(torch.float32)
+    return t
+
+
+class _CompositedSsimL1(torch.autograd.Function):
+    """sums = [sum |v - g|, sum ssim_map(v, g)] of the composites v = image * alpha + (1 - alpha) * background and
+    g = gt * mask + (1 - mask) * background (train.py:158-159), formed inside the kernels.  Gradients go to the image and to
+    alpha, each only when it requires one; the ground truth, the mask and the background get none."""
+
+    @staticmethod
+    def forward(ctx, image, alpha, gt, mask, background):
+        x, y = f32c(image, "image"), f32c(gt, "gt_image")
+        a = None if alpha is None else f32c(alpha, "alpha")
+        m = None if mask is None else f32c(mask, "gt_alpha_mask")
+        C, H, W = x.shape[-3:]
+        dev = x.device
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        sums = torch.empty(2, dtype=torch.float32, device=dev)
+        maps = torch.empty((3, C, H, W), dtype=torch.float32, device=dev) if need_grad else None
+        scratch = torch.empty(max(1, int(lib.gsr_photometric_scratch_floats(C, H, W))), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.gsr_photometric_forward(ptr(x), ptr(a), ptr(y), ptr(m), ptr(background), C, H, W, C1, C2, ptr(sums), ptr(scratch),
+                                              ptr(maps[0]) if need_grad else None, ptr(maps[1]) if need_grad else None,
+                                              ptr(maps[2]) if need_grad else None, stream_ptr(dev)), "gsr_photometric_forward")
+        ctx.save_for_backward(x, a, y, m, background, maps)
+        ctx.shape = (C, H, W)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g_sums):
+        x, a, y, m, background, maps = ctx.saved_tensors
+        C, H, W = ctx.shape
+        w = f32c(g_sums, "grad_sums")
+        g_img = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        g_alpha = torch.empty_like(a) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(x.device):
+            check(lib.gsr_photometric_backward(ptr(x), ptr(a), ptr(y), ptr(m), ptr(background), C, H, W, ptr(w), ptr(maps[0]), ptr(maps[1]),
+                                               ptr(maps[2]), ptr(g_img), ptr(g_alpha), stream_ptr(x.device)), "gsr_photometric_backward")
+        return g_img, g_alpha, None, None, None
+
+
+def _composited_sums(image, gt_image, alpha, gt_alpha_mask, background):
+    require_cuda(image, "image")
+    require_cuda(gt_image, "gt_image")
+    if image.dim() not in (3, 4) or (image.dim() == 4 and image.size(0) != 1):
+        raise ValueError(f"image: expected (C,H,W) or (1,C,H,W) with alpha / gt_alpha_mask / background, got {tuple(image.shape)}")
+    if image.shape != gt_image.shape:
+        raise ValueError(f"image shapes differ: {tuple(image.shape)} vs {tuple(gt_image.shape)}")
+    if background is None:
+        raise ValueError("alpha or gt_alpha_mask given without a background")
+    C, H, W = image.shape[-3:]
+    if C == 0 or H == 0 or W == 0:
+        raise ValueError(f"image: empty image {tuple(image.shape)}")
+    dev = image.device
+    a = _hw_plane(alpha, "alpha", H, W, dev)
+    m = _hw_plane(gt_alpha_mask, "gt_alpha_mask", H, W, dev)
+    if torch.is_tensor(background):
+        if background.device != dev:
+            raise ValueError(f"background: expected a tensor on {dev}, got {background.device}")
+        bg = background.detach().to(torch.float32).reshape(-1).contiguous()
+    else:
+        bg = torch.tensor([float(b) for b in background], dtype=torch.float32, device=dev)
+    if bg.numel() != C:
+        raise ValueError(f"background: expected {C} values, got {bg.numel()}")
+    return _CompositedSsimL1.apply(image, a, gt_image, m, bg)
+
+
+def photometric_loss(image, gt_image, lambda_dssim=0.2, *, alpha=None, gt_alpha_mask=None, background=None):
+    """train.py:167-173: (1 - lambda) * L1 + lambda * (1 - SSIM), one fused forward and one fused backward kernel.
+    With alpha [H,W] / gt_alpha_mask [H,W] (or [1,H,W]) and background [C] it is the loss of train.py:156-159, 167-174 on
+    image * alpha + (1 - alpha) * background and gt_image * mask + (1 - mask) * background, composited inside the same two kernels
+    (alpha is not clamped, as there); the gradient reaches `image` and `alpha`.  That form makes one explicit call: it does not
+    share its result with l1_loss() / ssim()."""
+    if alpha is None and gt_alpha_mask is None and background is None:
+        s = _sums(image, gt_image)
+    else:
+        s = _composited_sums(image, gt_image, alpha, gt_alpha_mask, background)
     n = image.numel()
     return (1.0 - lambda_dssim) * (s[0] / n) + lambda_dssim * (1.0 - s[1] / n)
 

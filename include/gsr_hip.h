@@ -473,6 +473,41 @@ size_t gsr_present_view_scratch_floats(int C, int H, int W, int flags);
 int gsr_present_view(const float* src, int C, int H, int W, int flags, const float* table, float* out_f32, uint8_t* out_u8,
                      float* scratch, size_t scratch_floats, void* stream);
 
+/* Loss front end of the train loop (train.py:154-174 of the reference) and the per-pixel SSIM-map gradient.  Added in ABI 102 without a
+ * version change, as the entries above.  All run on `stream` without host synchronisation and allocate nothing.
+ *
+ * gsr_photometric_forward / _backward: gsr_ssim_l1_forward / _backward on the two images as train.py:158-159 composites them when a view
+ *   carries a gt_alpha_mask, formed while the kernels stage their tiles:
+ *     v = rgb * alpha + (1 - alpha) * background[c]        when alpha is given (NOT clamped: train.py:159 does not; render.py does)
+ *     g = gt * gt_mask + (1 - gt_mask) * background[c]     when gt_mask is given
+ *   rgb, gt: float[C,H,W]; alpha, gt_mask: float[H,W], either may be NULL; background float[C], required with them.  The zero
+ *   padding of the window surrounds the composites: pixels outside the image contribute 0, not the background.
+ *   forward: sums float[2] <- { sum |v - g|, sum ssim_map(v, g) } (window, padding, C1, C2 as gsr_ssim_l1_forward); scratch
+ *     float[gsr_photometric_scratch_floats(C,H,W)]: per-block partials, added in a fixed order in double, so the sums are bitwise
+ *     reproducible; optional dm_dmu1, dm_dsigma1_sq, dm_dsigma12 float[C,H,W] (all three or none): planes saved for the backward.
+ *   backward: weights float[2] (device) = { dL/d sums[0], dL/d sums[1] }; with dL/dv = weights[0] * sign(v - g) + weights[1] *
+ *     (conv(dm_dmu1) + 2 v conv(dm_dsigma1_sq) + g conv(dm_dsigma12)):
+ *       dL_drgb   float[C,H,W] or NULL <- alpha * dL/dv (dL/dv without alpha)
+ *       dL_dalpha float[H,W] or NULL   <- sum_c (rgb[c] - background[c]) * dL/dv[c]; needs alpha.  No atomics: bitwise reproducible.
+ *     Every element of a non-NULL output is written.  gt, gt_mask and background get no gradient.
+ *   GSR_E_INVALID, before any device call: C, H or W <= 0 (or C, H / 32 > 65535), a NULL rgb, gt, sums, scratch, weights or (backward)
+ *   derivative plane, alpha or gt_mask without background, one or two of the three derivative planes, dL_dalpha without alpha.
+ *
+ * gsr_ssim_map_backward: the gradient of ANY reduction of the SSIM map (FusedSSIMMap.backward, utils/loss_utils.py:33-38):
+ *   dL_dimg1 float[planes,H,W] <- conv(G p0) + 2 img1 conv(G p1) + img2 conv(G p2), G = dL_dmap float[planes,H,W] and p0, p1, p2 the
+ *   three planes gsr_ssim_l1_forward left.  Planes are independent: a batch [B,C,H,W] is planes = B * C, in both directions. */
+size_t gsr_photometric_scratch_floats(int C, int H, int W);
+int gsr_photometric_forward(const float* rgb, const float* alpha, const float* gt, const float* gt_mask,
+                            const float* background, int C, int H, int W, float C1, float C2, float* sums, float* scratch,
+                            float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, void* stream);
+int gsr_photometric_backward(const float* rgb, const float* alpha, const float* gt, const float* gt_mask,
+                             const float* background, int C, int H, int W, const float* weights, const float* dm_dmu1,
+                             const float* dm_dsigma1_sq, const float* dm_dsigma12, float* dL_drgb, float* dL_dalpha,
+                             void* stream);
+int gsr_ssim_map_backward(const float* img1, const float* img2, int planes, int H, int W, const float* dL_dmap,
+                          const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12, float* dL_dimg1,
+                          void* stream);
+
 /* Normal-consistency term of the training loss (reference train.py:182-189): normal_error = (1 - sum_c rend_normal[c] *
  * surf_normal[c]) [* mask], loss = lambda * mean(normal_error).  rend_normal, surf_normal: [3,H,W]; mask: [H,W] (1,H,W) or NULL.
  * Forward: sum2[0] = sum over pixels of normal_error (sum2[1] = 0), scratch = gsr_normal_loss_scratch_floats() floats.
