@@ -408,6 +408,20 @@ class Workspace:
 
         self.cb = ALLOC_FN(_alloc)
 
+    def check(self, rc, what):
+        """check() for the forward call that was given this workspace's callback.  An exception the allocation raised (the caching
+        allocator's torch.OutOfMemoryError) comes first: the library answers the NULL it got with GSR_E_ALLOC, and the caller — a training
+        loop that catches the allocator's exception, as it can with the reference's resize callback — gets that very object, the library's
+        message as its context.  A GSR_E_ALLOC the callback did not cause is a GsrError like every other failure."""
+        if self.error is None:
+            return check(rc, what)
+        err, self.error = self.error, None      # (the exception's traceback holds this object through _alloc's frame: do not keep it in turn)
+        try:
+            check(rc, what)
+        except GsrError as lib_err:
+            raise err from lib_err
+        raise err
+
 
 def debug_fetch(variant, name, P, R, W, H, geom, binning, img, dtype, shape):
     """Parity-test helper: copy a named workspace array out (see gsr_debug_fetch in gsr_hip.h)."""

@@ -761,6 +761,7 @@ extern "C" int gsr_version(void) { return GSR_ABI_VERSION; }
 
 
 extern "C" int gsr_set_option(const char* name, int value) {
+	if (!name) { set_error("gsr_set_option: NULL option name"); return GSR_E_INVALID; }
 	if (std::string(name) == "cull") { g_opt_cull = value ? 1 : 0; return 0; }
 	if (std::string(name) == "dev") { g_opt_dev = value; return 0; }
 	if (std::string(name) == "emit_items") { g_opt_emit_items = (value == 1 || value == 2) ? value : 0; return 0; }   // Gaussians per thread of key emission; 0 = by size
@@ -808,6 +809,23 @@ extern "C" int gsr_mark_visible(int P, const float* means3D, const float* viewma
 extern "C" int gsr_debug_fetch(int variant, const char* name, int P, int R, int width, int height, const void* geom_buffer,
                                const void* binning_buffer, const void* image_buffer, void* dst, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
+	if ((variant != 0 && variant != 1) || !name || P < 0 || R < 0 || width <= 0 || height <= 0) {
+		set_error("gsr_debug_fetch: invalid argument (variant 0 or 1, a name, P >= 0, R >= 0, width, height)");
+		return GSR_E_INVALID;
+	}
+	{
+		// which workspace each array lives in (0 geometry, 1 binning, 2 image, -1 none), and whether this call copies anything out of it
+		static const struct { const char* name; int buf; } arrays[] = {
+			{"pairs", -1}, {"depths", 0}, {"means2D", 0}, {"tiles_touched", 0}, {"cull", 0}, {"point_offsets", 0}, {"clamped", 0}, {"rgb", 0}, {"geom4", 0},
+			{"transMat", 0}, {"cov3D", 0}, {"point_list", 1}, {"blend_mask", 1}, {"keys", 1}, {"ranges", 2}, {"final_T", 2}, {"n_contrib", 2}};
+		int buf = -2;
+		for (const auto& a : arrays) if (strcmp(a.name, name) == 0) buf = a.buf;
+		if (buf == -2 || (strcmp(name, "transMat") == 0 && variant != 0)) { set_error("gsr_debug_fetch: unknown array '%s'", name); return GSR_E_INVALID; }
+		const bool reads = buf == -1 || (buf == 0 && P > 0) || (buf == 1 && (R > 0 || strcmp(name, "blend_mask") == 0)) || buf == 2;
+		const void* src = buf == 0 ? geom_buffer : buf == 1 ? binning_buffer : buf == 2 ? image_buffer : dst;
+		// "keys" also reads the depths of the geometry buffer
+		if (reads && (!dst || !src || (strcmp(name, "keys") == 0 && !geom_buffer))) { set_error("gsr_debug_fetch: '%s' needs its workspace buffer and dst", name); return GSR_E_INVALID; }
+	}
 	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
 	const size_t HW = (size_t)width * height, tiles = (size_t)tiles_x * tiles_y;
 	const WorkspaceLayout& layout = variant == 0 ? SURFEL_LAYOUT : GAUSS_LAYOUT;

@@ -548,6 +548,8 @@ extern "C" int gsr_deferred_reflection_forward_keys(const float* normal_view, co
 		set_error("gsr_deferred_reflection_forward: invalid argument");
 		return GSR_E_INVALID;
 	}
+	// (texel ids and the sort keys are 32-bit, and 6*L*L itself is the key of a pixel without a footprint)
+	if ((size_t)6 * L * L >= 0xFFFFFFFFull) { set_error("gsr_deferred_reflection_forward: cubemap too large"); return GSR_E_INVALID; }
 	const size_t HW = (size_t)width * height;
 	StageTimer st_(GSR_STAGE_REFL_FWD, stream);
 	const unsigned grid = (unsigned)((HW + 255) / 256);
@@ -604,6 +606,12 @@ static auto with_refl_sort(int key_bits, bool small, F&& f) {
 	return f(RadixSort<1024, 8, 8>{});
 }
 static ReflScratch refl_scratch(uint32_t L, int width, int height) {
+	// a function of its three arguments alone, and a training loop asks for the same three at every call (twice per forward since the
+	// forward judges its scratch before it starts): the last answer of the thread is kept
+	thread_local uint32_t last_L = 0;
+	thread_local int last_w = 0, last_h = 0;
+	thread_local ReflScratch last;
+	if (last_L != 0 && L == last_L && width == last_w && height == last_h) return last;
 	ReflScratch r;
 	r.ntex = (size_t)6 * L * L;
 	r.n = (size_t)width * height;
@@ -617,6 +625,7 @@ static ReflScratch refl_scratch(uint32_t L, int width, int height) {
 	};
 	r.sort_bytes = std::max(need(false), need(true));
 	r.total_floats = (r.ntex + 2) * 4 + 8 * r.n + 3 * r.n + (r.sort_bytes + 3) / 4 + 128;   // + slack to align the sort temp
+	last = r; last_L = L; last_w = width; last_h = height;
 	return r;
 }
 extern "C" size_t gsr_deferred_reflection_scratch_floats(uint32_t L, int width, int height, int binned) {
@@ -743,14 +752,20 @@ int side_gate_wait(hipStream_t stream) {
 // forked in the backward no longer finished before that kernel took the chip (its second pass then waited 0.8 ms and the run combine ran
 // after the tile backward, beside — and at the expense of — the per-Gaussian backward).  The backward is told with keys_sorted = 1.
 // gated: arm the gate; not when no tile backward will consume it (nothing rendered), which would leave it for an unrelated one.
-int refl_sort_keys_early(uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async, bool gated,
-                         hipStream_t stream) {
-	ReflTail t(L, width, height, stream);
-	if (!t.carve(scratch, scratch_floats)) {
-		set_error("reflection backward (sorted footprints): scratch of %zu floats, 32-byte aligned, needed (gsr_deferred_reflection_scratch_floats(L, W, H, 1))",
-		          t.rs.total_floats);
+int refl_scratch_check(const char* entry, uint32_t L, int width, int height, const float* scratch, size_t scratch_floats) {
+	ReflTail t(L, width, height, nullptr);
+	if (!scratch || !t.carve(const_cast<float*>(scratch), scratch_floats)) {
+		set_error("%s: reflection backward (sorted footprints): scratch of %zu floats, 32-byte aligned, needed (gsr_deferred_reflection_scratch_floats(L, W, H, 1))",
+		          entry, t.rs.total_floats);
 		return GSR_E_INVALID;
 	}
+	return 0;
+}
+int refl_sort_keys_early(uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async, bool gated,
+                         hipStream_t stream) {
+	if (const int rc = refl_scratch_check("gsr_surfel_forward_refl", L, width, height, scratch, scratch_floats); rc < 0) return rc;
+	ReflTail t(L, width, height, stream);
+	t.carve(scratch, scratch_floats);
 	if (async) t.use_side_stream();
 	if (t.side) GSR_HIP_CHECK(t.fork(t.side->fork));
 	{
@@ -784,6 +799,10 @@ extern "C" int gsr_deferred_reflection_backward_keys(const float* normal_view, c
 		set_error("gsr_deferred_reflection_backward: invalid argument");
 		return GSR_E_INVALID;
 	}
+	if ((size_t)6 * L * L >= 0xFFFFFFFFull) { set_error("gsr_deferred_reflection_backward: cubemap too large"); return GSR_E_INVALID; }
+	// the texel staging at the head of the scratch and the interleaved cubemap are float4 arrays on every path
+	GSR_REQUIRE_ALIGNED16_IN("gsr_deferred_reflection_backward", scratch, "scratch");
+	GSR_REQUIRE_ALIGNED16_IN("gsr_deferred_reflection_backward", cubemap_rgba, "cubemap_rgba");
 	const size_t HW = (size_t)width * height;
 	ReflTail t(L, width, height, stream);
 	const size_t ntex = t.rs.ntex;
@@ -833,7 +852,7 @@ extern "C" int gsr_deferred_reflection_backward_keys(const float* normal_view, c
 	{
 		StageTimer st_(GSR_STAGE_REFL_BWD, stream);      // the pixel kernel; the texel-gradient tail is GSR_STAGE_REFL_BWD_TAIL
 		const unsigned egrid = (unsigned)((HW + ENTRIES_BS - 1) / ENTRIES_BS);
-		if (cubemap_rgba && ((uintptr_t)cubemap_rgba & 15) == 0)     // the texel-interleaved copy the forward made (same cubemap)
+		if (cubemap_rgba)     // the texel-interleaved copy the forward made (same cubemap)
 			deferred_refl_bwd_entries_kernel<true><<<egrid, ENTRIES_BS, 0, stream>>>(normal_view, base_color, refl_strength, cam, cubemap,
 			                                                                 reinterpret_cast<const float4*>(cubemap_rgba), fail_value, (int)L, width, height, g_final,
 			                                                                 g_refl_color, g_normal_world, g_normal_view, g_base, g_strength, t.fail_acc, t.staging,

@@ -716,6 +716,22 @@ gauss_preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means
 
 using namespace gsr;
 
+// The scene, camera and SH tests of variant G, made by the forward AND the backward so that the two directions refuse the same calls (the
+// backward's kernels read the same arrays, and walk an SH row of M coefficients by the same D).  `missing` is the text of the refusal of a NULL
+// pointer (the two directions word it differently).  P <= 0: nothing is read (a negative P is the size check's business).
+static int check_gauss_inputs(const char* entry, const char* missing, int P, int D, int M, const float* means3D, const float* shs,
+                              const float* colors_precomp, const float* normals, const float* refl_strengths, const float* opacities,
+                              const float* scales, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* cam_pos, const int* radii) {
+	if (P <= 0) return 0;
+	if (!means3D || !opacities || !normals || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii ||
+	    (!shs && !colors_precomp) || ((!scales || !rotations) && !cov3D_precomp)) {
+		set_error("%s: %s", entry, missing);
+		return GSR_E_INVALID;
+	}
+	return check_sh_input(entry, D, M, shs);
+}
+
 extern "C" int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M, const float* background, int width, int height,
                                  const float* means3D, const float* shs, const float* colors_precomp, const float* normals,
                                  const float* refl_strengths, const float* opacities, const float* scales, float scale_modifier,
@@ -735,12 +751,8 @@ extern "C" int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, in
 		if (out_invdepth) GSR_HIP_CHECK(hipMemsetAsync(out_invdepth, 0, HW * 4, stream));
 		return 0;
 	}
-	if (!means3D || !opacities || !normals || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii ||
-	    (!shs && !colors_precomp) || ((!scales || !rotations) && !cov3D_precomp)) {
-		set_error("gsr_gauss_forward: missing required input pointer");
-		return GSR_E_INVALID;
-	}
-	if (const int rc = check_sh_input("gsr_gauss_forward", D, M, shs); rc < 0) return rc;
+	if (const int rc = check_gauss_inputs("gsr_gauss_forward", "missing required input pointer", P, D, M, means3D, shs, colors_precomp, normals, refl_strengths,
+	                                      opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, radii); rc < 0) return rc;
 	const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
 	const int ntiles = tiles_x * tiles_y;
 	GeomState geom; ImageState img;
@@ -785,11 +797,14 @@ extern "C" int gsr_gauss_backward_accum(int P, int D, int M, int R, const float*
                                   const float* dL_invdepths, float* dL_dmean2D, float* dL_dmean2D_pixels, float* dL_dconic, float* dL_dopacity,
                                   float* dL_dcolor, float* dL_dnormals, float* dL_drefl_strengths, float* dL_dinvdepth, float* dL_dmean3D,
                                   float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing, int accumulate, int debug, void* stream_) {
-	(void)colors_precomp; (void)normals; (void)refl_strengths;
 	hipStream_t stream = (hipStream_t)stream_;
-	const bool missing = !geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dnormal_map || !dL_drefl_strength_map ||
+	// the scene as the forward got it: the same refusals (colors_precomp, normals and refl_strengths are not read here, but a call the
+	// forward would have refused has no buffers to hand to this one)
+	if (const int rc = check_gauss_inputs("gsr_gauss_backward", "missing required pointer", P, D, M, means3D, shs, colors_precomp, normals, refl_strengths,
+	                                      opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, radii); rc < 0) return rc;
+	const bool missing = !background || !geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dnormal_map || !dL_drefl_strength_map ||
 	    !dL_dmean2D_pixels || !dL_dopacity || (!shs && !dL_dcolor) || !dL_dnormals || !dL_drefl_strengths || !dL_dmean3D || (!scales && !dL_dcov3D) ||
-	    !dL_dscale || !dL_drot || (shs && !dL_dsh) || (dL_invdepths && !dL_dinvdepth) || !radii || !means3D || !opacities;
+	    !dL_dscale || !dL_drot || (shs && !dL_dsh) || (dL_invdepths && !dL_dinvdepth);
 	BackwardWorkspace w;
 	if (const int rc = backward_prologue("gsr_gauss_backward", __func__, GAUSS_LAYOUT, P, M, R, width, height, missing, shs, dL_dsh, dL_drot, dL_dconic, "dL_dconic",
 	                                     geom_buffer, binning_buffer, image_buffer, stream, &w); rc <= 0) return rc;

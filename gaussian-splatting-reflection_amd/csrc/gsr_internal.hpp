@@ -143,8 +143,8 @@ BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_temp_b
 int forward_workspace(gsr_alloc_fn alloc, void* alloc_user, const WorkspaceLayout& layout, size_t P, size_t HW, size_t tiles, GeomState* geom,
                       ImageState* img);
 
-// The check of the SH input every forward makes: degree 0..3 with (D+1)^2 <= M coefficients per row, and rows of a multiple of 16 bytes
-// 16-byte aligned (their float4 loads).  `entry` names the caller in the message.
+// The check of the SH input every forward AND backward makes (through its variant's check_*_inputs): degree 0..3 with (D+1)^2 <= M
+// coefficients per row, and rows of a multiple of 16 bytes 16-byte aligned (their float4 loads).  `entry` names the caller in the message.
 static inline int check_sh_input(const char* entry, int D, int M, const float* shs) {
 	if (D < 0 || D > 3 || (shs && (D + 1) * (D + 1) > M)) { set_error("%s: SH degree %d not supported with M=%d", entry, D, M); return GSR_E_INVALID; }
 	if (shs && ((M * 3) & 3) == 0 && misaligned16(shs)) {
@@ -171,9 +171,10 @@ static inline RasterCam make_cam(const float* view, const float* proj, const flo
 	return c;
 }
 
-// What both backward drivers do before their kernels: size check, P == 0 (returns 0: nothing to do), the variant's required-pointer test
-// (`missing_pointer`: the caller evaluates it, it only compares pointers), 16-byte alignment of what the per-Gaussian pass accesses as
-// float4 (`also_aligned`: one more such pointer of the variant, or NULL), the forward's buffers carved again, the accumulator zeroed.
+// What both backward drivers do before their kernels, after the variant's check_*_inputs (the scene, camera and SH tests the forward makes
+// too): size check, P == 0 (returns 0: nothing to do), the test of the pointers only the backward has (`missing_pointer`: the caller
+// evaluates it, it only compares pointers), 16-byte alignment of what the per-Gaussian pass stores as float4 (`also_aligned`: one more
+// such pointer of the variant, or NULL), the forward's buffers carved again, the accumulator zeroed.
 // `entry` / `func` name the operation / the driver in the messages.  Returns 1 to go on, < 0 on error.
 struct BackwardWorkspace { GeomState geom; ImageState img; BinningState bin; int tiles_x, ntiles; };
 static inline int backward_prologue(const char* entry, const char* func, const WorkspaceLayout& layout, int P, int M, int R, int width, int height,
@@ -183,8 +184,7 @@ static inline int backward_prologue(const char* entry, const char* func, const W
 	if (P < 0 || R < 0 || width <= 0 || height <= 0) { set_error("%s: invalid size", entry); return GSR_E_INVALID; }
 	if (P == 0) return 0;
 	if (missing_pointer) { set_error("%s: missing required pointer", entry); return GSR_E_INVALID; }
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16_IN(func, shs, "shs (rows of a multiple of 16 bytes)");
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16_IN(func, dL_dsh, "dL_dsh");
+	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16_IN(func, dL_dsh, "dL_dsh");   // (shs itself: check_sh_input)
 	GSR_REQUIRE_ALIGNED16_IN(func, dL_drot, "dL_drot");
 	GSR_REQUIRE_ALIGNED16_IN(func, also_aligned, also_what);
 	w->tiles_x = (width + 15) / 16;
@@ -217,6 +217,10 @@ int run_binning(gsr_alloc_fn alloc, void* alloc_user, int P, int tiles_x, int ti
 // next there; the training forward sorts the backward's footprint keys early (with async, on the side stream; `gated`: arm that gate —
 // only when a tile backward will follow, i.e. the forward rendered something).
 int side_gate_wait(hipStream_t stream);
+// 0 when `scratch` can hold the sorted-footprint path of an L cubemap over width x height pixels (32-byte aligned,
+// gsr_deferred_reflection_scratch_floats(L, W, H, 1) floats), else GSR_E_INVALID with the message set: host arithmetic only, so that the
+// training forward refuses a bad scratch before its first allocation instead of after its last kernel.
+int refl_scratch_check(const char* entry, uint32_t L, int width, int height, const float* scratch, size_t scratch_floats);
 int refl_sort_keys_early(uint32_t L, int width, int height, float* scratch, size_t scratch_floats, const uint32_t* sort_keys, int async, bool gated,
                          hipStream_t stream);
 

@@ -296,6 +296,7 @@ extern "C" int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, v
 		set_error("gsr_knn_mean_dist: scratch of %zu bytes, %zu needed (gsr_knn_scratch_bytes)", scratch_bytes, l.total);
 		return GSR_E_INVALID;
 	}
+	GSR_REQUIRE_ALIGNED16_IN("gsr_knn_mean_dist", scratch, "scratch");   // (it is carved into float4 arrays)
 	char* base = static_cast<char*>(scratch);
 	uint32_t* keys = reinterpret_cast<uint32_t*>(base + l.keys);
 	uint32_t* keys_sorted = reinterpret_cast<uint32_t*>(base + l.keys_sorted);

@@ -1202,7 +1202,8 @@ surfel_preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ mean
 using namespace gsr;
 
 // The checks both surfel forwards make, before their first allocation or device call.  `entry` names the caller in the message.
-static int check_refl_descriptor(const char* entry, const gsr_refl_forward* refl) {
+// width, height: of the image whose keys `scratch` will sort (the training forward; the eval forward takes neither keys nor scratch).
+static int check_refl_descriptor(const char* entry, const gsr_refl_forward* refl, int width, int height) {
 	if (!refl) return 0;
 	if (!refl->cam || !refl->cubemap || !refl->fail_value || refl->L == 0 || !refl->cubemap_rgba || ((uintptr_t)refl->cubemap_rgba & 15) != 0 ||
 	    !refl->out_final || !refl->out_refl_color || !refl->out_normal_world) {
@@ -1210,19 +1211,26 @@ static int check_refl_descriptor(const char* entry, const gsr_refl_forward* refl
 		return GSR_E_INVALID;
 	}
 	if ((size_t)6 * refl->L * refl->L >= 0xFFFFFFFFull) { set_error("%s: cubemap too large", entry); return GSR_E_INVALID; }
+	if (refl->scratch && !refl->sort_keys) { set_error("%s: refl->scratch is the place the sort keys are sorted into: it needs refl->sort_keys", entry); return GSR_E_INVALID; }
+	// (the early key sort runs behind the last kernel of the forward: its scratch is judged here, in front of the first)
+	if (refl->scratch) return refl_scratch_check(entry, refl->L, width, height, refl->scratch, refl->scratch_floats);
 	return 0;
 }
-static int check_surfel_inputs(const char* entry, int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp,
-                               const float* refl_strengths, const float* opacities, const float* scales, const float* rotations,
+// The scene, camera and SH tests of variant S, made by the forwards AND the backward so that the two directions refuse the same calls (the
+// backward's kernels read the same arrays, and walk an SH row of M coefficients by the same D).  `missing` is the text of the refusal of a NULL
+// pointer (the two directions word it differently).  P <= 0: nothing is read (a negative P is the size check's business).
+static int check_surfel_inputs(const char* entry, const char* missing, int P, int D, int M, const float* means3D, const float* shs,
+                               const float* colors_precomp, const float* refl_strengths, const float* scales, const float* rotations,
                                const float* transMat_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int* radii) {
-	if (P == 0) return 0;    // an empty scene reads none of them
-	if (!means3D || !opacities || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii || (!shs && !colors_precomp) ||
+	if (P <= 0) return 0;
+	if (!means3D || !refl_strengths || !viewmatrix || !projmatrix || !cam_pos || !radii || (!shs && !colors_precomp) ||
 	    ((!scales || !rotations) && !transMat_precomp)) {
-		set_error("%s: missing required input pointer", entry);
+		set_error("%s: %s", entry, missing);
 		return GSR_E_INVALID;
 	}
 	return check_sh_input(entry, D, M, shs);
 }
+#define SURFEL_FWD_MISSING "missing required input pointer"
 
 // The key sort of the reflection backward that the training forward starts when the descriptor hands it sort_keys and scratch; 0 otherwise.
 // R = num_rendered: the tile backward that consumes the sort's gate runs only when R > 0.
@@ -1320,9 +1328,9 @@ extern "C" int gsr_surfel_forward_refl(gsr_alloc_fn alloc, void* alloc_user, int
 		set_error("gsr_surfel_forward: invalid argument");
 		return GSR_E_INVALID;
 	}
-	if (P > 0 && !gaussian_weights) { set_error("gsr_surfel_forward: missing required input pointer"); return GSR_E_INVALID; }
-	if (const int rc = check_refl_descriptor("gsr_surfel_forward_refl", refl); rc < 0) return rc;
-	if (const int rc = check_surfel_inputs("gsr_surfel_forward", P, D, M, means3D, shs, colors_precomp, refl_strengths, opacities, scales, rotations,
+	if (P > 0 && (!gaussian_weights || !opacities)) { set_error("gsr_surfel_forward: " SURFEL_FWD_MISSING); return GSR_E_INVALID; }
+	if (const int rc = check_refl_descriptor("gsr_surfel_forward_refl", refl, width, height); rc < 0) return rc;
+	if (const int rc = check_surfel_inputs("gsr_surfel_forward", SURFEL_FWD_MISSING, P, D, M, means3D, shs, colors_precomp, refl_strengths, scales, rotations,
 	                                       transMat_precomp, viewmatrix, projmatrix, cam_pos, radii); rc < 0) return rc;
 	return surfel_forward<true>(alloc, alloc_user, P, D, M, background, width, height, means3D, env_scope_mask, shs, colors_precomp, refl_strengths,
 	                            opacities, scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
@@ -1357,8 +1365,9 @@ extern "C" int gsr_surfel_forward_eval(gsr_alloc_fn alloc, void* alloc_user, int
 		set_error("gsr_surfel_forward_eval: refl->sort_keys and refl->scratch must be NULL (the eval forward has no backward)");
 		return GSR_E_INVALID;
 	}
-	if (const int rc = check_refl_descriptor("gsr_surfel_forward_eval", refl); rc < 0) return rc;
-	if (const int rc = check_surfel_inputs("gsr_surfel_forward_eval", P, D, M, means3D, shs, colors_precomp, refl_strengths, opacities, scales, rotations,
+	if (const int rc = check_refl_descriptor("gsr_surfel_forward_eval", refl, width, height); rc < 0) return rc;
+	if (P > 0 && !opacities) { set_error("gsr_surfel_forward_eval: " SURFEL_FWD_MISSING); return GSR_E_INVALID; }
+	if (const int rc = check_surfel_inputs("gsr_surfel_forward_eval", SURFEL_FWD_MISSING, P, D, M, means3D, shs, colors_precomp, refl_strengths, scales, rotations,
 	                                       transMat_precomp, viewmatrix, projmatrix, cam_pos, radii); rc < 0) return rc;
 	return surfel_forward<false>(alloc, alloc_user, P, D, M, background, width, height, means3D, nullptr, shs, colors_precomp, refl_strengths, opacities,
 	                             scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
@@ -1373,11 +1382,15 @@ extern "C" int gsr_surfel_backward_ex(int P, int D, int M, int R, const float* b
                                    const float* dL_drefl_strength_map, float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity, float* dL_dcolor,
                                    float* dL_drefl_strengths, float* dL_dmean3D, float* dL_dtransMat, float* dL_dsh, float* dL_dscale,
                                    float* dL_drot, int accumulate, const float* dL_dnormal_extra, int debug, void* stream_) {
-	(void)colors_precomp; (void)refl_strengths; (void)scale_modifier; (void)transMat_precomp;
+	(void)scale_modifier;
 	hipStream_t stream = (hipStream_t)stream_;
-	const bool missing = !geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dothers || !dL_drefl_strength_map || !dL_dmean2D ||
-	    !dL_dopacity || !dL_drefl_strengths || !dL_dmean3D || !dL_dscale || !dL_drot || (!shs && !dL_dcolor) || (!scales && !dL_dtransMat) ||
-	    (shs && !dL_dsh) || !radii || !means3D;
+	// the scene as the forward got it: the same refusals (colors_precomp, refl_strengths and transMat_precomp are not read here, but a call
+	// the forward would have refused has no buffers to hand to this one)
+	if (const int rc = check_surfel_inputs("gsr_surfel_backward", "missing required pointer", P, D, M, means3D, shs, colors_precomp, refl_strengths, scales,
+	                                       rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos, radii); rc < 0) return rc;
+	const bool missing = !background || !geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !dL_dothers || !dL_drefl_strength_map ||
+	    !dL_dmean2D || !dL_dopacity || !dL_drefl_strengths || !dL_dmean3D || !dL_dscale || !dL_drot || (!shs && !dL_dcolor) || (!scales && !dL_dtransMat) ||
+	    (shs && !dL_dsh);
 	BackwardWorkspace w;
 	if (const int rc = backward_prologue("gsr_surfel_backward", __func__, SURFEL_LAYOUT, P, M, R, width, height, missing, shs, dL_dsh, dL_drot, nullptr, nullptr,
 	                                     geom_buffer, binning_buffer, image_buffer, stream, &w); rc <= 0) return rc;

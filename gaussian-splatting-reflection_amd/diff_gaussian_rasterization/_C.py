@@ -53,13 +53,11 @@ def rasterize_gaussians(background, means3D, colors, normals, refl_strengths, op
     ws = _gsr.Workspace(dev)
     M = _gsr.sh_coeffs(sh, empty_scene_counts=False)
     with torch.cuda.device(dev):
-        rendered = check(lib.gsr_gauss_forward(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(shc), ptr(col), ptr(nrm), ptr(refl),
+        rendered = ws.check(lib.gsr_gauss_forward(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(shc), ptr(col), ptr(nrm), ptr(refl),
                                                ptr(opa), ptr(sca), float(scale_modifier), ptr(rot), ptr(cov), ptr(vm), ptr(pm), ptr(cp),
                                                float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), ptr(out_color), ptr(out_normal_map),
                                                ptr(out_refl), ptr(out_invdepth), int(bool(antialiasing)), ptr(radii), int(bool(debug)),
                                                stream_ptr(dev)), "gsr_gauss_forward")
-    if ws.error is not None:
-        raise ws.error
     geomBuffer, binningBuffer, imgBuffer = ws.bufs
     return rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer, out_invdepth, out_normal_map, out_refl
 

@@ -93,14 +93,12 @@ def rasterize_gaussians(background, means3D, env_scope_mask, colors, refl_streng
     ws = _gsr.Workspace(dev)
     desc, refl_keep, extra = _refl_forward(refl, H, W, dev, keys=True)
     with torch.cuda.device(dev):
-        rendered = check(lib.gsr_surfel_forward_refl(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(mask), ptr(shc), ptr(col),
+        rendered = ws.check(lib.gsr_surfel_forward_refl(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(mask), ptr(shc), ptr(col),
                                                      ptr(rfl), ptr(opa), ptr(sca), float(scale_modifier), ptr(rot), ptr(tmp), ptr(vm), ptr(pm),
                                                      ptr(cp), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), ptr(out_color),
                                                      ptr(out_others), ptr(out_refl), ptr(radii), ptr(gaussian_weights), desc, int(bool(debug)),
                                                      stream_ptr(dev)),
                          "gsr_surfel_forward")
-    if ws.error is not None:
-        raise ws.error
     geomBuffer, binningBuffer, imgBuffer = ws.bufs
     return (rendered, out_color, out_others, radii, geomBuffer, binningBuffer, imgBuffer, out_refl, gaussian_weights) + extra
 
@@ -127,13 +125,11 @@ def rasterize_gaussians_eval(background, means3D, colors, refl_strengths, opacit
     ws = _gsr.Workspace(dev)
     desc, refl_keep, refl_out = _refl_forward(refl, H, W, dev, keys=False)
     with torch.cuda.device(dev):
-        rendered = check(lib.gsr_surfel_forward_eval(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(shc), ptr(col), ptr(rfl),
+        rendered = ws.check(lib.gsr_surfel_forward_eval(ws.cb, None, P, int(degree), M, ptr(bg), W, H, ptr(m3), ptr(shc), ptr(col), ptr(rfl),
                                                      ptr(opa), ptr(sca), float(scale_modifier), ptr(rot), ptr(tmp), ptr(vm), ptr(pm), ptr(cp),
                                                      float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), ptr(out_color), ptr(out_alpha),
                                                      ptr(out_normal), ptr(out_refl), ptr(radii), desc, int(bool(debug)), stream_ptr(dev)),
                          "gsr_surfel_forward_eval")
-    if ws.error is not None:
-        raise ws.error
     return (rendered, out_color, out_alpha, out_normal, out_refl, radii) + refl_out[:3]
 
 

@@ -22,9 +22,17 @@
  *
  * Alignment: tensors that are accessed with 128-bit loads/stores must be 16-byte aligned — shs
  * and dL_dsh when a row (3*M floats) is a multiple of 16 bytes (M = 4, 8, 12, 16), dL_drot,
- * and variant G's dL_dconic.  Fresh torch allocations always are; VIEWS into a packed buffer
+ * and variant G's dL_dconic; also cubemap_rgba and every `scratch` (the reflection backward's sorted path needs 32 bytes).  Fresh
+ * torch allocations always are; VIEWS into a packed buffer
  * (gradient sinks) are only if every slice starts at a multiple of 4 floats.  A misaligned
  * pointer is refused with GSR_E_INVALID (no kernel is launched).
+ *
+ * Refusals: every entry checks every argument before its first allocation request and its first device call, so a call that
+ * returns GSR_E_INVALID has done nothing.  tests/cabi_args.py holds the status of each argument (required, optional and under what
+ * condition, smallest size, alignment) as a table, and tests/test_cabi_refusals.py makes every bad call that follows from it.
+ * After GSR_E_ALLOC (gsr_alloc_fn returned NULL) the kernels the call had already enqueued still run to their end on `stream`, on the
+ * caller's inputs and on the buffers the callback did hand out: keep all of them alive until the stream has passed that point.
+ * Nothing else is kept: no side-stream work was started, and the next call behaves as if the failed one had not been made.
  */
 #ifndef GSR_HIP_H_
 #define GSR_HIP_H_
@@ -84,7 +92,13 @@ int gsr_surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M
  *   dL_dscale[P,2] dL_drot[P,4].
  *   Extension: dL_dnormal may be NULL, dL_dcolor may be NULL when shs is given, dL_dtransMat may be NULL when scales / rotations
  *   are given: those per-view gradients then belong to inputs the caller did not supply and are not written (the reference fills
- *   zero-initialised tensors for them, rasterize_points.cu:207-226, which its autograd wrapper then drops). */
+ *   zero-initialised tensors for them, rasterize_points.cu:207-226, which its autograd wrapper then drops).
+ *   Status of every argument (P > 0; P == 0 returns 0 and reads nothing).  The scene and the camera are the forward's, under the forward's
+ *   rules, and are refused alike: background, means3D, refl_strengths, viewmatrix, projmatrix, cam_pos, radii required; shs or
+ *   colors_precomp; scales AND rotations, or transMat_precomp; 0 <= D <= 3 and (D+1)^2 <= M with shs; shs 16-byte aligned as stated above.
+ *   Required: geom_buffer, image_buffer, binning_buffer when R > 0, dL_dpix, dL_dothers, dL_drefl_strength_map, dL_dmean2D, dL_dopacity,
+ *   dL_drefl_strengths, dL_dmean3D, dL_dscale, dL_drot (16-byte aligned), dL_dsh with shs (16-byte aligned when M is a multiple of 4),
+ *   dL_dcolor without shs, dL_dtransMat without scales.  Optional: dL_dnormal, and the two just named otherwise.  R >= 0, width, height > 0. */
 int gsr_surfel_backward(int P, int D, int M, int R, const float* background, int width, int height,
                         const float* means3D, const float* shs, const float* colors_precomp,
                         const float* refl_strengths, const float* scales, float scale_modifier, const float* rotations,
@@ -140,7 +154,9 @@ int gsr_surfel_backward_ex(int P, int D, int M, int R, const float* background, 
  * scratch (optional, with sort_keys): the buffer gsr_deferred_reflection_backward_keys will get.  The forward then also sorts the
  * (key, pixel) pairs into it — with async_sort on the side stream, where the sort runs beside whatever follows the forward on `stream`
  * (the loss; the start of the backward) while CUs are still free: 1024-thread sort workgroups cannot start on a chip the tile backward
- * has filled.  Hand the SAME scratch, untouched, to the backward with keys_sorted = 1; it must stay alive until gsr_side_join. */
+ * has filled.  Hand the SAME scratch, untouched, to the backward with keys_sorted = 1; it must stay alive until gsr_side_join.
+ * GSR_E_INVALID, before the first allocation: a NULL cam, cubemap, fail_value, cubemap_rgba or output, L == 0, 6*L*L >= 2^32 - 1, a
+ * misaligned cubemap_rgba, scratch without sort_keys, a scratch that is not 32-byte aligned or holds fewer than scratch_floats floats. */
 typedef struct {
 	const float* cam;
 	const float* cubemap;
@@ -196,7 +212,14 @@ int gsr_gauss_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, int M,
  *   dL_invdepths may be NULL (then dL_dinvdepth is not touched).  dL_dmean2D_pixels is what the
  *   reference hands to Python as grad_means2D (DGR rasterize_points.cu:263).  dL_dconic is float[P,4]
  *   (slots x,y,w used).  Outputs are fully written.  *   Extension: dL_dmean2D and dL_dconic (intermediates of the reference's backward that its binding never returns) may be NULL, dL_dcolor
- *   may be NULL when shs is given and dL_dcov3D when scales / rotations are given: not written then. */
+ *   may be NULL when shs is given and dL_dcov3D when scales / rotations are given: not written then.
+ *   Status of every argument (P > 0; P == 0 returns 0 and reads nothing).  The scene and the camera are the forward's, under the forward's
+ *   rules, and are refused alike: background, means3D, normals, refl_strengths, opacities, viewmatrix, projmatrix, cam_pos, radii required;
+ *   shs or colors_precomp; scales AND rotations, or cov3D_precomp; 0 <= D <= 3 and (D+1)^2 <= M with shs; shs 16-byte aligned as above.
+ *   Required: geom_buffer, image_buffer, binning_buffer when R > 0, dL_dpix, dL_dnormal_map, dL_drefl_strength_map, dL_dmean2D_pixels,
+ *   dL_dopacity, dL_dnormals, dL_drefl_strengths, dL_dmean3D, dL_dscale, dL_drot (16-byte aligned), dL_dsh with shs (16-byte aligned when
+ *   M is a multiple of 4), dL_dcolor without shs, dL_dcov3D without scales, dL_dinvdepth with dL_invdepths.  Optional: dL_invdepths,
+ *   dL_dmean2D, dL_dconic (16-byte aligned), and the conditional ones otherwise.  R >= 0, width, height > 0. */
 int gsr_gauss_backward(int P, int D, int M, int R, const float* background, int width, int height,
                        const float* means3D, const float* shs, const float* colors_precomp, const float* normals,
                        const float* refl_strengths, const float* opacities, const float* scales, float scale_modifier,
@@ -224,7 +247,8 @@ int gsr_gauss_backward_accum(int P, int D, int M, int R, const float* background
                        float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                        int antialiasing, int accumulate, int debug, void* stream);
 
-/* Replaces CudaRasterizer::Rasterizer::markVisible (DSR rasterizer.h:19-23, rasterizer_impl.cu:141-153). */
+/* Replaces CudaRasterizer::Rasterizer::markVisible (DSR rasterizer.h:19-23, rasterizer_impl.cu:141-153).  projmatrix is not read (the
+ * test is on view-space depth alone) and may be NULL; P == 0 does nothing. */
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      void* stream);
 
@@ -239,7 +263,10 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
  * entries of each 64-entry batch that blended: S [batch][quadrant][4x4 sub-block], G [quadrant][batch] in the first quarter; batch b of tile
  * t is batch index ranges[t][0] / 64 + t + b).
  * "pairs" u64[1] reads no workspace (the buffers may be NULL): the running number of (wave, list entry) pairs the forward tile kernels have
- * evaluated on the current device while the "dev" option had bit 2 set (gsr_set_option); it is never reset, so take differences. */
+ * evaluated on the current device while the "dev" option had bit 2 set (gsr_set_option); it is never reset, so take differences.
+ * GSR_E_INVALID: a variant other than 0 / 1, a NULL or unknown name, P < 0, R < 0, width or height <= 0, and a NULL dst or a NULL buffer
+ * of the workspace the named array lives in ("keys": binning and geometry) whenever the call copies something out of it (a per-Gaussian
+ * array with P == 0 and a per-instance array with R == 0 copy nothing). */
 int gsr_debug_fetch(int variant, const char* name, int P, int R, int width, int height, const void* geom_buffer,
                     const void* binning_buffer, const void* image_buffer, void* dst, void* stream);
 
@@ -274,8 +301,11 @@ int gsr_deferred_reflection_forward(const float* normal_view, const float* base_
  *   written.  scratch: caller-provided device buffer of `scratch_floats` floats (contents ignored).
  *   With at least gsr_deferred_reflection_scratch_floats(L, W, H, 0) = (6*L*L+1)*4 floats the texel gradients are added
  *   with float atomics from the pixel kernel; with gsr_deferred_reflection_scratch_floats(L, W, H, 1) floats
- *   (~44 bytes per pixel + the sort's temporary storage; 16-byte aligned) the sorted path runs instead: one footprint
- *   record per pixel, a radix sort by texel id, runs of equal texels summed in registers and LDS. */
+ *   (~44 bytes per pixel + the sort's temporary storage; 32-byte aligned) the sorted path runs instead: one footprint
+ *   record per pixel, a radix sort by texel id, runs of equal texels summed in registers and LDS.
+ *   GSR_E_INVALID (all forms, forward and backward): a NULL required pointer, L == 0, 6*L*L >= 2^32 - 1 (texel ids and sort keys are 32-bit),
+ *   width or height <= 0, a cubemap_rgba or scratch that is not 16-byte aligned, scratch_floats below the atomics size, keys_sorted without
+ *   sort_keys or without a scratch of the sorted path. */
 size_t gsr_deferred_reflection_scratch_floats(uint32_t L, int width, int height, int binned);
 int gsr_deferred_reflection_backward(const float* normal_view, const float* base_color, const float* refl_strength,
                                      const float* cam, const float* cubemap, const float* fail_value, uint32_t L,
@@ -353,7 +383,8 @@ int gsr_normal_world_backward(const float* normal_view, const float* cam, int wi
  *     partial sums, added up in a fixed order: the loss value is bitwise reproducible); optional ssim_map float[C,H,W];
  *     optional dm_dmu1, dm_dsigma1_sq, dm_dsigma12 float[C,H,W] (all three or none): planes saved for the backward.
  *   backward: weights float[2] (device) = { dL/d sums[0], dL/d sums[1] };
- *     dL_dimg1 float[C,H,W] <- weights[0] * sign(x - y) + weights[1] * d(sum ssim)/dx.  img2 gets no gradient. */
+ *     dL_dimg1 float[C,H,W] <- weights[0] * sign(x - y) + weights[1] * d(sum ssim)/dx.  img2 gets no gradient.
+ *   An empty image (a zero among C, H, W) is no error: the forward zeroes sums, the backward does nothing.  A negative size is refused. */
 size_t gsr_ssim_l1_scratch_floats(int C, int H, int W);
 int gsr_ssim_l1_forward(const float* img1, const float* img2, int C, int H, int W, float C1, float C2, float* sums,
                         float* scratch, float* ssim_map, float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12,
@@ -407,7 +438,7 @@ int gsr_split_children(int n_children, int scale_dims, int N, const int* parent,
  *   dx*dx + dy*dy + dz*dz (d = other - self, float32) from point i to the OTHER points (excluded by index: a duplicate is a
  *   neighbour at distance 0); a missing neighbour (P < 4) counts as FLT_MAX.  Exact search: the output does not depend on the
  *   input order.  points float[P,3] row-major, mean_dist float[P]; scratch: device memory of at least gsr_knn_scratch_bytes(P)
- *   bytes (the library allocates nothing).  Runs on `stream`, no host synchronisation.  0 <= P < 2^30; P = 0 does nothing.
+ *   bytes, 16-byte aligned (the library allocates nothing).  Runs on `stream`, no host synchronisation.  0 <= P < 2^30; P = 0 does nothing.
  * gsr_knn_scratch_bytes: the scratch size for P points (0 for P <= 0 or P >= 2^30).  Added in ABI 102 without a version change. */
 size_t gsr_knn_scratch_bytes(int P);
 int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, void* scratch, size_t scratch_bytes, void* stream);
@@ -571,7 +602,8 @@ int gsr_adam_step_range(float* param, const float* grad, float* exp_avg, float* 
  * forward tile kernels run as instances that count their evaluated pairs, see gsr_debug_fetch "pairs"; 4: with 2, those instances vote against
  * the whole block instead of its live pixels).  "emit_items" (default 0 =
  * chosen by the Gaussian count): 1 / 2 force the Gaussians per thread of key emission (tests).  "mailbox", "sort_driver" (default 1): 0 = the
- * round-2 read-back of num_rendered / the public rocPRIM sort entry points. */
+ * round-2 read-back of num_rendered / the public rocPRIM sort entry points.
+ * gsr_set_option refuses a NULL or unknown name; either array of gsr_profile_collect may be NULL (it is then not returned). */
 int gsr_set_option(const char* name, int value);
 int gsr_profile_enable(int on);
 int gsr_profile_collect(float* ms_out /* [GSR_STAGE_COUNT] */, int* launches_out /* [GSR_STAGE_COUNT] */);
