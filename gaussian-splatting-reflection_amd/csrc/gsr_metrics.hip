@@ -74,7 +74,7 @@ image_metrics_kernel(const float* __restrict__ img, const float* __restrict__ gt
 			const float d = v - g;
 			sse += d * d;
 			sad += fabsf(d);
-			ssim_sum += ssim_value(col, r, win, C1, C2);
+			ssim_sum += ssim_row(col, r, win, C1, C2).sv;
 			const size_t o = plane + (size_t)gy * W + gx;
 			// a presented value is k / 255 rounded once: times 255 it is within 2^-15 of k, so the truncation gives k back
 			if (img_u8) img_u8[o] = (uint8_t)(unsigned int)(v * 255.0f + 0.5f);
@@ -155,9 +155,7 @@ using namespace gsr;
 
 #define NORMAL_MAE_BLOCKS 1024
 
-static size_t image_metrics_blocks(int C, int H, int W) {
-	return (size_t)C * ((H + SSIM_T - 1) / SSIM_T) * ((W + SSIM_T - 1) / SSIM_T);
-}
+static size_t image_metrics_blocks(int C, int H, int W) { return (size_t)C * ssim_tiles(H) * ssim_tiles(W); }
 
 extern "C" size_t gsr_image_metrics_scratch_floats(int C, int H, int W) {
 	if (C <= 0 || H <= 0 || W <= 0) return 0;
@@ -169,7 +167,7 @@ extern "C" int gsr_image_metrics(const float* img, const float* gt, int C, int H
                                  void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
 	if (C <= 0 || H <= 0 || W <= 0) { set_error("gsr_image_metrics: invalid size C = %d, H = %d, W = %d", C, H, W); return GSR_E_INVALID; }
-	if (C > 65535 || (H + SSIM_T - 1) / SSIM_T > 65535) { set_error("gsr_image_metrics: C and H / 32 are grid dimensions, at most 65535"); return GSR_E_INVALID; }
+	if (C > 65535 || ssim_tiles(H) > 65535) { set_error("gsr_image_metrics: C and H / 32 are grid dimensions, at most 65535"); return GSR_E_INVALID; }
 	if (!img || !gt || !row) { set_error("gsr_image_metrics: NULL image or table row"); return GSR_E_INVALID; }
 	if (flags & ~(GSR_PRESENT_CLAMP | GSR_PRESENT_QUANT8)) { set_error("gsr_image_metrics: unknown presentation flags %d", flags); return GSR_E_INVALID; }
 	if ((img_u8 || gt_u8) && !(flags & GSR_PRESENT_QUANT8)) {
@@ -184,10 +182,9 @@ extern "C" int gsr_image_metrics(const float* img, const float* gt, int C, int H
 		return GSR_E_INVALID;
 	}
 	GSR_REQUIRE_ALIGNED16_IN("gsr_image_metrics", scratch, "scratch");
-	static const SsimWindow win = make_window();
 	const Presentation pr = {alpha, gt_mask, background, (flags & GSR_PRESENT_CLAMP) != 0, (flags & GSR_PRESENT_QUANT8) != 0};
-	dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C);
-	image_metrics_kernel<<<grid, 256, 0, stream>>>(img, gt, H, W, win, (float)(0.01 * 0.01), (float)(0.03 * 0.03), pr, (float4*)scratch, img_u8, gt_u8);
+	dim3 grid(ssim_tiles(W), ssim_tiles(H), C);
+	image_metrics_kernel<<<grid, 256, 0, stream>>>(img, gt, H, W, ssim_window(), (float)(0.01 * 0.01), (float)(0.03 * 0.03), pr, (float4*)scratch, img_u8, gt_u8);
 	metrics_reduce_kernel<<<1, 256, 0, stream>>>((const float4*)scratch, blocks, (double)C * H * W, row);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;

@@ -1,10 +1,7 @@
-// The pieces of the 11x11 Gaussian-window SSIM that the training loss (gsr_train.hip) and the evaluation metrics
-// (gsr_metrics.hip) share: the window, the 32x32 output tile with its 42x42 zero-padded halo in LDS, the halo loader and
-// the column window of the vertical pass.  Every function is inlined into the kernel that calls it.
-// ssim_l1_fwd_kernel keeps its own text of the two register-blocked passes (ssim_moments_hpass, ssim_load_columns<5> and
-// ssim_value below restate them for the metrics kernel): calling them from there moves its instruction stream, by a few
-// instructions out of 1546, and that kernel's timing is part of the train step's record; likewise ssim_load_tiles is not
-// written on top of ssim_stage_tiles.  tests/isa_digest.py shows the training kernels unchanged by this header.
+// The 11x11 Gaussian-window SSIM, written once for the loss kernels (gsr_loss.hip) and the evaluation metrics (gsr_metrics.hip):
+// the window, the 32x32 output tile with its 42x42 zero-padded halo in LDS, the halo loader, the two register-blocked forward
+// passes with the evaluation of one output row, the two adjoint passes of the backwards, and the fixed-order reduction of the
+// blocks' partial pairs.  Every device function is inlined into the kernel that calls it.
 #pragma once
 #include <cmath>
 #include "gsr_internal.hpp"
@@ -29,6 +26,13 @@ static SsimWindow make_window() {
 	for (int i = 0; i < 11; i++) w.g[i] /= sum;
 	return w;
 }
+// the window, made once per process
+inline const SsimWindow& ssim_window() {
+	static const SsimWindow win = make_window();
+	return win;
+}
+// tiles along an image side of n pixels
+inline int ssim_tiles(int n) { return (n + SSIM_T - 1) / SSIM_T; }
 
 #ifdef __HIPCC__
 // Stage the zero-padded halo tiles of NS planes into LDS.  `fetch(in, o, t)` gives the NS values of the pixel at offset o of
@@ -64,26 +68,10 @@ __device__ __forceinline__ void ssim_stage_tiles(Fetch fetch, int H, int W, int 
 // the planes as they are in memory
 template <int NP>
 __device__ __forceinline__ void ssim_load_tiles(const float* const (&src)[NP], int H, int W, int x0, int y0, float (*const (&dst)[NP])[SSIM_HALO + 1]) {
-	float v[NP][SSIM_LOADS];
+	ssim_stage_tiles<NP>([&](bool in, size_t o, float (&t)[NP]) {
 #pragma unroll
-	for (int j = 0; j < SSIM_LOADS; j++) {
-		const int i = threadIdx.x + 256 * j;
-		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
-		const int gx = x0 + lx - SSIM_R, gy = y0 + ly - SSIM_R;
-		const bool in = i < SSIM_HALO * SSIM_HALO && gx >= 0 && gx < W && gy >= 0 && gy < H;
-		const size_t o = in ? (size_t)gy * W + gx : 0;
-#pragma unroll
-		for (int p = 0; p < NP; p++) v[p][j] = in ? src[p][o] : 0.f;
-	}
-#pragma unroll
-	for (int j = 0; j < SSIM_LOADS; j++) {
-		const int i = threadIdx.x + 256 * j;
-		const int ly = i / SSIM_HALO, lx = i - ly * SSIM_HALO;
-		if (i < SSIM_HALO * SSIM_HALO) {
-#pragma unroll
-			for (int p = 0; p < NP; p++) dst[p][ly][lx] = v[p][j];
-		}
-	}
+		for (int p = 0; p < NP; p++) t[p] = in ? src[p][o] : 0.f;
+	}, H, W, x0, y0, dst);
 }
 
 // Horizontal pass of the five moments: 42 rows x (32 / 4) strips.  A work item produces SSIM_B neighbouring outputs from one
@@ -118,8 +106,16 @@ __device__ __forceinline__ void ssim_load_columns(const float (&hs)[NM][SSIM_HAL
 #pragma unroll
 		for (int k = 0; k < SSIM_B + 10; k++) col[m][k] = hs[m][tq * SSIM_B + k][tx];
 }
-// ... and the SSIM value of its row r (utils/loss_utils.py:75-92): A B / (Cc D)
-__device__ __forceinline__ float ssim_value(const float (&col)[5][SSIM_B + 10], int r, const SsimWindow& win, float C1, float C2) {
+// ... and row r of it (utils/loss_utils.py:75-92): the eleven taps of every moment, then ssim = A B / (Cc D).  The three derivatives
+// are those of the SSIM value with mu1, E[x^2], E[xy] as the independent conv outputs of image 1 (sigma1^2 = E[x^2] - mu1^2,
+// sigma12 = E[xy] - mu1 mu2); a kernel that does not ask for them does not compute them.
+struct SsimRow {
+	float mu1, mu2, A, B, Cc, D, inv, sv;
+	__device__ __forceinline__ float dm_dmu1() const { return 2.f * mu2 * (B - A) * inv - 2.f * mu1 * sv * (D - Cc) * inv; }
+	__device__ __forceinline__ float dm_dsigma1_sq() const { return -sv / D; }
+	__device__ __forceinline__ float dm_dsigma12() const { return 2.f * A * inv; }
+};
+__device__ __forceinline__ SsimRow ssim_row(const float (&col)[5][SSIM_B + 10], int r, const SsimWindow& win, float C1, float C2) {
 	float mu1 = 0, mu2 = 0, e11 = 0, e22 = 0, e12 = 0;
 #pragma unroll
 	for (int k = 0; k < 11; k++) {
@@ -131,7 +127,55 @@ __device__ __forceinline__ float ssim_value(const float (&col)[5][SSIM_B + 10], 
 	const float sigma1_sq = e11 - mu1_sq, sigma2_sq = e22 - mu2_sq, sigma12 = e12 - mu12;
 	const float A = 2.f * mu12 + C1, B = 2.f * sigma12 + C2, Cc = mu1_sq + mu2_sq + C1, D = sigma1_sq + sigma2_sq + C2;
 	const float inv = 1.0f / (Cc * D);
-	return A * B * inv;
+	return {mu1, mu2, A, B, Cc, D, inv, A * B * inv};
+}
+
+// The adjoint convolutions of the backwards run on three staged planes (the window is symmetric, so the adjoint of the zero-padded
+// correlation is the same correlation of the zero-padded planes): the horizontal pass into hs ...
+__device__ __forceinline__ void adjoint_hpass(const float (&t0)[SSIM_HALO][SSIM_HALO + 1], const float (&t1)[SSIM_HALO][SSIM_HALO + 1],
+                                              const float (&t2)[SSIM_HALO][SSIM_HALO + 1], float (&hs)[3][SSIM_HALO][SSIM_T + 1], const SsimWindow& win) {
+	for (int i = threadIdx.x; i < SSIM_HALO * (SSIM_T / SSIM_B); i += 256) {
+		const int ly = i % SSIM_HALO, lx = (i / SSIM_HALO) * SSIM_B;   // lanes run down the rows, as in ssim_moments_hpass
+		float v0[SSIM_B + 10], v1[SSIM_B + 10], v2[SSIM_B + 10];
+#pragma unroll
+		for (int k = 0; k < SSIM_B + 10; k++) { v0[k] = t0[ly][lx + k]; v1[k] = t1[ly][lx + k]; v2[k] = t2[ly][lx + k]; }
+#pragma unroll
+		for (int c = 0; c < SSIM_B; c++) {
+			float s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+			for (int k = 0; k < 11; k++) {
+				const float w = win.g[k];
+				s0 += w * v0[c + k]; s1 += w * v1[c + k]; s2 += w * v2[c + k];
+			}
+			hs[0][ly][lx + c] = s0; hs[1][ly][lx + c] = s1; hs[2][ly][lx + c] = s2;
+		}
+	}
+}
+// ... and the vertical pass of row r of a thread's column window, combined at the pixel: c0 + 2 x c1 + y c2
+__device__ __forceinline__ float adjoint_value(const float (&col)[3][SSIM_B + 10], int r, const SsimWindow& win, float x, float y) {
+	float c0 = 0, c1 = 0, c2 = 0;
+#pragma unroll
+	for (int k = 0; k < 11; k++) {
+		const float w = win.g[k];
+		c0 += w * col[0][r + k]; c1 += w * col[1][r + k]; c2 += w * col[2][r + k];
+	}
+	return c0 + 2.f * x * c1 + y * c2;
+}
+
+// Second stage of every sum of block partial pairs (the losses' sum |x - y| and sum ssim, the normal loss's sum): one workgroup,
+// double accumulation, fixed order -> the sums are bitwise reproducible.  (Thousands of blocks adding into ONE address serialise
+// at the memory side: measured 0.32 ms for the 1080p loss with atomics, see DESIGN.md.)
+static __global__ void __launch_bounds__(256) pair_reduce_kernel(const float* __restrict__ partials, size_t nblocks, float* __restrict__ sums) {
+	__shared__ double red[2][256];
+	double a = 0.0, b = 0.0;
+	for (size_t i = threadIdx.x; i < nblocks; i += 256) { a += (double)partials[2 * i]; b += (double)partials[2 * i + 1]; }
+	red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
+	__syncthreads();
+	for (int s = 128; s > 0; s >>= 1) {
+		if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) { sums[0] = (float)red[0][0]; sums[1] = (float)red[1][0]; }
 }
 #endif
 

@@ -32,26 +32,32 @@ def _chw(img, name):
     return f32c(img, name)
 
 
+def _ssim_l1_forward(img1, img2, c1, c2, want_map, need_grad):
+    """One gsr_ssim_l1_forward call on the images as planes: (x, y, sums, smap or None, maps or None), smap the per-pixel SSIM map
+    [P,H,W] and maps the three derivative planes [3,P,H,W] that both backward entries take."""
+    x, y = _chw(img1, "img1"), _chw(img2, "img2")
+    if x.shape != y.shape:
+        raise ValueError(f"image shapes differ: {tuple(x.shape)} vs {tuple(y.shape)}")
+    P, H, W = x.shape
+    dev = x.device
+    sums = torch.empty(2, dtype=torch.float32, device=dev)
+    smap = torch.empty((P, H, W), dtype=torch.float32, device=dev) if want_map else None
+    maps = torch.empty((3, P, H, W), dtype=torch.float32, device=dev) if need_grad else None
+    scratch = torch.empty(max(1, int(lib.gsr_ssim_l1_scratch_floats(P, H, W))), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.gsr_ssim_l1_forward(ptr(x), ptr(y), P, H, W, float(c1), float(c2), ptr(sums), ptr(scratch), ptr(smap),
+                                      ptr(maps[0]) if need_grad else None, ptr(maps[1]) if need_grad else None,
+                                      ptr(maps[2]) if need_grad else None, stream_ptr(dev)), "gsr_ssim_l1_forward")
+    return x, y, sums, smap, maps
+
+
 class _SsimL1(torch.autograd.Function):
     """sums = [sum |img1 - img2|, sum ssim_map]; gradient w.r.t. img1 only (the ground truth gets none, as in
     FusedSSIMMap.backward, utils/loss_utils.py:33-38)."""
 
     @staticmethod
     def forward(ctx, img1, img2, c1, c2, want_map):
-        x, y = _chw(img1, "img1"), _chw(img2, "img2")
-        if x.shape != y.shape:
-            raise ValueError(f"image shapes differ: {tuple(x.shape)} vs {tuple(y.shape)}")
-        C, H, W = x.shape
-        dev = x.device
-        sums = torch.empty(2, dtype=torch.float32, device=dev)
-        need_grad = img1.requires_grad
-        maps = torch.empty((3, C, H, W), dtype=torch.float32, device=dev) if need_grad else None
-        smap = torch.empty((C, H, W), dtype=torch.float32, device=dev) if want_map else None
-        scratch = torch.empty(max(1, int(lib.gsr_ssim_l1_scratch_floats(C, H, W))), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_ssim_l1_forward(ptr(x), ptr(y), C, H, W, float(c1), float(c2), ptr(sums), ptr(scratch), ptr(smap),
-                                          ptr(maps[0]) if need_grad else None, ptr(maps[1]) if need_grad else None,
-                                          ptr(maps[2]) if need_grad else None, stream_ptr(dev)), "gsr_ssim_l1_forward")
+        x, y, sums, smap, maps = _ssim_l1_forward(img1, img2, c1, c2, want_map, img1.requires_grad)
         ctx.save_for_backward(x, y, maps)
         # kept beside the saved tensors: l1_loss() and ssim() share this node (see _sums), and a caller who runs two backward passes —
         # l1.backward(retain_graph=True) for the render graph, then ssim.backward(), two graphs in the reference — reaches it twice, the
@@ -64,7 +70,7 @@ class _SsimL1(torch.autograd.Function):
         if want_map:
             ctx.mark_non_differentiable(smap)
             return sums, smap
-        return sums, torch.empty(0, device=dev)
+        return sums, torch.empty(0, device=x.device)
 
     @staticmethod
     def backward(ctx, g_sums, _):
@@ -158,20 +164,10 @@ class FusedSSIMMap(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, c1, c2, img1, img2):
-        x, y = _chw(img1, "img1"), _chw(img2, "img2")
-        if img1.shape != img2.shape:
+        if img1.shape != img2.shape:      # (stricter than the planes' shapes: the map is returned in img1's shape)
             raise ValueError(f"image shapes differ: {tuple(img1.shape)} vs {tuple(img2.shape)}")
-        P, H, W = x.shape
-        dev = x.device
         need_grad = ctx.needs_input_grad[2]
-        sums = torch.empty(2, dtype=torch.float32, device=dev)
-        smap = torch.empty((P, H, W), dtype=torch.float32, device=dev)
-        maps = torch.empty((3, P, H, W), dtype=torch.float32, device=dev) if need_grad else None
-        scratch = torch.empty(max(1, int(lib.gsr_ssim_l1_scratch_floats(P, H, W))), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_ssim_l1_forward(ptr(x), ptr(y), P, H, W, float(c1), float(c2), ptr(sums), ptr(scratch), ptr(smap),
-                                          ptr(maps[0]) if need_grad else None, ptr(maps[1]) if need_grad else None,
-                                          ptr(maps[2]) if need_grad else None, stream_ptr(dev)), "gsr_ssim_l1_forward")
+        x, y, _, smap, maps = _ssim_l1_forward(img1, img2, c1, c2, True, need_grad)
         if need_grad:
             ctx.save_for_backward(x, y, maps)
         return smap.view(img1.shape)

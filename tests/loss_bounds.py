@@ -1,5 +1,5 @@
 """Float64 references with per-element error bounds for the training-step kernels around the rasterizer: the fused SSIM + L1
-loss, the surface pass and the flat Adam step (csrc/gsr_train.hip, csrc/gsr_surface.hip), plus the seeded inputs their
+loss, the surface pass and the flat Adam step (csrc/gsr_loss.hip, csrc/gsr_surface.hip, csrc/gsr_train.hip), plus the seeded inputs their
 tests use.
 
 The reference value of each output comes from the float64 oracle (oracle/oracle_train.cpp), evaluated on the same float32

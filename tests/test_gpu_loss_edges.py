@@ -1,4 +1,4 @@
-"""Fused SSIM + L1 (csrc/gsr_train.hip) against the float64 oracle per element, within the error bounds of
+"""Fused SSIM + L1 (csrc/gsr_loss.hip) against the float64 oracle per element, within the error bounds of
 tests/loss_bounds.py, at the shapes and contents where a 32 x 32 tile with a 42 x 42 halo goes wrong: every tile and halo
 offset, thin images, full size, cancelling bright flat regions, HDR values, exact ties, impulses at tile edges.  Also the
 autograd wrapper (utils/loss_utils.py): in-place changes between forward and backward raise, supported call sequences keep

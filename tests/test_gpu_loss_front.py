@@ -46,7 +46,8 @@ def gpu_front(case, w_l1=W_L1, w_ssim=W_SSIM, want_rgb=True, want_alpha=None):
                                        _p(planes[2]), _p(drgb), _p(dalpha), s), "gsr_photometric_backward")
     torch.cuda.synchronize()
     assert not torch.isnan(planes).any()
-    out = dict(sums=sums.cpu().numpy(), drgb=None if drgb is None else drgb.cpu().numpy(), dalpha=None if dalpha is None else dalpha.cpu().numpy())
+    out = dict(sums=sums.cpu().numpy(), drgb=None if drgb is None else drgb.cpu().numpy(), dalpha=None if dalpha is None else dalpha.cpu().numpy(),
+               planes=planes.cpu().numpy())
     out["l1"], out["ssim"] = float(out["sums"][0]), float(out["sums"][1])
     return out
 
@@ -127,6 +128,34 @@ def test_repeated_calls_and_optional_outputs_are_bitwise_identical():
     only_alpha = gpu_front(case, want_rgb=False)
     assert only_rgb["dalpha"] is None and _same_bits(only_rgb["drgb"], a["drgb"])
     assert only_alpha["drgb"] is None and _same_bits(only_alpha["dalpha"], a["dalpha"])
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1), (1, 32, 32), (3, 33, 31), (3, 43, 65), (5, 33, 31)])
+def test_call_without_planes_is_bitwise_the_training_loss(shape):
+    """alpha, gt_mask and background NULL: the forward is the kernel gsr_ssim_l1_forward runs, so both sums and the three derivative
+    planes are bit for bit that entry's (all padding; exactly one tile; one pixel into a second tile row; a halo that reaches a third
+    tile; five channels).  The two backwards are different kernels: each, on its own planes, is held to the float64 bounds."""
+    from _gsr import check, lib, stream_ptr
+    C, H, W = shape
+    case = FB.front_case("hdr", shape, 3, (False, False))
+    ref, bnd = FB.front_reference(case, W_L1, W_SSIM)
+    front = gpu_front(case)
+    x, y = _dev(case["rgb"]), _dev(case["gt"])
+    sums = torch.full((2,), NAN, device="cuda")
+    scratch = torch.full((int(lib.gsr_ssim_l1_scratch_floats(C, H, W)),), NAN, device="cuda")
+    planes = torch.full((3, C, H, W), NAN, device="cuda")
+    grad = torch.full((C, H, W), NAN, device="cuda")
+    w = torch.tensor([W_L1, W_SSIM], dtype=torch.float32, device="cuda")
+    s = stream_ptr(x.device)
+    check(lib.gsr_ssim_l1_forward(_p(x), _p(y), C, H, W, LB.C1, LB.C2, _p(sums), _p(scratch), None, _p(planes[0]), _p(planes[1]), _p(planes[2]), s),
+          "gsr_ssim_l1_forward")
+    check(lib.gsr_ssim_l1_backward(_p(x), _p(y), C, H, W, _p(w), _p(planes[0]), _p(planes[1]), _p(planes[2]), _p(grad), s), "gsr_ssim_l1_backward")
+    torch.cuda.synchronize()
+    train = dict(sums=sums.cpu().numpy(), planes=planes.cpu().numpy(), drgb=grad.cpu().numpy())
+    assert _same_bits(front["sums"], train["sums"]) and _same_bits(front["planes"], train["planes"])
+    train["l1"], train["ssim"] = float(train["sums"][0]), float(train["sums"][1])
+    FB.check_front(front, ref, bnd, f"photometric {shape}")
+    FB.check_front(train, ref, bnd, f"ssim_l1 {shape}")
 
 
 # ----------------------------------------------------------------------------------------------------- autograd wrapper

@@ -85,7 +85,7 @@ def _loss_case(shape):
 
 @pytest.mark.parametrize("shape", LOSS_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_photometric_ssim_and_l1_losses(shape):
-    """Sums reduced in a fixed order (csrc/gsr_train.hip): values and image gradient the same bits under every pattern, and within the
+    """Sums reduced in a fixed order (csrc/gsr_loss.hip): values and image gradient the same bits under every pattern, and within the
     float64 bounds of loss_bounds.py.  The scalars are sum / n and a two-term combination in float32: two more roundings each."""
     from utils.loss_utils import clear_cache, l1_loss, photometric_loss, ssim
     x, y, (ref, bnd), _ = _loss_case(shape)
