@@ -37,6 +37,15 @@ class AdamSegment(ctypes.Structure):
                 ("split", c_uint32)]
 
 
+GSR_ACT_NONE, GSR_ACT_SIGMOID, GSR_ACT_EXP, GSR_ACT_NORMALIZE4, GSR_ACT_FROZEN = 0, 1, 2, 3, 0x100     # include/gsr_hip_train.h
+
+
+class ActSegment(ctypes.Structure):
+    """gsr_act_segment of include/gsr_hip_train.h."""
+    _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("lr", c_float), ("lr2", c_float), ("period", c_uint32),
+                ("split", c_uint32), ("kind", c_uint32), ("act_begin", ctypes.c_uint64)]
+
+
 class ReflForward(ctypes.Structure):
     """gsr_refl_forward of include/gsr_hip.h."""
     _fields_ = [("cam", c_void_p), ("cubemap", c_void_p), ("fail_value", c_void_p), ("L", c_uint32), ("cubemap_rgba", c_void_p),
@@ -181,6 +190,14 @@ def _load():
         lib.gsr_photometric_backward.argtypes = [P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P]
         lib.gsr_ssim_map_backward.restype = c_int
         lib.gsr_ssim_map_backward.argtypes = [P, P, c_int, c_int, c_int, P, P, P, P, P, P]
+    if hasattr(lib, "gsr_adam_act_step"):
+        # (likewise, declared in include/gsr_hip_train.h: a library built before the raw-parameter step lacks these two;
+        # gsr_train.RawTrainState then refuses to be built)
+        lib.gsr_adam_act_step.restype = c_int
+        lib.gsr_adam_act_step.argtypes = [P, P, P, P, P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ActSegment), c_int, c_float, c_float,
+                                          c_float, c_int, ctypes.c_uint64, ctypes.c_uint64, P]
+        lib.gsr_activate.restype = c_int
+        lib.gsr_activate.argtypes = [P, P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ActSegment), c_int, P]
     return lib
 
 
@@ -224,6 +241,9 @@ EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_b
             "gsr_image_metrics_scratch_floats", "gsr_image_metrics", "gsr_normal_mae_scratch_floats", "gsr_normal_mae",
             "gsr_present_view_scratch_floats", "gsr_present_view",
             "gsr_photometric_scratch_floats", "gsr_photometric_forward", "gsr_photometric_backward", "gsr_ssim_map_backward"]
+
+# the entries of include/gsr_hip_train.h (the raw-parameter step), added under ABI 102 and kept apart from the list above
+EXPORTED_TRAIN = ["gsr_adam_act_step", "gsr_activate"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

@@ -11,7 +11,7 @@ copies of the split children, each in index order.
 import torch
 
 from _gsr import GatherGroup, check, lib, ptr, stream_ptr
-from gsr_train import FlatParams, GaussianTrainState
+from gsr_train import FlatParams, GaussianTrainState, RawTrainState
 
 PER_GAUSSIAN = ("means3D", "shs", "opacities", "scales", "rotations", "refl_strengths")
 
@@ -81,6 +81,8 @@ def densify_and_prune(state, stats, max_grad, min_opacity, mean, extent, max_scr
     (new_state, new_stats, info).  `noise`: optional standard-normal tensor (N*k, scale_dims) for the k split parents (the
     reference draws it with torch.normal); drawn with torch.randn when None.  min_opacity is unused, as in the reference
     (its opacity prune is commented out, :561-562).
+    The scales are read as the reference's log-scales.  Given a gsr_train.RawTrainState (whose `p["scales"]` are log-scales) the new state
+    is a RawTrainState too: frozen groups and learning rates carried over, the activated copy filled by gsr_activate.
     Sharded state (view-parallel training with gsr_dist.ShardedStep): every rank holds all parameters and, after
     gsr_dist.reduce_densification_stats, the same statistics, so every rank takes the same decisions — given the same `noise`, which the
     caller must then supply (e.g. drawn on rank 0 and broadcast) — and rebuilds the same parameter buffer; the Adam moments, of which a
@@ -145,7 +147,8 @@ def densify_and_prune(state, stats, max_grad, min_opacity, mean, extent, max_scr
     shapes = {kk: ((P1,) + old.shapes[kk][1:] if kk in names else old.shapes[kk]) for kk in old.names}
     world = 1 if state.shard is None else state.shard[1]
     new = FlatParams(None, dev, shapes=shapes, shards=world)             # (padded to `world` equal 16-byte-aligned chunks, as the old store was)
-    new_state = GaussianTrainState(None, dev, spatial_lr_scale=state.spatial_lr_scale, lrs=state.lrs, _params=new, shard=state.shard)
+    # (the class of the state given: a gsr_train.RawTrainState, whose "scales" are the log-scales read above, stays one)
+    new_state = type(state)(None, dev, spatial_lr_scale=state.spatial_lr_scale, lrs=state.lrs, _params=new, shard=state.shard)
     opt_old, opt_new = state.optimizer, new_state.optimizer
     old_avg, old_sq = _whole_moments(state, group)
     sharded = opt_new.owned != (0, new.total)
@@ -174,5 +177,8 @@ def densify_and_prune(state, stats, max_grad, min_opacity, mean, extent, max_scr
     opt_new.step_count = opt_old.step_count
     for kk in opt_old.groups:
         opt_new.groups[kk] = opt_old.groups[kk]
+    if isinstance(new_state, RawTrainState):                                            # frozen groups stay frozen; activated copy of the new rows
+        opt_new.frozen = set(opt_old.frozen)
+        opt_new.activate()
     info = dict(pruned_by_weight=P0 - int(idx_a.numel()), cloned=int(clones.numel()), split=k, pruned_big=int((~keep).sum()), before=P0, after=P1)
     return new_state, DensifyStats(P1, dev), info

@@ -9,6 +9,9 @@ float32 buffers with one layout, so that
 The reference keeps `_features_dc` (P,1,3) and `_features_rest` (P,15,3) as separate parameters and concatenates them
 for every render (scene/gaussian_model.py:135-139); here `shs` (P,16,3) is stored concatenated and the two learning
 rates (feature_lr and feature_lr / 20, scene/gaussian_model.py:198-199) are applied by position inside each 48-float row.
+
+GaussianTrainState steps whatever numbers the buffer holds (callers hand it activated values); RawTrainState holds the reference's raw
+parameters and steps them through their activations in the same single launch (gsr_adam_act_step, include/gsr_hip_train.h).
 """
 import ctypes
 import math
@@ -151,13 +154,212 @@ class GaussianTrainState:
         if self.shard is not None:
             n = self.params.total // self.shard[1]
             owned = (self.shard[0] * n, (self.shard[0] + 1) * n)
-        self.optimizer = FlatAdam(self.params, self.grads.flat, {k: groups[k] for k in self.params.names}, owned=owned)
+        self.optimizer = self._make_optimizer({k: groups[k] for k in self.params.names}, owned)
         self.xyz_scheduler_args = get_expon_lr_func(lr_init=lr["position_lr_init"] * spatial_lr_scale,
                                                     lr_final=lr["position_lr_final"] * spatial_lr_scale,
                                                     lr_delay_mult=lr["position_lr_delay_mult"], max_steps=lr["position_lr_max_steps"])
+
+    def _make_optimizer(self, groups, owned):
+        return FlatAdam(self.params, self.grads.flat, groups, owned=owned)
 
     def update_learning_rate(self, iteration):
         # scene/gaussian_model.py:215-221
         v = self.xyz_scheduler_args(iteration)
         self.optimizer.set_lr("means3D", v)
         return v
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Raw parameters (scene/gaussian_model.py:42-52, 123-147): the reference trains _opacity, _scaling, _rotation and _refl_strength and
+# renders sigmoid / exp / normalize / sigmoid of them.  Here the flat buffer holds those RAW values, a second compact buffer holds
+# their activated copy for the rasterizer, and one launch (gsr_adam_act_step, include/gsr_hip_train.h) turns the dL/d(activated) the
+# rasterizer wrote into dL/d(raw), steps Adam and refreshes the copy.
+ACTIVATIONS = dict(opacities=_gsr.GSR_ACT_SIGMOID, scales=_gsr.GSR_ACT_EXP, rotations=_gsr.GSR_ACT_NORMALIZE4, refl_strengths=_gsr.GSR_ACT_SIGMOID)
+
+
+def inverse_sigmoid(x):
+    """utils/general_utils.py:18-19 of the reference."""
+    return torch.log(x / (1 - x))
+
+
+def _require_train_entries():
+    if not hasattr(lib, "gsr_adam_act_step"):
+        raise ImportError(f"{_gsr.LIB_PATH} was built before the raw-parameter step (gsr_adam_act_step, include/gsr_hip_train.h): rebuild it. "
+                          "There is no torch fallback.")
+
+
+class RawAdam(FlatAdam):
+    """FlatAdam over RAW parameters: `act` is the compact activated buffer, `act_slices[name] = (begin, end)` the place of each activated
+    group in it (multiples of 4, as long as the group's segment of the flat buffer, padding included).  step() is one launch of
+    gsr_adam_act_step; activate() fills `act` from the raw buffer alone (gsr_activate)."""
+
+    def __init__(self, params, grads_flat, groups, act, act_slices, betas=(0.9, 0.999), eps=1e-15):
+        _require_train_entries()
+        super().__init__(params, grads_flat, groups, betas=betas, eps=eps)
+        if act.data_ptr() % 16:
+            raise ValueError("the activated buffer must be 16-byte aligned")
+        self.act, self.act_slices, self.frozen = act, dict(act_slices), set()
+
+    def _act_segments(self):
+        names = self.params.names
+        segs = (_gsr.ActSegment * len(names))()
+        for i, k in enumerate(names):
+            a, _ = self.params.slices[k]
+            end = self.params.slices[names[i + 1]][0] if i + 1 < len(names) else self.params.total   # padding rides with the group
+            lr, lr2, period, split = self.groups[k]
+            kind = ACTIVATIONS.get(k, _gsr.GSR_ACT_NONE) if k in self.act_slices else _gsr.GSR_ACT_NONE
+            if k in self.frozen:
+                kind |= _gsr.GSR_ACT_FROZEN
+            segs[i] = _gsr.ActSegment(a, end, lr, lr2, period, split, kind, self.act_slices[k][0] if k in self.act_slices else 0)
+        return segs
+
+    def step(self):
+        self.step_count += 1
+        segs = self._act_segments()
+        dev = self.params.flat.device
+        _gsr.side_join(dev)      # (the cubemap gradient may still be in flight on the library's side stream)
+        n = self.params.total
+        with torch.cuda.device(dev):
+            check(lib.gsr_adam_act_step(self.params.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                        self.act.data_ptr(), n, self.act.numel(), segs, len(segs), self.betas[0], self.betas[1], self.eps,
+                                        self.step_count, 0, n, stream_ptr(dev)), "gsr_adam_act_step")
+
+    def activate(self):
+        """act = act(raw): at construction, after densification and after a reset."""
+        segs = self._act_segments()
+        dev = self.params.flat.device
+        with torch.cuda.device(dev):
+            check(lib.gsr_activate(self.params.flat.data_ptr(), self.act.data_ptr(), self.params.total, self.act.numel(), segs, len(segs),
+                                   stream_ptr(dev)), "gsr_activate")
+
+
+class _Model:
+    """The `get_xyz / get_opacity / ...` object gaussian_renderer.render() takes (the reference's GaussianModel properties)."""
+
+    def __init__(self, inputs, active_sh_degree):
+        class Env:
+            params = {"Cubemap_texture": inputs.get("cubemap"), "Cubemap_failv": inputs.get("fail")}
+        self.get_xyz, self.get_features = inputs["means3D"], inputs["shs"]
+        self.get_opacity, self.get_scaling, self.get_rotation = inputs["opacities"], inputs["scales"], inputs["rotations"]
+        self.get_refl = inputs["refl_strengths"]
+        self.active_sh_degree, self.get_envmap = active_sh_degree, Env
+
+
+class RawTrainState(GaussianTrainState):
+    """GaussianTrainState over the reference's RAW parameters (same constructor arguments, learning rates and update_learning_rate).
+
+      .p      leaf views of the raw flat buffer (logits, log-scales, unnormalised quaternions): what PLY export and densification read
+      .a      leaf views of the compact activated buffer for opacities, scales, rotations, refl_strengths: what the rasterizer reads
+      .grads  FlatGrads.mirroring(params), unchanged.  The slots of the four activated groups receive dL/d(ACTIVATED) — through the
+              rasterizer's gradient sink, or through autograd (`.a[k].grad` is the view of that slot) — and optimizer.step() applies
+              the chain rule itself.  (`.p[k].grad` of those four is the same view: it does not hold dL/d(raw).)
+    """
+
+    ACTIVATED = ("opacities", "scales", "rotations", "refl_strengths")
+
+    def __init__(self, tensors, device, spatial_lr_scale=1.0, lrs=None, _params=None, shard=None):
+        if shard is not None:
+            raise NotImplementedError("RawTrainState(shard=...): the sharded exchange of the activated copy is not implemented; "
+                                      "gsr_adam_act_step takes a range for it")
+        _require_train_entries()
+        super().__init__(tensors, device, spatial_lr_scale=spatial_lr_scale, lrs=lrs, _params=_params, shard=None)
+        self.a = {}
+        for k, (a, b) in self.optimizer.act_slices.items():
+            n = self.params.slices[k][1] - self.params.slices[k][0]
+            self.a[k] = self.optimizer.act[a:a + n].view(self.params.shapes[k]).requires_grad_(True)
+            self.a[k].grad = self.grads.view(k)
+        self.optimizer.activate()
+
+    def _make_optimizer(self, groups, owned):
+        names, act_slices, off = self.params.names, {}, 0
+        for i, k in enumerate(names):
+            if k in self.ACTIVATED:
+                end = self.params.slices[names[i + 1]][0] if i + 1 < len(names) else self.params.total
+                n = end - self.params.slices[k][0]
+                act_slices[k] = (off, off + n)
+                off += n
+        act = torch.zeros(max(off, 4), dtype=torch.float32, device=self.params.flat.device)
+        return RawAdam(self.params, self.grads.flat, groups, act, act_slices)
+
+    @classmethod
+    def from_activated(cls, tensors, device, **kw):
+        """A state from ACTIVATED values (what gsr_init.init_from_point_cloud returns and GaussianTrainState takes): log of the scales,
+        inverse_sigmoid of opacities and reflection strengths, quaternions as they are — applied once, with torch ops.  The activated copy
+        starts as the very values given (exp(log(x)) is not x in float32), so that what is rendered before the first step is what
+        GaussianTrainState renders from the same tensors bit for bit; the first step, a reset or a densification replaces it by act(raw)."""
+        raw = dict(tensors)
+        with torch.no_grad():
+            for k in ("opacities", "refl_strengths"):
+                if k in raw:
+                    raw[k] = inverse_sigmoid(raw[k].float())
+            if "scales" in raw:
+                raw["scales"] = torch.log(raw["scales"].float())
+        st = cls(raw, device, **kw)
+        with torch.no_grad():
+            for k, view in st.a.items():
+                view.copy_(tensors[k].reshape(view.shape))
+        return st
+
+    def render_inputs(self):
+        """The eight tensors to hand to the rasterizer: raw means3D, shs, cubemap, fail; activated opacities, scales, rotations, refl_strengths."""
+        return {k: (self.a[k] if k in self.a else self.p[k]) for k in self.params.names}
+
+    def model(self, active_sh_degree=3):
+        return _Model(self.render_inputs(), active_sh_degree)
+
+    def set_lr(self, name, lr):
+        self.optimizer.set_lr(name, lr)
+
+    def freeze(self, names, frozen=True):
+        """freeze_xyz of the reference is freeze(("means3D", "rotations")): the step leaves those groups' raw values, moments and activated
+        copy bit for bit."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [k for k in names if k not in self.params.names]
+        if unknown:
+            raise KeyError(f"freeze: unknown group(s) {unknown}")
+        (self.optimizer.frozen.update if frozen else self.optimizer.frozen.difference_update)(names)
+
+    def _replace(self, name, new_raw):
+        """replace_tensor_to_optimizer (scene/gaussian_model.py:395-408): new raw values, both moments of the group zeroed; then the
+        activated copy is refreshed."""
+        names = self.params.names
+        i = names.index(name)
+        a = self.params.slices[name][0]
+        end = self.params.slices[names[i + 1]][0] if i + 1 < len(names) else self.params.total
+        with torch.no_grad():
+            self.p[name].copy_(new_raw)
+            self.optimizer.exp_avg[a:end].zero_()
+            self.optimizer.exp_avg_sq[a:end].zero_()
+        self.optimizer.activate()
+
+    def reset_opacity(self, reset_value=0.01, exclusive_msk=None):
+        # scene/gaussian_model.py:271-276
+        with torch.no_grad():
+            raw = self.p["opacities"].detach()
+            act = torch.sigmoid(raw)
+            new = inverse_sigmoid(torch.min(act, torch.ones_like(act) * reset_value))
+            if exclusive_msk is not None:
+                new[exclusive_msk] = raw[exclusive_msk]
+        self._replace("opacities", new)
+
+    def reset_refl(self, init_refl_value=1e-3, exclusive_msk=None):
+        # scene/gaussian_model.py:264-269
+        with torch.no_grad():
+            raw = self.p["refl_strengths"].detach()
+            act = torch.sigmoid(raw)
+            new = inverse_sigmoid(torch.max(act, torch.ones_like(act) * init_refl_value))
+            if exclusive_msk is not None:
+                new[exclusive_msk] = raw[exclusive_msk]
+        self._replace("refl_strengths", new)
+
+    def reset_scale(self, enlarge_scale=1.5, exclusive_msk=None):
+        # scene/gaussian_model.py:286-294: every axis but the smallest grows by enlarge_scale
+        with torch.no_grad():
+            raw = self.p["scales"].detach()
+            scales = torch.exp(raw)
+            min_axis_id = torch.argmin(scales, dim=-1, keepdim=True)
+            rmin_axis = (torch.ones_like(scales) * enlarge_scale).scatter(1, min_axis_id, 1)
+            new = torch.log(scales * rmin_axis)
+            if exclusive_msk is not None:
+                new[exclusive_msk] = raw[exclusive_msk]
+        self._replace("scales", new)
