@@ -198,6 +198,15 @@ def _load():
                                           c_float, c_int, ctypes.c_uint64, ctypes.c_uint64, P]
         lib.gsr_activate.restype = c_int
         lib.gsr_activate.argtypes = [P, P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ActSegment), c_int, P]
+    if hasattr(lib, "gsr_env_scope_forward"):
+        # (likewise, declared in include/gsr_hip_scope.h: a library built before the env-scope pass lacks these three;
+        # utils.loss_utils.env_scope_masks and refl_scope_loss then refuse to run)
+        lib.gsr_env_scope_scratch_floats.restype = c_size_t
+        lib.gsr_env_scope_scratch_floats.argtypes = []
+        lib.gsr_env_scope_forward.restype = c_int
+        lib.gsr_env_scope_forward.argtypes = [c_int, P, P, c_float, c_float, c_float, c_float, P, P, P, P, P]
+        lib.gsr_env_scope_backward.restype = c_int
+        lib.gsr_env_scope_backward.argtypes = [c_int, P, P, P, P, c_int, P]
     return lib
 
 
@@ -244,6 +253,9 @@ EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_b
 
 # the entries of include/gsr_hip_train.h (the raw-parameter step), added under ABI 102 and kept apart from the list above
 EXPORTED_TRAIN = ["gsr_adam_act_step", "gsr_activate"]
+
+# the entries of include/gsr_hip_scope.h (the env-scope masks and the reflection-mask loss), likewise
+EXPORTED_SCOPE = ["gsr_env_scope_scratch_floats", "gsr_env_scope_forward", "gsr_env_scope_backward"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

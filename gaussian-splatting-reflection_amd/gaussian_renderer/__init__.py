@@ -484,7 +484,14 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     # allmap[2:5] as an output tap: the gradient of its consumer below reaches the tile backward as a pointer of its own instead
     # of being summed into a full-size allmap gradient by autograd (same values; GaussianRasterizer.set_output_taps)
     rasterizer.set_output_taps(("normal_view",))
-    if env_scope_radius > 0.0:
+    env_scope_mask = getattr(pipe, "gsr_env_scope_mask", None)
+    if env_scope_mask is not None:
+        # (extension, in the convention of pipe.gsr_grad_sink: the `inside` mask of utils.loss_utils.refl_scope_loss / env_scope_masks,
+        # which the iteration has already computed beside its loss; env_scope_center and env_scope_radius are then not evaluated)
+        if env_scope_mask.dtype != torch.bool or tuple(env_scope_mask.shape) != (xyz.shape[0],) or env_scope_mask.device != dev:
+            raise ValueError(f"pipe.gsr_env_scope_mask: expected a torch.bool tensor of shape ({xyz.shape[0]},) on {dev}, got "
+                             f"{env_scope_mask.dtype} {tuple(env_scope_mask.shape)} on {env_scope_mask.device}")
+    elif env_scope_radius > 0.0:
         centre = torch.tensor([float(c) for c in env_scope_center], device=dev)
         env_scope_mask = ((xyz - centre[None]) ** 2).sum(dim=-1) < env_scope_radius ** 2
     else:

@@ -168,6 +168,34 @@ class GaussianTrainState:
         self.optimizer.set_lr("means3D", v)
         return v
 
+    def _activated(self, name):
+        """What the rasterizer reads for group `name` (RawTrainState: the activated copy)."""
+        return self.p[name]
+
+    def refl_scope_loss(self, center, radius, weight=0.4, accumulate=True):
+        """The env-scope branch of the reference's iteration (train.py:56-63, 176-179) for the sink-driven step:
+            loss += weight * refl[outside].mean(),   outside = sum((xyz - center)^2, -1) > radius^2
+        Reads p["means3D"] and the activated reflection strengths, adds weight / count on the outside rows straight into
+        grads.view("refl_strengths") — both state classes keep dL/d(activated) there, so the raw step's chain rule applies as it is —
+        and returns (weight * loss detached, inside, outside): `inside` for pipe.gsr_env_scope_mask, `outside` for the exclusive masks of
+        the resets.  One forward and one backward launch, no autograd node, no host read (utils.loss_utils.refl_scope_loss is the autograd
+        form).  With no point outside the value is NaN, as in the reference, and the gradient buffer gets zeros or nothing.
+        Ordering: call it AFTER the rasterizer's backward with accumulate=True (it adds to what the sink holds); or call it FIRST with
+        accumulate=False (it overwrites the whole refl_strengths slot) and give the rasterizer's sink accumulate=True.
+        A sharded state (shard=) raises NotImplementedError."""
+        if self.shard is not None:
+            # every rank would add the whole term to its buffer and the reduce-scatter would sum it world_size times
+            raise NotImplementedError("refl_scope_loss on a sharded state (shard=(rank, world_size)) is not implemented")
+        from utils import loss_utils as lu
+        lu._require_scope_entries()
+        with torch.no_grad():
+            x = lu._scope_xyz(self.p["means3D"])
+            refl = self._activated("refl_strengths").detach()
+            inside, outside, sums = lu._scope_forward(x, refl.float().contiguous(), lu._scope_sphere(center, radius))
+            g = torch.full((1,), float(weight), dtype=torch.float32, device=x.device)
+            lu._scope_backward(outside, sums, g, self.grads.view("refl_strengths"), accumulate)
+            return weight * (sums[0] / sums[1]), inside, outside
+
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Raw parameters (scene/gaussian_model.py:42-52, 123-147): the reference trains _opacity, _scaling, _rotation and _refl_strength and
@@ -307,6 +335,9 @@ class RawTrainState(GaussianTrainState):
     def model(self, active_sh_degree=3):
         return _Model(self.render_inputs(), active_sh_degree)
 
+    def _activated(self, name):
+        return self.a[name] if name in self.a else self.p[name]
+
     def set_lr(self, name, lr):
         self.optimizer.set_lr(name, lr)
 
@@ -363,3 +394,21 @@ class RawTrainState(GaussianTrainState):
             if exclusive_msk is not None:
                 new[exclusive_msk] = raw[exclusive_msk]
         self._replace("scales", new)
+
+    def dist_color(self, noise_range=0.4, exclusive_msk=None, noise=None):
+        """The colour sabotage (scene/gaussian_model.py:278-284): uniform noise in [-noise_range, noise_range) on the DC colour of every
+        row outside exclusive_msk, and — replace_tensor_to_optimizer on the whole f_dc group — both Adam moments zeroed at the f_dc
+        positions (the first 3 floats of each 3*M-float row of shs) of ALL rows.  The f_rest moments, every other group and the activated
+        copy stay bit for bit.  noise: uniform in [0, 1), [P,1,3] or [P,3] (torch.rand when None), as densify_and_prune(noise=) takes it."""
+        with torch.no_grad():
+            shs = self.p["shs"].detach()
+            P, M = shs.shape[0], shs.shape[1]
+            dcc = shs[:, 0, :].clone()
+            noise = torch.rand_like(dcc) if noise is None else noise.to(device=dcc.device, dtype=torch.float32).reshape(P, 3)
+            new = dcc + (noise * noise_range * 2 - noise_range)
+            if exclusive_msk is not None:
+                new[exclusive_msk] = dcc[exclusive_msk]
+            shs[:, 0, :] = new
+            a = self.params.slices["shs"][0]
+            for moment in (self.optimizer.exp_avg, self.optimizer.exp_avg_sq):
+                moment[a:a + P * M * 3].view(P, M * 3)[:, :3].zero_()

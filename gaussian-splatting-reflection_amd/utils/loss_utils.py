@@ -11,8 +11,9 @@ sigma 1.5, zero padding 5) is implemented.
 import weakref
 
 import torch
+from torch.autograd.function import once_differentiable
 
-from _gsr import check, f32c, lib, ptr, require_cuda, stream_ptr
+from _gsr import check, check_sink_tensor, f32c, lib, ptr, require_cuda, stream_ptr
 
 if not hasattr(lib, "gsr_photometric_forward"):
     raise ImportError("libgsr_hip.so does not export gsr_photometric_forward: it was built before the composited loss "
@@ -317,3 +318,112 @@ def normal_consistency_loss(rend_normal, surf_normal, lambda_normal=1.0, env_sco
     rasterizer's binary env-scope plane, which has none in the reference's backward either)."""
     n = rend_normal.shape[1] * rend_normal.shape[2]
     return lambda_normal * (_NormalErrorSum.apply(rend_normal, surf_normal, env_scope_mask) / n)
+
+
+# ------------------------------------------------------------------------------------------- env scope (opt.use_env_scope)
+# train.py:56-63, 176-179 of the reference: the sphere test of every Gaussian centre and the reflection-mask loss over the centres outside
+# it, on gsr_env_scope_forward / _backward (include/gsr_hip_scope.h): one pass over the points each way and no host read.
+def _require_scope_entries():
+    if not hasattr(lib, "gsr_env_scope_forward"):
+        raise ImportError("libgsr_hip.so does not export gsr_env_scope_forward: it was built before the env-scope pass "
+                          "(csrc/gsr_scope.hip); rebuild with csrc/build.py --force.  There is no torch fallback.")
+
+
+def _scope_sphere(center, radius):
+    """(cx, cy, cz, radius2) as the Python floats the library takes by value; ctypes rounds them to float32 exactly as
+    `torch.tensor(center)` and torch's comparison against the Python float `radius ** 2` do.  A tensor centre is read on the host
+    (a device tensor costs a synchronisation: pass the numbers the options hold)."""
+    c = [float(v) for v in (center.detach().reshape(-1).tolist() if torch.is_tensor(center) else center)]
+    if len(c) != 3:
+        raise ValueError(f"env scope: the centre must have three coordinates, got {len(c)}")
+    return c[0], c[1], c[2], float(radius) ** 2
+
+
+def _scope_xyz(xyz):
+    require_cuda(xyz, "xyz")
+    if xyz.dim() != 2 or xyz.size(1) != 3:
+        raise ValueError(f"env scope: expected xyz of shape (P,3), got {tuple(xyz.shape)}")
+    return xyz.detach().float().contiguous()
+
+
+def _scope_forward(x, refl, sphere, want_inside=True):
+    """One gsr_env_scope_forward call: (inside, outside, sums); sums is None without refl."""
+    P, dev = x.size(0), x.device
+    inside = torch.empty(P, dtype=torch.bool, device=dev) if want_inside else None
+    outside = torch.empty(P, dtype=torch.bool, device=dev)
+    sums = scratch = None
+    if refl is not None:
+        sums = torch.empty(2, dtype=torch.float32, device=dev)
+        scratch = torch.empty(int(lib.gsr_env_scope_scratch_floats()), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.gsr_env_scope_forward(P, ptr(x), ptr(refl), sphere[0], sphere[1], sphere[2], sphere[3], ptr(inside), ptr(outside), ptr(sums),
+                                        ptr(scratch), stream_ptr(dev)), "gsr_env_scope_forward")
+    return inside, outside, sums
+
+
+def _scope_backward(outside, sums, g, grad, accumulate):
+    """grad (+)= outside ? g / count : 0 (gsr_env_scope_backward); g is one float on the device."""
+    P = outside.numel()
+    if P == 0:
+        return
+    with torch.cuda.device(outside.device):
+        check(lib.gsr_env_scope_backward(P, ptr(outside), ptr(sums), ptr(g), ptr(grad), 1 if accumulate else 0, stream_ptr(outside.device)),
+              "gsr_env_scope_backward")
+
+
+def env_scope_masks(xyz, center, radius):
+    """(inside, outside): two torch.bool [P] tensors from one launch,
+        inside  = ((xyz - center[None]) ** 2).sum(-1) < radius ** 2      (gaussian_renderer.render's env_scope_mask)
+        outside = ((xyz - center[None]) ** 2).sum(-1) > radius ** 2      (train.py:61-63, get_outside_msk)
+    with the float32 roundings of those expressions.  Neither is the other's negation: a centre exactly on the sphere or with a NaN
+    coordinate is in neither.  `center`: three numbers (passed by value: no device copy) or a tensor."""
+    _require_scope_entries()
+    x = _scope_xyz(xyz)
+    inside, outside, _ = _scope_forward(x, None, _scope_sphere(center, radius))
+    return inside, outside
+
+
+class _ReflScopeLoss(torch.autograd.Function):
+    """loss = mean of refl over the outside points; gradient to refl only (the sphere test has none in the reference either)."""
+
+    @staticmethod
+    def forward(ctx, refl, xyz, sphere, grad_sink, accumulate):
+        x = _scope_xyz(xyz)
+        if refl.dim() not in (1, 2) or refl.numel() != x.size(0):
+            raise ValueError(f"refl_scope_loss: expected refl of shape (P,) or (P,1) with P = {x.size(0)}, got {tuple(refl.shape)}")
+        r = refl.detach().float().contiguous()
+        if grad_sink is not None:
+            check_sink_tensor("grad sink", "refl", grad_sink, refl.shape, r.device, aligned=False)
+        inside, outside, sums = _scope_forward(x, r, sphere)
+        ctx.save_for_backward(outside, sums)
+        ctx.sink, ctx.accumulate, ctx.in_shape, ctx.in_dtype = grad_sink, bool(accumulate), refl.shape, refl.dtype
+        ctx.mark_non_differentiable(inside, outside)
+        return sums[0] / sums[1], inside, outside
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, _gi, _go):
+        outside, sums = ctx.saved_tensors
+        g = g_loss.float().reshape(1).contiguous()
+        if ctx.sink is not None:
+            _scope_backward(outside, sums, g, ctx.sink, ctx.accumulate)
+            return None, None, None, None, None
+        grad = torch.empty(ctx.in_shape, dtype=torch.float32, device=outside.device)
+        _scope_backward(outside, sums, g, grad, False)
+        return grad.to(ctx.in_dtype), None, None, None, None
+
+
+def refl_scope_loss(refl, xyz, center, radius, grad_sink=None, accumulate=False):
+    """(loss, inside, outside) of the reference's env-scope branch (train.py:61-63, 176-179):
+        loss = refl[outside].mean(),  outside = torch.sum((xyz - center[None]) ** 2, dim=-1) > radius ** 2
+    as one fused pass each way: no nonzero, no host read.  `loss` is a 0-dim device tensor, sum / count formed on the device: NaN when no
+    point is outside, as torch's mean of an empty selection (which, like here, then sends no gradient to any row).  `inside` and `outside`
+    are the masks of env_scope_masks (non-differentiable).  The gradient reaches `refl` ([P] or [P,1], ACTIVATED strengths) only.
+    grad_sink: a contiguous float32 tensor of refl's shape; the backward then writes (accumulate=False: every element, zeros where the
+    point is not outside) or adds (accumulate=True: outside rows only) dL/drefl straight into it and autograd receives None for refl —
+    the semantics of the rasterizer's sinks (_raster_api.GradSink)."""
+    _require_scope_entries()
+    if accumulate and grad_sink is None:
+        raise ValueError("refl_scope_loss: accumulate=True needs a grad_sink to add to")
+    require_cuda(refl, "refl")
+    return _ReflScopeLoss.apply(refl, xyz, _scope_sphere(center, radius), grad_sink, accumulate)
