@@ -207,6 +207,13 @@ def _load():
         lib.gsr_env_scope_forward.argtypes = [c_int, P, P, c_float, c_float, c_float, c_float, P, P, P, P, P]
         lib.gsr_env_scope_backward.restype = c_int
         lib.gsr_env_scope_backward.argtypes = [c_int, P, P, P, P, c_int, P]
+    if hasattr(lib, "gsr_envmap_resize"):
+        # (likewise, declared in include/gsr_hip_envmap.h: a library built before the environment-map transforms lacks these two;
+        # gsr_envmap.resize_env_map, double_env_map and filter_env_map then refuse to run)
+        lib.gsr_envmap_resize.restype = c_int
+        lib.gsr_envmap_resize.argtypes = [P, P, c_int, c_int, c_int, P]
+        lib.gsr_envmap_sharpen.restype = c_int
+        lib.gsr_envmap_sharpen.argtypes = [P, P, c_int, c_int, c_float, c_float, c_float, P]
     return lib
 
 
@@ -256,6 +263,9 @@ EXPORTED_TRAIN = ["gsr_adam_act_step", "gsr_activate"]
 
 # the entries of include/gsr_hip_scope.h (the env-scope masks and the reflection-mask loss), likewise
 EXPORTED_SCOPE = ["gsr_env_scope_scratch_floats", "gsr_env_scope_forward", "gsr_env_scope_backward"]
+
+# the entries of include/gsr_hip_envmap.h (the environment map's bicubic resize and its sharpening in sigmoid space), likewise
+EXPORTED_ENVMAP = ["gsr_envmap_resize", "gsr_envmap_sharpen"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

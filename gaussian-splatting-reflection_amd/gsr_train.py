@@ -261,16 +261,27 @@ class RawAdam(FlatAdam):
                                    stream_ptr(dev)), "gsr_activate")
 
 
+class _Env:
+    """What render() and render_env_map() take of a CubemapEncoder: `params` under the reference's keys and, called with directions [B, 3],
+    the lookup of a default encoder (linear, seamless) on those two tensors, [B, C]."""
+
+    def __init__(self, cubemap, fail):
+        self.params = {"Cubemap_texture": cubemap, "Cubemap_failv": fail}
+
+    def __call__(self, dirs):
+        from cubemapencoder.cubemap_encoder import CubemapEncoder, _interp_to_id, cubemap_encode
+        return cubemap_encode(dirs, self.params["Cubemap_texture"], self.params["Cubemap_failv"], _interp_to_id["linear"],
+                              CubemapEncoder.seamless).permute(1, 0)
+
+
 class _Model:
     """The `get_xyz / get_opacity / ...` object gaussian_renderer.render() takes (the reference's GaussianModel properties)."""
 
     def __init__(self, inputs, active_sh_degree):
-        class Env:
-            params = {"Cubemap_texture": inputs.get("cubemap"), "Cubemap_failv": inputs.get("fail")}
         self.get_xyz, self.get_features = inputs["means3D"], inputs["shs"]
         self.get_opacity, self.get_scaling, self.get_rotation = inputs["opacities"], inputs["scales"], inputs["rotations"]
         self.get_refl = inputs["refl_strengths"]
-        self.active_sh_degree, self.get_envmap = active_sh_degree, Env
+        self.active_sh_degree, self.get_envmap = active_sh_degree, _Env(inputs.get("cubemap"), inputs.get("fail"))
 
 
 class RawTrainState(GaussianTrainState):
