@@ -220,6 +220,14 @@ def _load():
 lib = _load()
 
 
+def require_entry(library, name, source_file):
+    """The check in front of an entry added under ABI 102 without a version change (the `hasattr` blocks above): `library` is the
+    calling module's `lib`, `source_file` the file under this directory the entry lives in."""
+    if not hasattr(library, name):
+        raise ImportError(f"{LIB_PATH} does not export {name} ({source_file}): it was built before that entry was added; "
+                          f"rebuild with `python {os.path.join(_HERE, 'csrc', 'build.py')} --force`.  There is no torch fallback.")
+
+
 def compiled_binding():
     """The optional compiled torch/pybind binding (csrc/gsr_torch_binding.cpp -> _gsr_C.so): marshaling in C++ over the same C
     ABI, about half the host cost per call of the ctypes path (tests/host_overhead.py at C1: 25 vs 49 us per backward).

@@ -15,75 +15,28 @@ namespace gsr {
 // ---------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam, amsgrad = False, weight_decay = 0, maximize = False; torch/optim/adam.py _single_tensor_adam):
 //   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// One kernel steps every caller.  The raw-parameter step (include/gsr_hip_train.h) has the activation's chain rule in front of adam_one
+// and the activation behind it; gsr_adam_step[_range] is that step with every segment GSR_ACT_NONE.  The rasterizer left
+// dL/d(activated) in the gradient slots of the activated segments; the activation is recomputed from raw in registers (8 of the
+// 59 floats per surfel; the pass stays HBM-bound), the activated copy is only ever written.
+// A NORMALIZE4 segment begins at a multiple of 4 and holds whole rows, so one lane's float4 IS one quaternion; an activated segment
+// begins at a multiple of 4 in both buffers, so a float4 that lies inside one segment has one aligned float4 destination.
 #define ADAM_MAX_SEG 16
+#define ACT_KIND_MASK 0xFFu
 struct AdamSegs {
 	int n;
 	unsigned long long end[ADAM_MAX_SEG];   // exclusive end offset of segment i (begin = end[i-1])
 	float lr[ADAM_MAX_SEG], lr2[ADAM_MAX_SEG];
 	unsigned int period[ADAM_MAX_SEG], split[ADAM_MAX_SEG];
-};
-__device__ __forceinline__ float adam_lr(const AdamSegs& s, unsigned long long i) {
-	int k = 0;
-	while (k + 1 < s.n && i >= s.end[k]) k++;
-	const unsigned long long begin = k ? s.end[k - 1] : 0ull;
-	if (s.period[k] == 0u) return s.lr[k];
-	return ((i - begin) % s.period[k]) < s.split[k] ? s.lr[k] : s.lr2[k];
-}
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
-                                         float sqrt_bc2) {
-	m = b1 * m + (1.f - b1) * g;
-	v = b2 * v + (1.f - b2) * (g * g);
-	const float denom = sqrtf(v) / sqrt_bc2 + eps;
-	p -= (lr / bc1) * (m / denom);
-}
-__global__ void __launch_bounds__(256)
-adam_kernel(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-            unsigned long long first, unsigned long long n, AdamSegs segs, float b1, float b2, float eps, float inv_bc1, float inv_sqrt_bc2) {
-	// (inv_bc1, inv_sqrt_bc2 carry bc1 and sqrt(bc2) themselves: the divisions stay in the kernel, as in torch's addcdiv path)
-	// elements [first, n) of the buffers (first is a multiple of 4): a rank that owns one shard of the flat buffer steps only that
-	const unsigned long long i4 = first + ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * 4ull;
-	if (i4 >= n) return;
-	if (i4 + 4 <= n) {
-		float4 p = *reinterpret_cast<float4*>(param + i4);
-		const float4 g = *reinterpret_cast<const float4*>(grad + i4);
-		float4 m = *reinterpret_cast<float4*>(exp_avg + i4), v = *reinterpret_cast<float4*>(exp_avg_sq + i4);
-		adam_one(p.x, g.x, m.x, v.x, adam_lr(segs, i4), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-		adam_one(p.y, g.y, m.y, v.y, adam_lr(segs, i4 + 1), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-		adam_one(p.z, g.z, m.z, v.z, adam_lr(segs, i4 + 2), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-		adam_one(p.w, g.w, m.w, v.w, adam_lr(segs, i4 + 3), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-		*reinterpret_cast<float4*>(param + i4) = p;
-		*reinterpret_cast<float4*>(exp_avg + i4) = m;
-		*reinterpret_cast<float4*>(exp_avg_sq + i4) = v;
-	} else {
-		for (unsigned long long i = i4; i < n; i++) {
-			float p = param[i], m = exp_avg[i], v = exp_avg_sq[i];
-			adam_one(p, grad[i], m, v, adam_lr(segs, i), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-			param[i] = p; exp_avg[i] = m; exp_avg_sq[i] = v;
-		}
-	}
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Raw-parameter step (include/gsr_hip_train.h): adam_kernel with the activation's chain rule in front of adam_one and the activation
-// behind it.  The rasterizer left dL/d(activated) in the gradient slots of the activated segments; the activation is recomputed
-// from raw in registers (8 of the 59 floats per surfel; the pass stays HBM-bound), the activated copy is only ever written.
-// A NORMALIZE4 segment begins at a multiple of 4 and holds whole rows, so one lane's float4 IS one quaternion; an activated segment
-// begins at a multiple of 4 in both buffers, so a float4 that lies inside one segment has one aligned float4 destination.
-#define ACT_KIND_MASK 0xFFu
-struct ActSegs {
-	int n;
-	unsigned long long end[ADAM_MAX_SEG];
-	float lr[ADAM_MAX_SEG], lr2[ADAM_MAX_SEG];
-	unsigned int period[ADAM_MAX_SEG], split[ADAM_MAX_SEG];
 	unsigned int kind[ADAM_MAX_SEG];
 	unsigned long long act_begin[ADAM_MAX_SEG];
 };
-__device__ __forceinline__ int act_seg(const ActSegs& s, unsigned long long i) {
+__device__ __forceinline__ int adam_seg(const AdamSegs& s, unsigned long long i) {
 	int k = 0;
 	while (k + 1 < s.n && i >= s.end[k]) k++;
 	return k;
 }
-__device__ __forceinline__ float act_lr(const ActSegs& s, int k, unsigned long long i) {
+__device__ __forceinline__ float adam_lr(const AdamSegs& s, int k, unsigned long long i) {
 	const unsigned long long begin = k ? s.end[k - 1] : 0ull;
 	if (s.period[k] == 0u) return s.lr[k];
 	return ((i - begin) % s.period[k]) < s.split[k] ? s.lr[k] : s.lr2[k];
@@ -94,12 +47,11 @@ __device__ __forceinline__ float act_grad(unsigned int kind, float r, float g) {
 	const float a = act_value(kind, r);
 	return kind == GSR_ACT_SIGMOID ? g * a * (1.f - a) : g * a;
 }
-// adam_one with its roundings spelled out.  Under -ffp-contract=fast the compiler picks which product of `b1 * m + (1 - b1) * g` it fuses
-// into the sum, and it picks by the shape of the code around it: inside adam_kernel it fuses the gradient's product into each moment and
-// the update into the parameter, inside this kernel it chose the other product.  A GSR_ACT_NONE segment must step bit for bit as
-// gsr_adam_step does (tests/test_gpu_raw_step.py holds the two side by side), so the choice is written down here instead of left open.
-__device__ __forceinline__ void adam_one_spelled(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
-                                                 float sqrt_bc2) {
+// The one definition of the update, and it fixes the roundings: the gradient's product is fused into each moment and the update into the
+// parameter, every other operation rounds once.  Under -ffp-contract=fast the compiler would pick which product of `b1 * m + (1 - b1) * g`
+// it fuses by the shape of the code around it, so an edit elsewhere in the kernel could move results by an ulp.
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
+                                         float sqrt_bc2) {
 #pragma clang fp contract(off)
 	m = fmaf(1.f - b1, g, b1 * m);
 	v = fmaf(1.f - b2, g * g, b2 * v);
@@ -115,12 +67,14 @@ __device__ __forceinline__ float4 normalize4(float4 q, float& norm) {
 // STEP: the whole step.  !STEP: act = act(raw) alone (grad and the moments are not touched and may be NULL; FROZEN is ignored).
 template <bool STEP>
 __global__ void __launch_bounds__(256)
-adam_act_kernel(float* __restrict__ raw, const float* __restrict__ grad, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-                float* __restrict__ act, unsigned long long first, unsigned long long n, ActSegs segs, float b1, float b2, float eps, float inv_bc1,
-                float inv_sqrt_bc2) {
+adam_kernel(float* __restrict__ raw, const float* __restrict__ grad, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+            float* __restrict__ act, unsigned long long first, unsigned long long n, AdamSegs segs, float b1, float b2, float eps, float inv_bc1,
+            float inv_sqrt_bc2) {
+	// (inv_bc1, inv_sqrt_bc2 carry bc1 and sqrt(bc2) themselves: the divisions stay in the kernel, as in torch's addcdiv path)
+	// elements [first, n) of the buffers (first is a multiple of 4): a rank that owns one shard of the flat buffer steps only that
 	const unsigned long long i4 = first + ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * 4ull;
 	if (i4 >= n) return;
-	const int k0 = act_seg(segs, i4);
+	const int k0 = adam_seg(segs, i4);
 	if (i4 + 4 <= n && i4 + 4 <= segs.end[k0]) {
 		// the float4 lies inside segment k0 (every float4 of a FlatParams layout does: its groups are padded to multiples of 4)
 		const unsigned int kind = segs.kind[k0] & ACT_KIND_MASK;
@@ -141,10 +95,10 @@ adam_act_kernel(float* __restrict__ raw, const float* __restrict__ grad, float* 
 			} else if (kind != GSR_ACT_NONE) {
 				g = make_float4(act_grad(kind, p.x, g.x), act_grad(kind, p.y, g.y), act_grad(kind, p.z, g.z), act_grad(kind, p.w, g.w));
 			}
-			adam_one_spelled(p.x, g.x, m.x, v.x, act_lr(segs, k0, i4), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-			adam_one_spelled(p.y, g.y, m.y, v.y, act_lr(segs, k0, i4 + 1), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-			adam_one_spelled(p.z, g.z, m.z, v.z, act_lr(segs, k0, i4 + 2), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
-			adam_one_spelled(p.w, g.w, m.w, v.w, act_lr(segs, k0, i4 + 3), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
+			adam_one(p.x, g.x, m.x, v.x, adam_lr(segs, k0, i4), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
+			adam_one(p.y, g.y, m.y, v.y, adam_lr(segs, k0, i4 + 1), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
+			adam_one(p.z, g.z, m.z, v.z, adam_lr(segs, k0, i4 + 2), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
+			adam_one(p.w, g.w, m.w, v.w, adam_lr(segs, k0, i4 + 3), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
 			*reinterpret_cast<float4*>(raw + i4) = p;
 			*reinterpret_cast<float4*>(exp_avg + i4) = m;
 			*reinterpret_cast<float4*>(exp_avg_sq + i4) = v;
@@ -161,14 +115,14 @@ adam_act_kernel(float* __restrict__ raw, const float* __restrict__ grad, float* 
 	// element here belongs to a NORMALIZE4 segment: those begin and end at multiples of 4, and so does a range bound other than n.
 	const unsigned long long stop = i4 + 4 < n ? i4 + 4 : n;
 	for (unsigned long long i = i4; i < stop; i++) {
-		const int k = act_seg(segs, i);
+		const int k = adam_seg(segs, i);
 		const unsigned int kind = segs.kind[k] & ACT_KIND_MASK;
 		if (kind == GSR_ACT_NORMALIZE4 || (STEP ? (segs.kind[k] & GSR_ACT_FROZEN) != 0 : kind == GSR_ACT_NONE)) continue;
 		float p = raw[i];
 		if (STEP) {
 			float g = grad[i], m = exp_avg[i], v = exp_avg_sq[i];
 			if (kind != GSR_ACT_NONE) g = act_grad(kind, p, g);
-			adam_one_spelled(p, g, m, v, act_lr(segs, k, i), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
+			adam_one(p, g, m, v, adam_lr(segs, k, i), b1, b2, eps, inv_bc1, inv_sqrt_bc2);
 			raw[i] = p; exp_avg[i] = m; exp_avg_sq[i] = v;
 			if (kind == GSR_ACT_NONE) continue;
 		}
@@ -176,8 +130,8 @@ adam_act_kernel(float* __restrict__ raw, const float* __restrict__ grad, float* 
 	}
 }
 
-// The checks both raw-parameter entries share, and the device-side table.  Returns 0 or GSR_E_INVALID (message set, naming `entry`).
-static int act_segments(const char* entry, const float* act, uint64_t n, uint64_t n_act, const gsr_act_segment* segments, int num_segments, ActSegs& s) {
+// The checks of the segment table every entry shares, and the device-side table.  Returns 0 or GSR_E_INVALID (message set, naming `entry`).
+static int adam_segments(const char* entry, const float* act, uint64_t n, uint64_t n_act, const gsr_act_segment* segments, int num_segments, AdamSegs& s) {
 	if (!segments || num_segments < 1 || num_segments > ADAM_MAX_SEG) {
 		set_error("%s: invalid argument (NULL segments, or not 1 to 16 of them)", entry);
 		return GSR_E_INVALID;
@@ -212,6 +166,37 @@ static int act_segments(const char* entry, const float* act, uint64_t n, uint64_
 	return 0;
 }
 
+// The host side of every Adam entry: all checks, the bias corrections, the one launch.  The buffers are device memory, and exp_avg /
+// exp_avg_sq may point in front of their allocation (a caller that keeps moments for its range alone moves them back by range_begin
+// elements): nothing is read from them here and the kernel touches [range_begin, range_end) only.
+static int adam_step(const char* entry, float* raw, const float* grad, float* exp_avg, float* exp_avg_sq, float* act, uint64_t n, uint64_t n_act,
+                     const gsr_act_segment* segments, int num_segments, float beta1, float beta2, float eps, int step, uint64_t range_begin,
+                     uint64_t range_end, hipStream_t stream) {
+	if (n == 0) return 0;
+	if (range_begin > range_end || range_end > n || (range_begin & 3u) != 0 || (range_end != n && (range_end & 3u) != 0)) {
+		set_error("%s: [range_begin, range_end) must lie inside [0, n) with multiples of 4 as bounds", entry);
+		return GSR_E_INVALID;
+	}
+	if (!raw || !grad || !exp_avg || !exp_avg_sq || step < 1) { set_error("%s: invalid argument (NULL buffer or step < 1)", entry); return GSR_E_INVALID; }
+	if ((((uintptr_t)raw | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15u) != 0) {
+		set_error("%s: buffers must be 16-byte aligned", entry);
+		return GSR_E_INVALID;
+	}
+	AdamSegs s;
+	if (int rc = adam_segments(entry, act, n, n_act, segments, num_segments, s)) return rc;
+	// bias corrections in double on the host, as Python floats are in torch/optim/adam.py
+	const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+	if (range_begin == range_end) return 0;
+	const unsigned long long nvec = (range_end - range_begin + 3) / 4;
+	{
+		StageTimer st_(GSR_STAGE_ADAM, stream);
+		adam_kernel<true><<<(unsigned)((nvec + 255) / 256), 256, 0, stream>>>(raw, grad, exp_avg, exp_avg_sq, act, range_begin, range_end, s, beta1, beta2, eps,
+		                                                                      (float)bc1, (float)sqrt(bc2));
+	}
+	GSR_LAUNCH_CHECK(0, stream);
+	return 0;
+}
+
 }  // namespace gsr
 
 using namespace gsr;
@@ -219,29 +204,27 @@ using namespace gsr;
 extern "C" int gsr_adam_act_step(float* raw, const float* grad, float* exp_avg, float* exp_avg_sq, float* act, uint64_t n, uint64_t n_act,
                                  const gsr_act_segment* segments, int num_segments, float beta1, float beta2, float eps, int step,
                                  uint64_t range_begin, uint64_t range_end, void* stream_) {
-	hipStream_t stream = (hipStream_t)stream_;
-	if (n == 0) return 0;
-	if (range_begin > range_end || range_end > n || (range_begin & 3u) != 0 || (range_end != n && (range_end & 3u) != 0)) {
-		set_error("gsr_adam_act_step: [range_begin, range_end) must lie inside [0, n) with multiples of 4 as bounds");
-		return GSR_E_INVALID;
+	return adam_step("gsr_adam_act_step", raw, grad, exp_avg, exp_avg_sq, act, n, n_act, segments, num_segments, beta1, beta2, eps, step, range_begin,
+	                 range_end, (hipStream_t)stream_);
+}
+
+// gsr_adam_step[_range] (include/gsr_hip.h): the same step with no segment activated
+extern "C" int gsr_adam_step_range(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, uint64_t n, const gsr_adam_segment* segments,
+                                   int num_segments, float beta1, float beta2, float eps, int step, uint64_t range_begin, uint64_t range_end,
+                                   void* stream_) {
+	gsr_act_segment table[ADAM_MAX_SEG];
+	const bool counted = segments && num_segments >= 1 && num_segments <= ADAM_MAX_SEG;      // (otherwise adam_step refuses the NULL table)
+	for (int i = 0; counted && i < num_segments; i++) {
+		const gsr_adam_segment& g = segments[i];
+		table[i] = gsr_act_segment{g.begin, g.end, g.lr, g.lr2, g.period, g.split, GSR_ACT_NONE, 0};
 	}
-	if (!raw || !grad || !exp_avg || !exp_avg_sq || step < 1) { set_error("gsr_adam_act_step: invalid argument (NULL buffer or step < 1)"); return GSR_E_INVALID; }
-	if ((((uintptr_t)raw | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15u) != 0) {
-		set_error("gsr_adam_act_step: buffers must be 16-byte aligned");
-		return GSR_E_INVALID;
-	}
-	ActSegs s;
-	if (int rc = act_segments("gsr_adam_act_step", act, n, n_act, segments, num_segments, s)) return rc;
-	const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);   // as gsr_adam_step_range
-	if (range_begin == range_end) return 0;
-	const unsigned long long nvec = (range_end - range_begin + 3) / 4;
-	{
-		StageTimer st_(GSR_STAGE_ADAM, stream);
-		adam_act_kernel<true><<<(unsigned)((nvec + 255) / 256), 256, 0, stream>>>(raw, grad, exp_avg, exp_avg_sq, act, range_begin, range_end, s, beta1, beta2,
-		                                                                          eps, (float)bc1, (float)sqrt(bc2));
-	}
-	GSR_LAUNCH_CHECK(0, stream);
-	return 0;
+	return adam_step("gsr_adam_step", param, grad, exp_avg, exp_avg_sq, nullptr, n, 0, counted ? table : nullptr, num_segments, beta1, beta2, eps, step,
+	                 range_begin, range_end, (hipStream_t)stream_);
+}
+
+extern "C" int gsr_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, uint64_t n, const gsr_adam_segment* segments,
+                             int num_segments, float beta1, float beta2, float eps, int step, void* stream_) {
+	return gsr_adam_step_range(param, grad, exp_avg, exp_avg_sq, n, segments, num_segments, beta1, beta2, eps, step, 0, n, stream_);
 }
 
 extern "C" int gsr_activate(const float* raw, float* act, uint64_t n, uint64_t n_act, const gsr_act_segment* segments, int num_segments, void* stream_) {
@@ -249,12 +232,12 @@ extern "C" int gsr_activate(const float* raw, float* act, uint64_t n, uint64_t n
 	if (n == 0) return 0;
 	if (!raw) { set_error("gsr_activate: invalid argument (NULL raw)"); return GSR_E_INVALID; }
 	if (((uintptr_t)raw & 15u) != 0) { set_error("gsr_activate: raw must be 16-byte aligned"); return GSR_E_INVALID; }
-	ActSegs s;
-	if (int rc = act_segments("gsr_activate", act, n, n_act, segments, num_segments, s)) return rc;
+	AdamSegs s;
+	if (int rc = adam_segments("gsr_activate", act, n, n_act, segments, num_segments, s)) return rc;
 	const unsigned long long nvec = (n + 3) / 4;
 	{
 		StageTimer st_(GSR_STAGE_ADAM, stream);
-		adam_act_kernel<false><<<(unsigned)((nvec + 255) / 256), 256, 0, stream>>>(const_cast<float*>(raw), nullptr, nullptr, nullptr, act, 0ull, n, s, 0.f, 0.f,
+		adam_kernel<false><<<(unsigned)((nvec + 255) / 256), 256, 0, stream>>>(const_cast<float*>(raw), nullptr, nullptr, nullptr, act, 0ull, n, s, 0.f, 0.f,
 		                                                                           0.f, 1.f, 1.f);
 	}
 	GSR_LAUNCH_CHECK(0, stream);
@@ -321,53 +304,4 @@ extern "C" int gsr_normal_loss_backward(const float* rend_normal, const float* s
 	normal_loss_bwd_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, stream>>>(rend_normal, surf_normal, mask, HW, g_sum, g_rend_normal, g_surf_normal);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
-}
-
-extern "C" int gsr_adam_step_range(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, uint64_t n, const gsr_adam_segment* segments,
-                                   int num_segments, float beta1, float beta2, float eps, int step, uint64_t range_begin, uint64_t range_end,
-                                   void* stream_) {
-	hipStream_t stream = (hipStream_t)stream_;
-	if (n == 0) return 0;
-	if (range_begin > range_end || range_end > n || (range_begin & 3u) != 0 || (range_end != n && (range_end & 3u) != 0)) {
-		set_error("gsr_adam_step_range: [range_begin, range_end) must lie inside [0, n) with multiples of 4 as bounds");
-		return GSR_E_INVALID;
-	}
-	if (!param || !grad || !exp_avg || !exp_avg_sq || !segments || num_segments < 1 || num_segments > ADAM_MAX_SEG || step < 1) {
-		set_error("gsr_adam_step: invalid argument (NULL buffer, step < 1 or more than 16 segments)");
-		return GSR_E_INVALID;
-	}
-	if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15u) != 0) {
-		set_error("gsr_adam_step: buffers must be 16-byte aligned");
-		return GSR_E_INVALID;
-	}
-	AdamSegs s;
-	memset(&s, 0, sizeof(s));
-	s.n = num_segments;
-	uint64_t prev = 0;
-	for (int i = 0; i < num_segments; i++) {
-		if (segments[i].begin != prev || segments[i].end < segments[i].begin || (segments[i].period != 0 && segments[i].split > segments[i].period)) {
-			set_error("gsr_adam_step: segments must tile [0, n) in order");
-			return GSR_E_INVALID;
-		}
-		prev = segments[i].end;
-		s.end[i] = segments[i].end; s.lr[i] = segments[i].lr; s.lr2[i] = segments[i].lr2;
-		s.period[i] = segments[i].period; s.split[i] = segments[i].split;
-	}
-	if (prev != n) { set_error("gsr_adam_step: segments must tile [0, n) in order"); return GSR_E_INVALID; }
-	// bias corrections in double on the host, as Python floats are in torch/optim/adam.py
-	const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-	if (range_begin == range_end) return 0;
-	const unsigned long long nvec = (range_end - range_begin + 3) / 4;
-	{
-		StageTimer st_(GSR_STAGE_ADAM, stream);
-		adam_kernel<<<(unsigned)((nvec + 255) / 256), 256, 0, stream>>>(param, grad, exp_avg, exp_avg_sq, range_begin, range_end, s, beta1, beta2, eps,
-		                                                               (float)bc1, (float)sqrt(bc2));
-	}
-	GSR_LAUNCH_CHECK(0, stream);
-	return 0;
-}
-
-extern "C" int gsr_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, uint64_t n, const gsr_adam_segment* segments,
-                             int num_segments, float beta1, float beta2, float eps, int step, void* stream_) {
-	return gsr_adam_step_range(param, grad, exp_avg, exp_avg_sq, n, segments, num_segments, beta1, beta2, eps, step, 0, n, stream_);
 }

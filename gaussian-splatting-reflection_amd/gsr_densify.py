@@ -11,7 +11,7 @@ copies of the split children, each in index order.
 import torch
 
 from _gsr import GatherGroup, check, lib, ptr, stream_ptr
-from gsr_train import FlatParams, GaussianTrainState, RawTrainState
+from gsr_train import RawTrainState, copy_groups
 
 PER_GAUSSIAN = ("means3D", "shs", "opacities", "scales", "rotations", "refl_strengths")
 
@@ -145,11 +145,10 @@ def densify_and_prune(state, stats, max_grad, min_opacity, mean, extent, max_scr
     map_moment = torch.where(is_new[keep], torch.full_like(map_param, -1), map_param).contiguous()
     # -- one gather per flat buffer into a new store of P1 rows
     shapes = {kk: ((P1,) + old.shapes[kk][1:] if kk in names else old.shapes[kk]) for kk in old.names}
-    world = 1 if state.shard is None else state.shard[1]
-    new = FlatParams(None, dev, shapes=shapes, shards=world)             # (padded to `world` equal 16-byte-aligned chunks, as the old store was)
-    # (the class of the state given: a gsr_train.RawTrainState, whose "scales" are the log-scales read above, stays one)
-    new_state = type(state)(None, dev, spatial_lr_scale=state.spatial_lr_scale, lrs=state.lrs, _params=new, shard=state.shard)
-    opt_old, opt_new = state.optimizer, new_state.optimizer
+    # (the class of the state given: a gsr_train.RawTrainState, whose "scales" are the log-scales read above, stays one; learning rates,
+    # step count, betas, eps, frozen groups and the shard are carried over)
+    new_state = state.successor(shapes)
+    new, opt_new = new_state.params, new_state.optimizer
     old_avg, old_sq = _whole_moments(state, group)
     sharded = opt_new.owned != (0, new.total)
     new_avg = torch.zeros(new.total, dtype=torch.float32, device=dev) if sharded else opt_new.exp_avg
@@ -163,22 +162,13 @@ def densify_and_prune(state, stats, max_grad, min_opacity, mean, extent, max_scr
             child_keep = keep[is_child]
             new.p["means3D"][kept_child] = child_xyz[child_keep]
             new.p["scales"][kept_child] = child_scaling[child_keep]
-        for kk in old.names:                                                            # the "env" group is left alone (:462)
-            if kk not in names:
-                a, b = old.slices[kk]
-                c, d = new.slices[kk]
-                new.flat[c:d].copy_(old.flat[a:b])
-                new_avg[c:d].copy_(old_avg[a:b])
-                new_sq[c:d].copy_(old_sq[a:b])
+        # the "env" group is left alone (:462)
+        copy_groups(((old.flat, new.flat), (old_avg, new_avg), (old_sq, new_sq)), old, new, [kk for kk in old.names if kk not in names])
         if sharded:                                                                     # this rank's chunk of the new layout
             a2, b2 = opt_new.owned
             opt_new.exp_avg.copy_(new_avg[a2:b2])
             opt_new.exp_avg_sq.copy_(new_sq[a2:b2])
-    opt_new.step_count = opt_old.step_count
-    for kk in opt_old.groups:
-        opt_new.groups[kk] = opt_old.groups[kk]
-    if isinstance(new_state, RawTrainState):                                            # frozen groups stay frozen; activated copy of the new rows
-        opt_new.frozen = set(opt_old.frozen)
+    if isinstance(new_state, RawTrainState):                                            # activated copy of the new rows
         opt_new.activate()
     info = dict(pruned_by_weight=P0 - int(idx_a.numel()), cloned=int(clones.numel()), split=k, pruned_big=int((~keep).sum()), before=P0, after=P1)
     return new_state, DensifyStats(P1, dev), info

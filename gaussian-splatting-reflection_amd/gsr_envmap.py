@@ -12,15 +12,9 @@ import torch
 
 import _gsr
 from _gsr import check, lib, stream_ptr
-from gsr_train import FlatParams, RawTrainState
+from gsr_train import RawTrainState, copy_groups
 
 SHARPEN_CLAMP = (1e-3, 1 - 1e-3)      # cubemap_encoder.py:112 of the reference
-
-
-def _require_envmap_entries():
-    if not hasattr(lib, "gsr_envmap_resize"):
-        raise ImportError("libgsr_hip.so does not export gsr_envmap_resize: it was built before the environment-map transforms "
-                          "(csrc/gsr_envmap.hip); rebuild with csrc/build.py --force.  There is no torch fallback.")
 
 
 def _check_state(state, what):
@@ -29,14 +23,7 @@ def _check_state(state, what):
     if state.shard is not None and state.shard[1] > 1:
         # a rank holds only its chunk of the moments, and the chunk borders move with the layout: gsr_densify._whole_moments territory
         raise NotImplementedError(f"{what} on a sharded state (shard=(rank, world_size)) is not implemented")
-    _require_envmap_entries()
-
-
-def _segment(params, name):
-    """(begin, end) of a group in the flat buffers with the padding that rides with it (what the fused Adam steps as that group)."""
-    i = params.names.index(name)
-    end = params.slices[params.names[i + 1]][0] if i + 1 < len(params.names) else params.total
-    return params.slices[name][0], end
+    _gsr.require_entry(lib, "gsr_envmap_resize", "csrc/gsr_envmap.hip")
 
 
 def resize_env_map(state, new_resolution):
@@ -67,30 +54,17 @@ def resize_env_map(state, new_resolution):
     dev = old.flat.device
     six, C, L = old.shapes["cubemap"][:3]
     shapes = {k: ((six, C, new_resolution, new_resolution) if k == "cubemap" else old.shapes[k]) for k in old.names}
-    world = 1 if state.shard is None else state.shard[1]
-    new = FlatParams(None, dev, shapes=shapes, shards=world)
-    new_state = type(state)(None, dev, spatial_lr_scale=state.spatial_lr_scale, lrs=state.lrs, _params=new, shard=state.shard)
-    opt_old, opt_new = state.optimizer, new_state.optimizer
+    new_state = state.successor(shapes)
+    new, opt_old, opt_new = new_state.params, state.optimizer, new_state.optimizer
     _gsr.side_join(dev)      # (the old cubemap gradient may still be in flight on the library's side stream: nothing of the old state is freed under it)
-    with torch.no_grad():
-        for k in old.names:
-            if k == "cubemap":
-                continue
-            (a, b), (c, d) = _segment(old, k), _segment(new, k)
-            n = min(b - a, d - c)      # (the last group's padding may differ; what lies beyond the shorter one is padding on both sides)
-            for src, dst in ((old.flat, new.flat), (state.grads.flat, new_state.grads.flat), (opt_old.exp_avg, opt_new.exp_avg),
-                             (opt_old.exp_avg_sq, opt_new.exp_avg_sq)):
-                dst[c:c + n].copy_(src[a:a + n])
-        a, c = old.slices["cubemap"][0], new.slices["cubemap"][0]
-        with torch.cuda.device(dev):
-            check(lib.gsr_envmap_resize(old.flat.data_ptr() + 4 * a, new.flat.data_ptr() + 4 * c, six * C, L, new_resolution, stream_ptr(dev)),
-                  "gsr_envmap_resize")
-        # (the texture's gradient slot and moments are the zeros the new buffers were made of)
-    opt_new.step_count, opt_new.betas, opt_new.eps = opt_old.step_count, opt_old.betas, opt_old.eps
-    for k in opt_old.groups:
-        opt_new.groups[k] = opt_old.groups[k]
+    copy_groups(((old.flat, new.flat), (state.grads.flat, new_state.grads.flat), (opt_old.exp_avg, opt_new.exp_avg),
+                 (opt_old.exp_avg_sq, opt_new.exp_avg_sq)), old, new, [k for k in old.names if k != "cubemap"], segments=True)
+    a, c = old.slices["cubemap"][0], new.slices["cubemap"][0]
+    with torch.cuda.device(dev):
+        check(lib.gsr_envmap_resize(old.flat.data_ptr() + 4 * a, new.flat.data_ptr() + 4 * c, six * C, L, new_resolution, stream_ptr(dev)),
+              "gsr_envmap_resize")
+    # (the texture's gradient slot and moments are the zeros the new buffers were made of)
     if isinstance(new_state, RawTrainState):
-        opt_new.frozen = set(opt_old.frozen)
         with torch.no_grad():
             opt_new.act.copy_(opt_old.act)      # the activated groups lie in front of the texture: one layout for both
     return new_state
@@ -111,7 +85,6 @@ def filter_env_map(state, factor=2.0):
     dev = params.flat.device
     six, C, L = params.shapes["cubemap"][:3]
     a, b = params.slices["cubemap"]
-    end = _segment(params, "cubemap")[1]
     with torch.no_grad():
         tex = params.flat[a:b]
         scratch = torch.empty_like(tex)
@@ -119,6 +92,5 @@ def filter_env_map(state, factor=2.0):
             check(lib.gsr_envmap_sharpen(tex.data_ptr(), scratch.data_ptr(), six * C, L, float(factor), SHARPEN_CLAMP[0], SHARPEN_CLAMP[1],
                                          stream_ptr(dev)), "gsr_envmap_sharpen")
         tex.copy_(scratch)
-        opt.exp_avg[a:end].zero_()
-        opt.exp_avg_sq[a:end].zero_()
+    opt.zero_moments("cubemap")
     return state

@@ -79,6 +79,23 @@ class FlatParams:
         a, b = self.slices[name]
         return flat[a:b].view(self.shapes[name])
 
+    def segment(self, name):
+        """(begin, end) of a group in the flat buffers with the padding that rides with it (what the fused Adam steps as that group): the
+        next group's begin is its end, the last group ends at `total`."""
+        i = self.names.index(name)
+        return self.slices[name][0], (self.slices[self.names[i + 1]][0] if i + 1 < len(self.names) else self.total)
+
+
+def copy_groups(pairs, old, new, names, segments=False):
+    """dst <- src for the groups `names` in every (src, dst) pair of flat buffers laid out as `old` and `new` (FlatParams): each group's
+    slice, or with `segments` its segment, padding included."""
+    with torch.no_grad():
+        for k in names:
+            (a, b), (c, d) = (old.segment(k), new.segment(k)) if segments else (old.slices[k], new.slices[k])
+            n = min(b - a, d - c)      # (the last group's padding may differ; what lies beyond the shorter one is padding on both sides)
+            for src, dst in pairs:
+                dst[c:c + n].copy_(src[a:a + n])
+
 
 class FlatAdam:
     """torch.optim.Adam(l, lr=0.0, eps=1e-15) of scene/gaussian_model.py:196-209 over FlatParams, one kernel launch
@@ -103,29 +120,39 @@ class FlatAdam:
         g = self.groups[name]
         self.groups[name] = (float(lr),) + tuple(g[1:])
 
-    def _segments(self):
+    def _table(self, struct, extra=lambda name: ()):
+        """The segment table of the layout: one `struct` (begin, end, lr, lr2, period, split, *extra(name)) per group."""
         names = self.params.names
-        segs = (AdamSegment * len(names))()
-        for i, k in enumerate(names):
-            a, _ = self.params.slices[k]
-            end = self.params.slices[names[i + 1]][0] if i + 1 < len(names) else self.params.total   # padding rides with the group
-            lr, lr2, period, split = self.groups[k]
-            segs[i] = AdamSegment(a, end, lr, lr2, period, split)
-        return segs
+        return (struct * len(names))(*[struct(*self.params.segment(k), *self.groups[k], *extra(k)) for k in names])
+
+    def _segments(self):
+        return self._table(AdamSegment)
+
+    def zero_moments(self, name):
+        """Both moments of one group zeroed, padding included (replace_tensor_to_optimizer, scene/gaussian_model.py:395-408): the part of
+        the group's segment that lies in the owned range."""
+        (a, b), (lo, hi) = self.params.segment(name), self.owned
+        a, b = max(a, lo) - lo, max(min(b, hi), lo) - lo
+        self.exp_avg[a:b].zero_()
+        self.exp_avg_sq[a:b].zero_()
+
+    def _launch(self, buffers, rest):
+        """(status, name) of the entry that takes the step: `buffers` are the pointers of param, grad, exp_avg and exp_avg_sq, `rest` every
+        argument behind the segment table."""
+        segs = self._segments()
+        return lib.gsr_adam_step_range(*buffers, self.params.total, segs, len(segs), *rest), "gsr_adam_step"
 
     def step(self):
         """One Adam step over the owned range (the whole buffer unless `owned` was given)."""
         self.step_count += 1
-        segs = self._segments()
         dev = self.params.flat.device
         _gsr.side_join(dev)      # (the cubemap gradient may still be in flight on the library's side stream)
         a, b = self.owned
         # the kernel indexes all four buffers with the GLOBAL element index; the moment buffers only exist for [a, b), so their base
         # pointers are moved back by `a` elements (a is a multiple of 4: still 16-byte aligned; nothing outside [a, b) is touched)
+        buffers = (self.params.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr() - 4 * a, self.exp_avg_sq.data_ptr() - 4 * a)
         with torch.cuda.device(dev):
-            check(lib.gsr_adam_step_range(self.params.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr() - 4 * a,
-                                          self.exp_avg_sq.data_ptr() - 4 * a, self.params.total, segs, len(segs), self.betas[0], self.betas[1],
-                                          self.eps, self.step_count, a, b, stream_ptr(dev)), "gsr_adam_step")
+            check(*self._launch(buffers, (self.betas[0], self.betas[1], self.eps, self.step_count, a, b, stream_ptr(dev))))
 
 
 class GaussianTrainState:
@@ -162,6 +189,16 @@ class GaussianTrainState:
     def _make_optimizer(self, groups, owned):
         return FlatAdam(self.params, self.grads.flat, groups, owned=owned)
 
+    def successor(self, shapes):
+        """A state of this class on a new layout (`shapes`: name -> shape, in the order of the groups; the same shard count) that goes on
+        where this one stands: spatial_lr_scale, lrs, shard, optimizer.groups (the scheduled means3D rate included), step_count, betas and
+        eps are carried over.  Parameters, gradient slots and moments are zero: filling them is the caller's part."""
+        new = FlatParams(None, self.params.flat.device, shapes=shapes, shards=1 if self.shard is None else self.shard[1])
+        st = type(self)(None, new.flat.device, spatial_lr_scale=self.spatial_lr_scale, lrs=self.lrs, _params=new, shard=self.shard)
+        old, opt = self.optimizer, st.optimizer
+        opt.groups, opt.step_count, opt.betas, opt.eps = dict(old.groups), old.step_count, old.betas, old.eps
+        return st
+
     def update_learning_rate(self, iteration):
         # scene/gaussian_model.py:215-221
         v = self.xyz_scheduler_args(iteration)
@@ -187,7 +224,7 @@ class GaussianTrainState:
             # every rank would add the whole term to its buffer and the reduce-scatter would sum it world_size times
             raise NotImplementedError("refl_scope_loss on a sharded state (shard=(rank, world_size)) is not implemented")
         from utils import loss_utils as lu
-        lu._require_scope_entries()
+        _gsr.require_entry(lu.lib, "gsr_env_scope_forward", "csrc/gsr_scope.hip")
         with torch.no_grad():
             x = lu._scope_xyz(self.p["means3D"])
             refl = self._activated("refl_strengths").detach()
@@ -210,47 +247,27 @@ def inverse_sigmoid(x):
     return torch.log(x / (1 - x))
 
 
-def _require_train_entries():
-    if not hasattr(lib, "gsr_adam_act_step"):
-        raise ImportError(f"{_gsr.LIB_PATH} was built before the raw-parameter step (gsr_adam_act_step, include/gsr_hip_train.h): rebuild it. "
-                          "There is no torch fallback.")
-
-
 class RawAdam(FlatAdam):
     """FlatAdam over RAW parameters: `act` is the compact activated buffer, `act_slices[name] = (begin, end)` the place of each activated
     group in it (multiples of 4, as long as the group's segment of the flat buffer, padding included).  step() is one launch of
     gsr_adam_act_step; activate() fills `act` from the raw buffer alone (gsr_activate)."""
 
     def __init__(self, params, grads_flat, groups, act, act_slices, betas=(0.9, 0.999), eps=1e-15):
-        _require_train_entries()
+        _gsr.require_entry(lib, "gsr_adam_act_step", "csrc/gsr_train.hip")
         super().__init__(params, grads_flat, groups, betas=betas, eps=eps)
         if act.data_ptr() % 16:
             raise ValueError("the activated buffer must be 16-byte aligned")
         self.act, self.act_slices, self.frozen = act, dict(act_slices), set()
 
     def _act_segments(self):
-        names = self.params.names
-        segs = (_gsr.ActSegment * len(names))()
-        for i, k in enumerate(names):
-            a, _ = self.params.slices[k]
-            end = self.params.slices[names[i + 1]][0] if i + 1 < len(names) else self.params.total   # padding rides with the group
-            lr, lr2, period, split = self.groups[k]
+        def kind_and_place(k):
             kind = ACTIVATIONS.get(k, _gsr.GSR_ACT_NONE) if k in self.act_slices else _gsr.GSR_ACT_NONE
-            if k in self.frozen:
-                kind |= _gsr.GSR_ACT_FROZEN
-            segs[i] = _gsr.ActSegment(a, end, lr, lr2, period, split, kind, self.act_slices[k][0] if k in self.act_slices else 0)
-        return segs
+            return kind | (_gsr.GSR_ACT_FROZEN if k in self.frozen else 0), self.act_slices[k][0] if k in self.act_slices else 0
+        return self._table(_gsr.ActSegment, kind_and_place)
 
-    def step(self):
-        self.step_count += 1
+    def _launch(self, buffers, rest):
         segs = self._act_segments()
-        dev = self.params.flat.device
-        _gsr.side_join(dev)      # (the cubemap gradient may still be in flight on the library's side stream)
-        n = self.params.total
-        with torch.cuda.device(dev):
-            check(lib.gsr_adam_act_step(self.params.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                        self.act.data_ptr(), n, self.act.numel(), segs, len(segs), self.betas[0], self.betas[1], self.eps,
-                                        self.step_count, 0, n, stream_ptr(dev)), "gsr_adam_act_step")
+        return lib.gsr_adam_act_step(*buffers, self.act.data_ptr(), self.params.total, self.act.numel(), segs, len(segs), *rest), "gsr_adam_act_step"
 
     def activate(self):
         """act = act(raw): at construction, after densification and after a reset."""
@@ -300,7 +317,7 @@ class RawTrainState(GaussianTrainState):
         if shard is not None:
             raise NotImplementedError("RawTrainState(shard=...): the sharded exchange of the activated copy is not implemented; "
                                       "gsr_adam_act_step takes a range for it")
-        _require_train_entries()
+        _gsr.require_entry(lib, "gsr_adam_act_step", "csrc/gsr_train.hip")
         super().__init__(tensors, device, spatial_lr_scale=spatial_lr_scale, lrs=lrs, _params=_params, shard=None)
         self.a = {}
         for k, (a, b) in self.optimizer.act_slices.items():
@@ -310,13 +327,12 @@ class RawTrainState(GaussianTrainState):
         self.optimizer.activate()
 
     def _make_optimizer(self, groups, owned):
-        names, act_slices, off = self.params.names, {}, 0
-        for i, k in enumerate(names):
+        act_slices, off = {}, 0
+        for k in self.params.names:
             if k in self.ACTIVATED:
-                end = self.params.slices[names[i + 1]][0] if i + 1 < len(names) else self.params.total
-                n = end - self.params.slices[k][0]
-                act_slices[k] = (off, off + n)
-                off += n
+                a, b = self.params.segment(k)
+                act_slices[k] = (off, off + b - a)
+                off += b - a
         act = torch.zeros(max(off, 4), dtype=torch.float32, device=self.params.flat.device)
         return RawAdam(self.params, self.grads.flat, groups, act, act_slices)
 
@@ -337,6 +353,11 @@ class RawTrainState(GaussianTrainState):
         with torch.no_grad():
             for k, view in st.a.items():
                 view.copy_(tensors[k].reshape(view.shape))
+        return st
+
+    def successor(self, shapes):
+        st = super().successor(shapes)
+        st.optimizer.frozen = set(self.optimizer.frozen)      # (the activated copy is the caller's part, as the parameters are)
         return st
 
     def render_inputs(self):
@@ -364,14 +385,9 @@ class RawTrainState(GaussianTrainState):
     def _replace(self, name, new_raw):
         """replace_tensor_to_optimizer (scene/gaussian_model.py:395-408): new raw values, both moments of the group zeroed; then the
         activated copy is refreshed."""
-        names = self.params.names
-        i = names.index(name)
-        a = self.params.slices[name][0]
-        end = self.params.slices[names[i + 1]][0] if i + 1 < len(names) else self.params.total
         with torch.no_grad():
             self.p[name].copy_(new_raw)
-            self.optimizer.exp_avg[a:end].zero_()
-            self.optimizer.exp_avg_sq[a:end].zero_()
+        self.optimizer.zero_moments(name)
         self.optimizer.activate()
 
     def reset_opacity(self, reset_value=0.01, exclusive_msk=None):

@@ -13,7 +13,7 @@ import weakref
 import torch
 from torch.autograd.function import once_differentiable
 
-from _gsr import check, check_sink_tensor, f32c, lib, ptr, require_cuda, stream_ptr
+from _gsr import check, check_sink_tensor, f32c, lib, ptr, require_cuda, require_entry, stream_ptr
 
 if not hasattr(lib, "gsr_photometric_forward"):
     raise ImportError("libgsr_hip.so does not export gsr_photometric_forward: it was built before the composited loss "
@@ -323,12 +323,6 @@ def normal_consistency_loss(rend_normal, surf_normal, lambda_normal=1.0, env_sco
 # ------------------------------------------------------------------------------------------- env scope (opt.use_env_scope)
 # train.py:56-63, 176-179 of the reference: the sphere test of every Gaussian centre and the reflection-mask loss over the centres outside
 # it, on gsr_env_scope_forward / _backward (include/gsr_hip_scope.h): one pass over the points each way and no host read.
-def _require_scope_entries():
-    if not hasattr(lib, "gsr_env_scope_forward"):
-        raise ImportError("libgsr_hip.so does not export gsr_env_scope_forward: it was built before the env-scope pass "
-                          "(csrc/gsr_scope.hip); rebuild with csrc/build.py --force.  There is no torch fallback.")
-
-
 def _scope_sphere(center, radius):
     """(cx, cy, cz, radius2) as the Python floats the library takes by value; ctypes rounds them to float32 exactly as
     `torch.tensor(center)` and torch's comparison against the Python float `radius ** 2` do.  A tensor centre is read on the host
@@ -377,7 +371,7 @@ def env_scope_masks(xyz, center, radius):
         outside = ((xyz - center[None]) ** 2).sum(-1) > radius ** 2      (train.py:61-63, get_outside_msk)
     with the float32 roundings of those expressions.  Neither is the other's negation: a centre exactly on the sphere or with a NaN
     coordinate is in neither.  `center`: three numbers (passed by value: no device copy) or a tensor."""
-    _require_scope_entries()
+    require_entry(lib, "gsr_env_scope_forward", "csrc/gsr_scope.hip")
     x = _scope_xyz(xyz)
     inside, outside, _ = _scope_forward(x, None, _scope_sphere(center, radius))
     return inside, outside
@@ -422,7 +416,7 @@ def refl_scope_loss(refl, xyz, center, radius, grad_sink=None, accumulate=False)
     grad_sink: a contiguous float32 tensor of refl's shape; the backward then writes (accumulate=False: every element, zeros where the
     point is not outside) or adds (accumulate=True: outside rows only) dL/drefl straight into it and autograd receives None for refl —
     the semantics of the rasterizer's sinks (_raster_api.GradSink)."""
-    _require_scope_entries()
+    require_entry(lib, "gsr_env_scope_forward", "csrc/gsr_scope.hip")
     if accumulate and grad_sink is None:
         raise ValueError("refl_scope_loss: accumulate=True needs a grad_sink to add to")
     require_cuda(refl, "refl")

@@ -14,8 +14,8 @@
  * dL/d(activated) in the gradient slots of those segments; the step turns it into dL/d(raw) in registers.
  *
  * Per element i of a segment of kind K, with r = raw[i], g = grad[i]:
- *   GSR_ACT_NONE        nothing is written to act; g enters Adam as it is.  Bit for bit the update of gsr_adam_step_range wherever that
- *                       entry updates four floats at once (everywhere but the last n % 4 floats: all of a layout padded to multiples of 4).
+ *   GSR_ACT_NONE        nothing is written to act; g enters Adam as it is.  Bit for bit the update of gsr_adam_step_range (one kernel
+ *                       serves both entries).
  *   GSR_ACT_SIGMOID     a = 1 / (1 + exp(-r));  g * a * (1 - a) enters Adam
  *   GSR_ACT_EXP         a = exp(r);             g * a enters Adam
  *   GSR_ACT_NORMALIZE4  rows of four: a = q / max(|q|, 1e-12);  |q| > 1e-12: (g - a (a . g)) / |q| enters Adam, otherwise g / 1e-12

@@ -110,13 +110,15 @@ def test_densify_and_prune_on_a_sharded_state(world, monkeypatch):
     """A state built with shard=(rank, N) (gsr_dist.ShardedStep) holds 1 / N of the Adam moments; densification permutes rows of the whole
     moment buffers.  Every rank of a (here: emulated) group densifies its own state; the all-gather of the moment chunks is stood in for
     by concatenating the ranks' chunks.  Result: the same parameters as the unsharded state on every rank, and each rank's new moment
-    chunk = that range of the unsharded state's new moments (the two layouts differ only in the padding at the very end)."""
+    chunk = that range of the unsharded state's new moments (the two layouts differ only in the padding at the very end).  Betas and eps
+    other than the defaults come through on both, as step_count does."""
     import gsr_densify
     from gsr_densify import DensifyStats, densify_and_prune
     from gsr_train import GaussianTrainState
     P = 9001                                            # odd: chunk borders fall inside parameter groups
     sc, plain, stats, names = _setup(P, 11, -3.2)
     tensors = {k: plain.p[k].detach().cpu() for k in plain.params.names}
+    plain.optimizer.betas, plain.optimizer.eps = (0.8, 0.99), 1e-8
     shards = [GaussianTrainState(tensors, "cuda", shard=(r, world)) for r in range(world)]
     total, n = shards[0].params.total, shards[0].params.total // world
     assert total % (4 * world) == 0 and total >= plain.params.total
@@ -125,7 +127,7 @@ def test_densify_and_prune_on_a_sharded_state(world, monkeypatch):
         whole = torch.cat([plain.optimizer.exp_avg, torch.zeros(pad, device="cuda")]), torch.cat([plain.optimizer.exp_avg_sq, torch.zeros(pad, device="cuda")])
         st.optimizer.exp_avg.copy_(whole[0][r * n:(r + 1) * n])
         st.optimizer.exp_avg_sq.copy_(whole[1][r * n:(r + 1) * n])
-        st.optimizer.step_count = 17
+        st.optimizer.step_count, st.optimizer.betas, st.optimizer.eps = 17, (0.8, 0.99), 1e-8
         assert st.optimizer.exp_avg.numel() == n
     rs = np.random.RandomState(5)
     denom = rs.randint(0, 5, P).astype(np.float32)
@@ -149,11 +151,13 @@ def test_densify_and_prune_on_a_sharded_state(world, monkeypatch):
     k = info["split"]
     ref, _, info = densify_and_prune(plain, fill(plain), 0.0002, 0.05, torch.zeros(3), 3.0, 20, noise=noise[:2 * k])
     assert info["split"] == k > 20 and info["cloned"] > 20
+    assert (ref.optimizer.betas, ref.optimizer.eps, ref.optimizer.step_count) == ((0.8, 0.99), 1e-8, 17)
     monkeypatch.setattr(gsr_densify, "_whole_moments", lambda state, group: (torch.cat([s.optimizer.exp_avg for s in shards]),
                                                                              torch.cat([s.optimizer.exp_avg_sq for s in shards])))
     for r, st in enumerate(shards):
         new, new_stats, inf = densify_and_prune(st, fill(st), 0.0002, 0.05, torch.zeros(3), 3.0, 20, noise=noise[:2 * k])
         assert inf == info and new.shard == (r, world) and new.params.total % (4 * world) == 0
+        assert (new.optimizer.betas, new.optimizer.eps, new.optimizer.step_count) == ((0.8, 0.99), 1e-8, 17)
         for kk in new.params.names:
             assert torch.equal(new.p[kk].detach(), ref.p[kk].detach()), kk
         a, b = new.optimizer.owned

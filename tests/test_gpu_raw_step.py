@@ -300,6 +300,40 @@ def test_non_default_stream_and_activate_alone():
     assert before == {k: u32(a[k].cpu().numpy()).tobytes() for k in a}
 
 
+def test_both_entries_agree_on_odd_borders_and_the_tail():
+    """gsr_adam_step_range beside gsr_adam_act_step with the same table as GSR_ACT_NONE and act = NULL, where the layouts above never put
+    them: n = 4099 (a tail of 3) and three segments with odd borders, so that float4s straddle them; the middle one has two rates by
+    position.  Three steps: parameters and both moments bit-identical over all n floats, the float behind each buffer untouched."""
+    import _gsr
+    n = 4099
+    table = [(0, 1001, 0.05, 0.0, 0, 0), (1001, 2050, 0.0025, 0.000125, 7, 3), (2050, n, 0.001, 0.0, 0, 0)]
+    plain = (_gsr.AdamSegment * 3)(*[_gsr.AdamSegment(*s) for s in table])
+    none = (_gsr.ActSegment * 3)(*[_gsr.ActSegment(*s, _gsr.GSR_ACT_NONE, 0) for s in table])
+    rs = np.random.RandomState(4100)
+    raw0 = torch.from_numpy(rs.randn(n).astype(np.float32))
+    guard = 1.25
+    stores = [{k: torch.full((n + 1,), guard, device="cuda") for k in ("raw", "grad", "m", "v")} for _ in range(2)]
+    for store in stores:
+        store["raw"][:n].copy_(raw0)
+        store["m"][:n].zero_()
+        store["v"][:n].zero_()
+    a, b = stores
+    stream = _gsr.stream_ptr(a["raw"].device)
+    for step in range(1, 4):
+        g = torch.from_numpy((1e-3 * rs.randn(n) * (rs.rand(n) >= 0.1)).astype(np.float32))
+        for store in stores:
+            store["grad"][:n].copy_(g)
+        _gsr.check(_gsr.lib.gsr_adam_step_range(a["raw"].data_ptr(), a["grad"].data_ptr(), a["m"].data_ptr(), a["v"].data_ptr(), n, plain, 3, B1, B2,
+                                                1e-15, step, 0, n, stream), "gsr_adam_step_range")
+        _gsr.check(_gsr.lib.gsr_adam_act_step(b["raw"].data_ptr(), b["grad"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), None, n, 0, none, 3, B1, B2,
+                                              1e-15, step, 0, n, stream), "gsr_adam_act_step")
+        torch.cuda.synchronize()
+        for q in ("raw", "m", "v"):
+            assert u32(a[q][:n].cpu().numpy()).tobytes() == u32(b[q][:n].cpu().numpy()).tobytes(), (q, step)
+        assert not torch.equal(a["raw"][:n].cpu(), raw0)
+        assert all(float(x[n]) == guard for store in stores for x in store.values())
+
+
 def test_one_sigmoid_segment_of_4099_floats_reaches_the_scalar_tail():
     """A direct call: n = 4099 = 4 * 1024 + 3, one SIGMOID segment; the last three elements take the one-element path.  Three steps against the
     restatement, bounds as above; the activated buffer is exactly n floats long and the float behind `raw`'s last is not touched."""
