@@ -104,10 +104,34 @@ def pixel_grid(W, H, dtype):
     return px, py
 
 
+class _ValueWithGradientTo(torch.autograd.Function):
+    """Returns `value` unchanged (the same bits) and sends the incoming gradient to `route` instead: the forward of one expression with
+    the backward of another, for the places where the reference's backward differentiates something its forward did not evaluate."""
+
+    @staticmethod
+    def forward(ctx, value, route):
+        return value.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, g
+
+
 def render_gauss(means, scales, rots, opac, shs, normals, refl, view, proj, campos, tanfovx, tanfovy, W, H, bg, degree=3, scale_modifier=1.0,
-                 antialiasing=False, xy_offset=None):
+                 antialiasing=False, xy_offset=None, reference_clamp_gradient=False):
     """Variant G (Appendix A.1): EWA-projected 3D Gaussians.  Returns dict(color [3,H,W], normal_map [3,H,W],
-    refl_strength_map [1,H,W], invdepth [1,H,W], radii [P], n_contrib [H,W])."""
+    refl_strength_map [1,H,W], invdepth [1,H,W], radii [P], n_contrib [H,W]) plus clamped_x / clamped_y [P] bool.
+
+    reference_clamp_gradient: the frustum clamp of the projection Jacobian (DGR forward.cu computeCov2D / backward.cu
+    computeCov2DCUDA).  The forward replaces t.x by clamp(t.x / t.z, -1.3 tanfovx, 1.3 tanfovx) * t.z before it forms
+    J = [fx / t.z, 0, -fx t.x / t.z^2; ...].  Where the clamp is active t.x = lim * t.z is a function of t.z alone, so the true
+    derivatives of J[0][2] = -fx lim / t.z are 0 w.r.t. the view-space x and +fx lim / t.z^2 = fx t.x / t.z^3 w.r.t. t.z.  The
+    reference's backward multiplies dL/dt.x by x_grad_mul = 0 there — correct — but leaves its dL/dt.z formula as it stands for the
+    unclamped case, 2 fx t.x / t.z^3 * dL/dJ[0][2]: the derivative of -fx t.x / t.z^2 with t.x HELD CONSTANT at its clamped value,
+    twice the true one.  (The same for t.y.)  Holding a value constant is a detach: with the option on, a clamped coordinate enters J
+    as (lim * t.z).detach() and an unclamped one as the view-space coordinate itself, and autograd then returns what the reference
+    returns.  With the option off (plain autograd of the forward) the rows of dL_dmeans3D of clamped Gaussians differ; the covariance
+    gradient dL/dSigma = M^T dL/dcov M does not pass through dJ, so dL_dscales and dL_drotations are the same either way."""
     dt = means.dtype
     P = means.shape[0]
     A = view[:3, :3].T                                    # world -> view rotation for column vectors
@@ -123,8 +147,13 @@ def render_gauss(means, scales, rots, opac, shs, normals, refl, view, proj, camp
     # projection Jacobian at the (clamped) view-space position
     fx, fy = W / (2 * tanfovx), H / (2 * tanfovy)
     limx, limy = F(1.3) * tanfovx, F(1.3) * tanfovy
+    rx, ry = (p_view[:, 0] / tz).detach(), (p_view[:, 1] / tz).detach()
+    clamped_x, clamped_y = (rx < -limx) | (rx > limx), (ry < -limy) | (ry > limy)
     tx = torch.clamp(p_view[:, 0] / tz, -limx, limx) * tz
     ty = torch.clamp(p_view[:, 1] / tz, -limy, limy) * tz
+    if reference_clamp_gradient:
+        tx = torch.where(clamped_x, tx.detach(), p_view[:, 0])
+        ty = torch.where(clamped_y, ty.detach(), p_view[:, 1])
     zero = torch.zeros_like(tz)
     J = torch.stack([torch.stack([fx / tz, zero, -fx * tx / (tz * tz)], dim=1), torch.stack([zero, fy / tz, -fy * ty / (tz * tz)], dim=1)], dim=1)
     M = J @ A[None]
@@ -163,17 +192,26 @@ def render_gauss(means, scales, rots, opac, shs, normals, refl, view, proj, camp
     radii = torch.where(visible, radius, torch.zeros_like(radius)).to(torch.int32)
     colour_only = torch.einsum("phw,pc->chw", w, rgb)     # without the background term (used by the mean2D quirk test)
     return dict(color=color, normal_map=normal_map, refl_strength_map=refl_map, invdepth=invdepth, radii=radii, final_T=T_final,
-                color_nobg=colour_only)
+                color_nobg=colour_only, clamped_x=clamped_x, clamped_y=clamped_y)
 
 
 def render_surfel(means, scales, rots, opac, shs, refl, mask, view, proj, campos, tanfovx, tanfovy, W, H, bg, degree=3, scale_modifier=1.0,
-                  freeze_lowpass_depth=False, pair_path_only_T=False):
+                  freeze_lowpass_depth=False, pair_path_only_T=False, backward_size=None):
     """Variant S (Appendix A.3): 2D Gaussian surfels intersected per ray.  Returns dict(color [3,H,W], allmap [8,H,W],
     refl_strength_map [1,H,W], radii [P], gaussian_weights [P]).
 
     freeze_lowpass_depth: where the low-pass falloff wins (rho2d < rho3d) the reference's backward differentiates the depth
     with the ray-splat intersection point held constant (Appendix A.4); True restates that by detaching s there, so that
-    autograd reproduces the reference's depth / distortion gradients also on that branch."""
+    autograd reproduces the reference's depth / distortion gradients also on that branch.
+
+    backward_size = (Wb, Hb): the image size the reference's per-surfel backward believes in (DSR backward.cu:637-638).
+    The tile pass accumulates G = dL/dT against the forward's homography T = [L0|0; L1|0; p|1] . PV . ndc2pix(W, H).  The per-surfel
+    pass then rebuilds the homography from the inputs for W' = int(focal_x * tan_fovx * 2), H' = int(focal_y * tan_fovy * 2) — in
+    floating point often W - 1, H - 1 — adds the bounding-box-centre term to G using that T', and pulls the sum back to the mean, the
+    scales and the rotation through PV . ndc2pix(W', H').  So every gradient that passes through T is that of the forward evaluated at T
+    but differentiated as if T had been T': the values of the forward, the gradient routed into T' (and, for the centre, into the
+    centre expression evaluated at T').  The paths that do not pass through T (SH colour -> mean, normal -> rotation, opacity,
+    reflection strength) are untouched.  None: T' = T, plain autograd."""
     dt = means.dtype
     P = means.shape[0]
     p_view = means @ view[:3, :3] + view[3, :3]
@@ -186,8 +224,12 @@ def render_surfel(means, scales, rots, opac, shs, refl, mask, view, proj, campos
     # homography rows: (u, v, 1) -> (x w, y w, w) in pixels;  splat2world = [L0|0; L1|0; p|1] (3 x 4), then PV, then NDC -> pixel
     s2w = torch.stack([torch.cat([L0, torch.zeros(P, 1, dtype=dt)], 1), torch.cat([L1, torch.zeros(P, 1, dtype=dt)], 1),
                        torch.cat([means, torch.ones(P, 1, dtype=dt)], 1)], dim=1)                       # [P,3,4]
-    n2p = torch.tensor([[W / 2, 0, 0, (W - 1) / 2], [0, H / 2, 0, (H - 1) / 2], [0, 0, 0, 1]], dtype=dt).T   # [4,3]
-    Tm = s2w @ proj @ n2p                                  # [P,3,3]: Tm[:, i, j] = coefficient of local coordinate i in output j
+    n2p_of = lambda w, h: torch.tensor([[w / 2, 0, 0, (w - 1) / 2], [0, h / 2, 0, (h - 1) / 2], [0, 0, 0, 1]], dtype=dt).T   # [4,3]
+    Tm = s2w @ proj @ n2p_of(W, H)                         # [P,3,3]: Tm[:, i, j] = coefficient of local coordinate i in output j
+    Tm_bwd = None
+    if backward_size is not None:
+        Tm_bwd = s2w @ proj @ n2p_of(*backward_size)
+        Tm = _ValueWithGradientTo.apply(Tm, Tm_bwd)
     Tm.retain_grad() if Tm.requires_grad else None
     Tu, Tv, Tw = Tm[:, :, 0], Tm[:, :, 1], Tm[:, :, 2]
     normal = R[:, :, 2] @ view[:3, :3]                     # view-space normal
@@ -205,6 +247,10 @@ def render_surfel(means, scales, rots, opac, shs, refl, mask, view, proj, campos
     hy = torch.sqrt(torch.clamp(cy * cy - (f * Tv * Tv).sum(dim=1), min=F(1e-4)))
     radius = torch.ceil(torch.maximum(torch.maximum(hx, hy), torch.full_like(hx, 3.0 * F(0.707106))).detach())
     xy = torch.stack([cx, cy], dim=1)
+    if Tm_bwd is not None:          # the centre's gradient is formed from T' as well: the same expression, evaluated at T'
+        fb = t[None] / (t * Tm_bwd[:, :, 2] * Tm_bwd[:, :, 2]).sum(dim=1)[:, None]
+        xy_bwd = torch.stack([(fb * Tm_bwd[:, :, 0] * Tm_bwd[:, :, 2]).sum(dim=1), (fb * Tm_bwd[:, :, 1] * Tm_bwd[:, :, 2]).sum(dim=1)], dim=1)
+        xy = _ValueWithGradientTo.apply(xy.detach(), xy_bwd)
     if pair_path_only_T:            # gradient w.r.t. Tm then counts the per-pair use of T only, not the bounding-box centre
         xy = xy.detach()
     in_rect, nonempty = tile_rect_mask(xy.detach(), radius, W, H)

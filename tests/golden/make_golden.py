@@ -77,7 +77,39 @@ def camera_golden():
     np.savez(os.path.join(OUT, "camera_golden.npz"), **recs)
 
 
+def camera_hwk_golden():
+    """Pinhole cameras as a COLMAP reader hands them over: fx != fy, off-centre principal point, general pose (scene/cameras.py:40-69
+    with HWK given).  Inputs and the matrices the reference builds from them; tests/cameras.py hwk_camera is pinned against these."""
+    rs = np.random.RandomState(17)
+    recs = {}
+    sizes = [(200, 136), (48, 32), (1920, 1080), (800, 801), (211, 137), (640, 480)]
+    for i, (W, H) in enumerate(sizes):
+        q, _ = np.linalg.qr(rs.randn(3, 3))
+        if np.linalg.det(q) < 0:
+            q[:, 0] = -q[:, 0]
+        t = rs.randn(3) * 2.0
+        fy = H / (2 * math.tan(math.radians(rs.uniform(12, 110)) / 2))
+        fx = fy * (1.4 if i % 2 == 0 else 1 / 1.4) * rs.uniform(0.95, 1.05)
+        cx = W / 2.0 + rs.choice([-1, 1]) * rs.uniform(0.1, 0.2) * W
+        cy = H / 2.0 + rs.choice([-1, 1]) * rs.uniform(0.1, 0.2) * H
+        K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float64)
+        wvt = torch.tensor(getWorld2View2(q, t)).transpose(0, 1)
+        projc = getProjectionMatrixCorrect(0.01, 100.0, H, W, K).transpose(0, 1)
+        full = (wvt.unsqueeze(0).bmm(projc.unsqueeze(0))).squeeze(0)
+        recs[f"R{i}"] = q
+        recs[f"T{i}"] = t
+        recs[f"hwk{i}"] = np.array([W, H, fx, fy, cx, cy], dtype=np.float64)
+        recs[f"fov{i}"] = np.array([focal2fov(fx, W), focal2fov(fy, H)], dtype=np.float64)
+        recs[f"wvt{i}"] = wvt.numpy()
+        recs[f"projc{i}"] = projc.numpy()
+        recs[f"full{i}"] = full.numpy()
+        recs[f"center{i}"] = wvt.inverse()[3, :3].numpy()
+    recs["n"] = np.array(len(sizes))
+    np.savez(os.path.join(OUT, "camera_hwk_golden.npz"), **recs)
+
+
 if __name__ == "__main__":
-    sh_golden()
-    camera_golden()
+    which = sys.argv[1:] or ["sh", "camera", "camera_hwk"]
+    for name in which:
+        {"sh": sh_golden, "camera": camera_golden, "camera_hwk": camera_hwk_golden}[name]()
     print("written", sorted(os.listdir(OUT)))

@@ -294,10 +294,10 @@ def seam_camera(W=SEAM_W, H=SEAM_H):
     return S.look_at_camera(W, H, eye=(1.0, -0.5, -4.0))
 
 
-def seam_inputs(L, seed, W=SEAM_W, H=SEAM_H):
+def seam_inputs(L, seed, W=SEAM_W, H=SEAM_H, cam=None):
     """The targeted image of make_targets plus random base colour, strength, cubemap, fail value and upstream weights; `amb` marks the
-    ambiguous pixels (margin < DELTA)."""
-    cam = seam_camera(W, H)
+    ambiguous pixels (margin < DELTA).  cam: another camera of size W x H than seam_camera's."""
+    cam = seam_camera(W, H) if cam is None else cam
     t = make_targets(cam, W, H, L, seed)
     g = torch.Generator().manual_seed(1000 + seed)
     inp = dict(L=L, W=W, H=H, cam=cam, nv=t["nv"], kind=t["kind"],

@@ -1,12 +1,15 @@
 """The oracle against the dense float64 torch-autograd restatement (tests/dense_torch.py): a second pin that shares no
 code and no derivation with oracle/*.cpp — forward planes compared value by value, every TRUE gradient supplied by torch
 autograd.  Outputs of the reference that are not true gradients are left out here exactly as in
-test_oracle_fd.py and pinned by known answers in test_oracle_quirks.py.  CPU only, float64, 48 primitives, 32 x 32."""
+test_oracle_fd.py and pinned by known answers in test_oracle_quirks.py.  CPU only, float64, 48 primitives, 32 x 32 under the stock
+camera (fx == fy, centred principal point, a small rotation) and 48 x 32 / 32 x 48 under the general cameras of tests/cameras.py
+(fx != fy, off-centre principal point, rolled pose; the *_general_camera tests), at the same tolerances."""
 import numpy as np
 import pytest
 import torch
 
 import dense_torch as dn
+from cameras import backward_size, hwk_camera, rolled_pose
 from oracle import oracle as orc
 
 W = H = 32
@@ -38,6 +41,34 @@ def _camera(seed):
     return view, full, campos
 
 
+def _stock(seed):
+    return _camera(seed) + (TAN, TAN, W, H)
+
+
+GENERAL = ("aniso", "aniso_inv", "offcentre", "rolled", "all")
+
+
+def _general_camera(kind, seed):
+    """(view, full, campos, tanfovx, tanfovy, W, H) of a camera as the reference builds it from COLMAP intrinsics (tests/cameras.py):
+    fx != fy, off-centre principal point, rolled pose with a translation.  Focal lengths exact in binary, so that the surfel
+    backward's int(focal * tan * 2) returns W and H in double (asserted where it matters)."""
+    w, h = (32, 48) if kind == "aniso_inv" else (48, 32)
+    fx, fy = dict(aniso=(48.0, 32.0), aniso_inv=(32.0, 48.0), all=(64.0, 32.0)).get(kind, (32.0, 32.0))
+    cx, cy = (w / 2 + 0.15 * w, h / 2 - 0.12 * h) if kind in ("offcentre", "all") else (w / 2, h / 2)
+    R, T = rolled_pose(seed) if kind in ("rolled", "all") else (None, None)
+    cam = hwk_camera(w, h, fx, fy, cx, cy, R, T)
+    return (cam["viewmatrix"].astype(np.float64), cam["projmatrix"].astype(np.float64), cam["campos"].astype(np.float64), cam["tanfovx"],
+            cam["tanfovy"], w, h)
+
+
+def _in_view(p, cam):
+    """The scene of _scene, drawn for the stock camera's 53-degree frustum, placed in front of `cam`: its coordinates read as VIEW-space
+    ones, widened or narrowed to the camera's FoV, and mapped to world space with the inverse view."""
+    view, _, _, tanx, tany, _, _ = cam
+    pv = p["means3D"] * np.array([tanx / TAN, tany / TAN, 1.0])
+    return dict(p, means3D=(pv - view[3, :3]) @ np.linalg.inv(view[:3, :3]))
+
+
 def _scene(variant, P, seed, log_scale=-1.7):
     rs = np.random.RandomState(seed)
     means = np.stack([rs.uniform(-1.3, 1.3, P), rs.uniform(-1.3, 1.3, P), rs.uniform(2.5, 5.5, P)], 1)
@@ -66,20 +97,20 @@ def _assert_close(a, b, rtol, what):
     assert err <= rtol * scale, f"{what}: max abs diff {err:.3e} vs scale {scale:.3e}"
 
 
-@pytest.mark.parametrize("seed,antialiasing", [(0, False), (1, False), (2, True)])
-def test_gauss_forward_and_true_gradients(seed, antialiasing):
+def _gauss_case(seed, antialiasing, cam, place=False):
     P = 48
-    p = _scene("G", P, seed)
-    view, full, campos = _camera(seed)
+    view, full, campos, TANX, TANY, W, H = cam
+    p = _in_view(_scene("G", P, seed), cam) if place else _scene("G", P, seed)
     bg = np.array([0.2, 0.5, 0.3])
     o = orc.GaussOracle(np.float64)
-    ref = o.forward(bg=bg, means3D=p["means3D"], opacities=p["opacities"], viewmatrix=view, projmatrix=full, campos=campos, tanfovx=TAN,
-                    tanfovy=TAN, image_height=H, image_width=W, sh_degree=3, shs=p["shs"], normals=p["normals"],
+    ref = o.forward(bg=bg, means3D=p["means3D"], opacities=p["opacities"], viewmatrix=view, projmatrix=full, campos=campos, tanfovx=TANX,
+                    tanfovy=TANY, image_height=H, image_width=W, sh_degree=3, shs=p["shs"], normals=p["normals"],
                     refl_strengths=p["refl_strengths"], scales=p["scales"], rotations=p["rotations"], antialiasing=antialiasing)
     assert ref["num_rendered"] > 0
     t = {k: _t(p[k]) for k in ("means3D", "scales", "rotations", "opacities", "shs", "normals", "refl_strengths")}
     out = dn.render_gauss(t["means3D"], t["scales"], t["rotations"], t["opacities"], t["shs"], t["normals"], t["refl_strengths"],
-                          _t(view, False), _t(full, False), _t(campos, False), TAN, TAN, W, H, _t(bg, False), antialiasing=antialiasing)
+                          _t(view, False), _t(full, False), _t(campos, False), TANX, TANY, W, H, _t(bg, False), antialiasing=antialiasing,
+                          reference_clamp_gradient=True)
     np.testing.assert_array_equal(out["radii"].numpy(), ref["radii"])
     for k in ("color", "normal_map", "refl_strength_map", "invdepth"):
         _assert_close(out[k].detach().numpy(), ref[k], 1e-10, k)
@@ -102,20 +133,31 @@ def test_gauss_forward_and_true_gradients(seed, antialiasing):
         _assert_close(g[gk].reshape(p[k].shape), t[k].grad.numpy(), tol, gk)
 
 
-@pytest.mark.parametrize("seed", [0, 1, 2])
-def test_surfel_forward_and_true_gradients(seed):
+@pytest.mark.parametrize("seed,antialiasing", [(0, False), (1, False), (2, True)])
+def test_gauss_forward_and_true_gradients(seed, antialiasing):
+    _gauss_case(seed, antialiasing, _stock(seed))
+
+
+@pytest.mark.parametrize("kind", GENERAL)
+@pytest.mark.parametrize("seed,antialiasing", [(1, False), (2, True)])
+def test_gauss_forward_and_true_gradients_general_camera(seed, antialiasing, kind):
+    _gauss_case(seed, antialiasing, _general_camera(kind, seed), place=True)
+
+
+def _surfel_case(seed, cam, place=False):
     P = 48
-    p = _scene("S", P, seed)
-    view, full, campos = _camera(seed)
+    view, full, campos, TANX, TANY, W, H = cam
+    assert (backward_size(W, TANX, np.float64), backward_size(H, TANY, np.float64)) == (W, H)     # that quirk: test_oracle_quirks.py
+    p = _in_view(_scene("S", P, seed), cam) if place else _scene("S", P, seed)
     bg = np.array([0.2, 0.5, 0.3])
     o = orc.SurfelOracle(np.float64)
-    ref = o.forward(bg=bg, means3D=p["means3D"], opacities=p["opacities"], viewmatrix=view, projmatrix=full, campos=campos, tanfovx=TAN,
-                    tanfovy=TAN, image_height=H, image_width=W, sh_degree=3, shs=p["shs"], refl_strengths=p["refl_strengths"],
+    ref = o.forward(bg=bg, means3D=p["means3D"], opacities=p["opacities"], viewmatrix=view, projmatrix=full, campos=campos, tanfovx=TANX,
+                    tanfovy=TANY, image_height=H, image_width=W, sh_degree=3, shs=p["shs"], refl_strengths=p["refl_strengths"],
                     scales=p["scales"], rotations=p["rotations"], env_scope_mask=p["mask"])
     assert ref["num_rendered"] > 0
     t = {k: _t(p[k]) for k in ("means3D", "scales", "rotations", "opacities", "shs", "refl_strengths")}
     out = dn.render_surfel(t["means3D"], t["scales"], t["rotations"], t["opacities"], t["shs"], t["refl_strengths"],
-                           torch.from_numpy(p["mask"].astype(np.float64)), _t(view, False), _t(full, False), _t(campos, False), TAN, TAN, W, H,
+                           torch.from_numpy(p["mask"].astype(np.float64)), _t(view, False), _t(full, False), _t(campos, False), TANX, TANY, W, H,
                            _t(bg, False), freeze_lowpass_depth=True)
     np.testing.assert_array_equal(out["radii"].numpy(), ref["radii"])
     _assert_close(out["color"].detach().numpy(), ref["color"], 1e-10, "color")
@@ -137,6 +179,17 @@ def test_surfel_forward_and_true_gradients(seed):
     # input the true gradient (autograd, through the normalisation) is its projection onto the tangent space
     q, ga = p["rotations"], g["dL_drotations"]
     _assert_close(ga - q * (q * ga).sum(axis=1, keepdims=True), t["rotations"].grad.numpy(), 1e-7, "dL_drotations (tangential)")
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_surfel_forward_and_true_gradients(seed):
+    _surfel_case(seed, _stock(seed))
+
+
+@pytest.mark.parametrize("kind", GENERAL)
+@pytest.mark.parametrize("seed", [1, 2])
+def test_surfel_forward_and_true_gradients_general_camera(seed, kind):
+    _surfel_case(seed, _general_camera(kind, seed), place=True)
 
 
 def test_surfel_depth_gradient_is_a_true_gradient_on_the_ray_splat_branch():
