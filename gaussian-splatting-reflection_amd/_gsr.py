@@ -31,6 +31,12 @@ class GatherGroup(ctypes.Structure):
     _fields_ = [("src_offset", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64), ("width", c_uint32)]
 
 
+class DensifyPlan(ctypes.Structure):
+    """gsr_densify_plan of include/gsr_hip_densify.h."""
+    _fields_ = [("max_grad", c_float), ("min_weight", c_float), ("dense_limit", c_float), ("big_near", c_float), ("big_far", c_float),
+                ("extent2", c_float), ("mean", c_float * 3), ("size_prune", c_int), ("N", c_int), ("scale_dims", c_int)]
+
+
 class AdamSegment(ctypes.Structure):
     """gsr_adam_segment of include/gsr_hip.h."""
     _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("lr", c_float), ("lr2", c_float), ("period", c_uint32),
@@ -214,6 +220,19 @@ def _load():
         lib.gsr_envmap_resize.argtypes = [P, P, c_int, c_int, c_int, P]
         lib.gsr_envmap_sharpen.restype = c_int
         lib.gsr_envmap_sharpen.argtypes = [P, P, c_int, c_int, c_float, c_float, c_float, P]
+    if hasattr(lib, "gsr_densify_plan_select"):
+        # (likewise, declared in include/gsr_hip_densify.h: a library built before the device-side densification plan lacks these five;
+        # gsr_densify.densify_and_prune(plan="device") and gsr_densify.prune_points then refuse to run)
+        lib.gsr_densify_plan_scratch_bytes.restype = c_size_t
+        lib.gsr_densify_plan_scratch_bytes.argtypes = [c_int, c_int]
+        lib.gsr_densify_plan_select.restype = c_int
+        lib.gsr_densify_plan_select.argtypes = [c_int, ctypes.POINTER(DensifyPlan), P, P, P, P, P, P, c_size_t, P, P, P]
+        lib.gsr_densify_plan_rows.restype = c_int
+        lib.gsr_densify_plan_rows.argtypes = [c_int, ctypes.POINTER(DensifyPlan), P, c_size_t, P, P, P, P, P, c_int, P, P, P, P, P]
+        lib.gsr_prune_rows.restype = c_int
+        lib.gsr_prune_rows.argtypes = [c_int, P, P, c_size_t, P, P, P]
+        lib.gsr_scatter_rows.restype = c_int
+        lib.gsr_scatter_rows.argtypes = [P, P, P, ctypes.c_uint64, ctypes.POINTER(GatherGroup), c_int, P]
     return lib
 
 
@@ -274,6 +293,9 @@ EXPORTED_SCOPE = ["gsr_env_scope_scratch_floats", "gsr_env_scope_forward", "gsr_
 
 # the entries of include/gsr_hip_envmap.h (the environment map's bicubic resize and its sharpening in sigmoid space), likewise
 EXPORTED_ENVMAP = ["gsr_envmap_resize", "gsr_envmap_sharpen"]
+
+# the entries of include/gsr_hip_densify.h (the densification plan on the device, prune_points, the scatter of the split children), likewise
+EXPORTED_DENSIFY = ["gsr_densify_plan_scratch_bytes", "gsr_densify_plan_select", "gsr_densify_plan_rows", "gsr_prune_rows", "gsr_scatter_rows"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]
