@@ -233,6 +233,11 @@ def _load():
         lib.gsr_prune_rows.argtypes = [c_int, P, P, c_size_t, P, P, P]
         lib.gsr_scatter_rows.restype = c_int
         lib.gsr_scatter_rows.argtypes = [P, P, P, ctypes.c_uint64, ctypes.POINTER(GatherGroup), c_int, P]
+    if hasattr(lib, "gsr_densification_stats_filter"):
+        # (likewise, declared in include/gsr_hip_densify_stats.h: a library built before the statistics under a boolean filter lacks it;
+        # scene.GaussianModel.add_densification_stats then refuses to run without `radii`)
+        lib.gsr_densification_stats_filter.restype = c_int
+        lib.gsr_densification_stats_filter.argtypes = [c_int, P, P, P, P, P, P, P, P]
     return lib
 
 
@@ -296,6 +301,9 @@ EXPORTED_ENVMAP = ["gsr_envmap_resize", "gsr_envmap_sharpen"]
 
 # the entries of include/gsr_hip_densify.h (the densification plan on the device, prune_points, the scatter of the split children), likewise
 EXPORTED_DENSIFY = ["gsr_densify_plan_scratch_bytes", "gsr_densify_plan_select", "gsr_densify_plan_rows", "gsr_prune_rows", "gsr_scatter_rows"]
+
+# the entry of include/gsr_hip_densify_stats.h (add_densification_stats under the reference's boolean filter), likewise
+EXPORTED_DENSIFY_STATS = ["gsr_densification_stats_filter"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

@@ -10,7 +10,23 @@
 
 namespace gsr {
 
-// add_densification_stats (scene/gaussian_model.py:578-584) + the max_radii2D update of train.py:243, one pass over P.
+// add_densification_stats (scene/gaussian_model.py:578-584) for row i: `seen` is the reference's update_filter[i].
+__device__ __forceinline__ void densify_stats_row(int i, bool seen, const float* __restrict__ grad_means2D, const float* __restrict__ weights,
+                                                  float* __restrict__ xyz_gradient_accum, float* __restrict__ denom, float* __restrict__ accum_w,
+                                                  float* __restrict__ denom_w) {
+	if (seen) {
+		const float gx = grad_means2D[3 * i], gy = grad_means2D[3 * i + 1], gz = grad_means2D[3 * i + 2];
+		xyz_gradient_accum[i] += sqrtf(gx * gx + gy * gy + gz * gz);   // torch.norm(grad[update_filter], dim=-1)
+		denom[i] += 1.0f;
+	}
+	const float w = weights[i];
+	if (w > 0.0f) {
+		accum_w[i] += w;
+		denom_w[i] += 1.0f;
+	}
+}
+
+// add_densification_stats + the max_radii2D update of train.py:243, one pass over P.
 __global__ void __launch_bounds__(256)
 densify_stats_kernel(int P, const float* __restrict__ grad_means2D, const int* __restrict__ radii, const float* __restrict__ weights,
                      float* __restrict__ xyz_gradient_accum, float* __restrict__ denom, float* __restrict__ accum_w, float* __restrict__ denom_w,
@@ -18,17 +34,18 @@ densify_stats_kernel(int P, const float* __restrict__ grad_means2D, const int* _
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= P) return;
 	const int r = radii[i];
-	if (r > 0) {   // visibility_filter = radii > 0
-		const float gx = grad_means2D[3 * i], gy = grad_means2D[3 * i + 1], gz = grad_means2D[3 * i + 2];
-		xyz_gradient_accum[i] += sqrtf(gx * gx + gy * gy + gz * gz);   // torch.norm(grad[update_filter], dim=-1)
-		denom[i] += 1.0f;
-		max_radii2D[i] = fmaxf(max_radii2D[i], (float)r);
-	}
-	const float w = weights[i];
-	if (w > 0.0f) {
-		accum_w[i] += w;
-		denom_w[i] += 1.0f;
-	}
+	densify_stats_row(i, r > 0, grad_means2D, weights, xyz_gradient_accum, denom, accum_w, denom_w);   // visibility_filter = radii > 0
+	if (r > 0) max_radii2D[i] = fmaxf(max_radii2D[i], (float)r);
+}
+
+// add_densification_stats as the reference calls it, under a boolean filter (torch.bool storage); max_radii2D is the caller's line.
+__global__ void __launch_bounds__(256)
+densify_stats_filter_kernel(int P, const float* __restrict__ grad_means2D, const uint8_t* __restrict__ update_filter, const float* __restrict__ weights,
+                            float* __restrict__ xyz_gradient_accum, float* __restrict__ denom, float* __restrict__ accum_w,
+                            float* __restrict__ denom_w) {
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= P) return;
+	densify_stats_row(i, update_filter[i] != 0, grad_means2D, weights, xyz_gradient_accum, denom, accum_w, denom_w);
 }
 
 // Row gather over several row-major blocks that share one row map: dst_g[r, :] = map[r] >= 0 ? src_g[map[r], :] : 0.
@@ -365,6 +382,21 @@ extern "C" int gsr_densification_stats(int P, const float* grad_means2D, const i
 	}
 	densify_stats_kernel<<<(P + 255) / 256, 256, 0, stream>>>(P, grad_means2D, radii, gaussian_weights, xyz_gradient_accum, denom, accum_w, denom_w,
 	                                                         max_radii2D);
+	GSR_LAUNCH_CHECK(0, stream);
+	return 0;
+}
+
+extern "C" int gsr_densification_stats_filter(int P, const float* grad_means2D, const uint8_t* update_filter, const float* gaussian_weights,
+                                              float* xyz_gradient_accum, float* denom, float* accum_w, float* denom_w, void* stream_) {
+	hipStream_t stream = (hipStream_t)stream_;
+	if (P < 0) { set_error("gsr_densification_stats_filter: P = %d", P); return GSR_E_INVALID; }
+	if (P == 0) return 0;
+	if (!grad_means2D || !update_filter || !gaussian_weights || !xyz_gradient_accum || !denom || !accum_w || !denom_w) {
+		set_error("gsr_densification_stats_filter: NULL buffer");
+		return GSR_E_INVALID;
+	}
+	densify_stats_filter_kernel<<<(P + 255) / 256, 256, 0, stream>>>(P, grad_means2D, update_filter, gaussian_weights, xyz_gradient_accum, denom,
+	                                                                accum_w, denom_w);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }

@@ -602,3 +602,11 @@ def render_env_map(pc, height=512, width=1024):
         rgb = torch.sigmoid(env(dirs.reshape(-1, 3)))
         out[name] = rgb.reshape(height, width, 3).permute(2, 0, 1)
     return out
+
+
+def __getattr__(name):
+    """`from gaussian_renderer import GaussianModel` of the reference's render.py / eval_fps.py; resolved on first use."""
+    if name == "GaussianModel":
+        from scene.gaussian_model import GaussianModel
+        return GaussianModel
+    raise AttributeError(f"module 'gaussian_renderer' has no attribute {name!r}")

@@ -35,10 +35,11 @@ def save_ply(path, means3D, shs, opacities, refl_strengths, scales, rotations, c
     xyz, shs_, op, rf, sc, rot = (_np(a).astype(np.float32) for a in (means3D, shs, opacities, refl_strengths, scales, rotations))
     P, M = xyz.shape[0], shs_.shape[1]
     f_dc = shs_[:, 0, :]                                                   # (P,3)   = _features_dc.transpose(1,2).flatten(1)
-    f_rest = np.transpose(shs_[:, 1:, :], (0, 2, 1)).reshape(P, -1)        # (P,3*(M-1)) channel-major
-    cols = np.concatenate([xyz, np.zeros_like(xyz), f_dc, f_rest, op.reshape(P, 1), rf.reshape(P, 1), sc.reshape(P, -1), rot.reshape(P, 4)],
+    f_rest = np.transpose(shs_[:, 1:, :], (0, 2, 1)).reshape(P, 3 * (M - 1))   # channel-major (widths spelled out: with P = 0 a -1 is undetermined)
+    sc = sc.reshape(P, -1) if P else sc.reshape(0, sc.shape[-1])
+    cols = np.concatenate([xyz, np.zeros_like(xyz), f_dc, f_rest, op.reshape(P, 1), rf.reshape(P, 1), sc, rot.reshape(P, 4)],
                           axis=1).astype('<f4')
-    names = attribute_names(M, sc.reshape(P, -1).shape[1])
+    names = attribute_names(M, sc.shape[1])
     assert cols.shape[1] == len(names)
     d = os.path.dirname(path)
     if d:

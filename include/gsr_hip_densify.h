@@ -37,6 +37,7 @@
 #define GSR_HIP_DENSIFY_H_
 
 #include "gsr_hip.h"
+#include "gsr_hip_densify_stats.h"   /* the statistics under a boolean filter, declared in a header of its own */
 
 #ifdef __cplusplus
 extern "C" {
