@@ -62,192 +62,156 @@ class ReflForward(ctypes.Structure):
 GSR_ABI_VERSION = 102      # GSR_ABI_VERSION of include/gsr_hip.h this binding was written against
 
 
+# ------------------------------------------------------------------ the C ABI, once: one group per header and source file, one row per entry
+# A group is (header under include/, file under this directory its entries live in, added later?, [(entry, restype, argtypes)]).  The groups
+# that are not `later` are ABI 102 as it was frozen: a library that lacks one of their symbols does not load.  A `later` group was added
+# under ABI 102 by name, without a version change: it is bound only when its FIRST entry is present, and the Python layer that needs it
+# calls require_entry(lib, <that entry>), so a library built before the group keeps serving everything else.  Adding an entry is one row
+# here beside its prototype in the header ("Adding an entry under ABI 102"); tests/test_cabi.py holds every row to its header.
+P, I, F, U32, U64 = c_void_p, c_int, c_float, c_uint32, ctypes.c_uint64
+_SURFEL_FWD = [ALLOC_FN, P, I, I, I, P, I, I, P, P, P, P, P, P, P, F, P, P, P, P, P, F, F, I, P, P, P, P, P, I, P]
+_SURFEL_BWD = [I, I, I, I, P, I, I, P, P, P, P, P, F, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P]
+_GAUSS_BWD = [I, I, I, I, P, I, I, P, P, P, P, P, P, P, F, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I,
+              I, P]
+_REFL_FWD = [P, P, P, P, P, P, U32, I, I, P, P, P, P]
+_REFL_BWD = [P, P, P, P, P, P, U32, I, I, P, P, P, P, P, P, P, P, P, c_size_t, P]
+_ADAM = [P, P, P, P, U64, ctypes.POINTER(AdamSegment), I, F, F, F, I, P]
+_ROWS_BY_MAP = [P, P, P, U64, ctypes.POINTER(GatherGroup), I, P]
+
+ABI = [
+    ("gsr_hip.h", "csrc/gsr_common.hip", False, [
+        ("gsr_last_error", c_char_p, None),        # (void): argtypes is left unset, as for gsr_version
+        ("gsr_version", I, None),
+        ("gsr_set_option", I, [c_char_p, I]),
+        ("gsr_profile_enable", I, [I]),
+        ("gsr_profile_collect", I, [P, P]),
+        ("gsr_mark_visible", I, [I, P, P, P, P, P]),
+        ("gsr_debug_fetch", I, [I, c_char_p, I, I, I, I, P, P, P, P, P])]),
+    ("gsr_hip.h", "csrc/gsr_surfel.hip", False, [
+        ("gsr_surfel_forward", I, _SURFEL_FWD),
+        ("gsr_surfel_forward_refl", I, _SURFEL_FWD[:-2] + [ctypes.POINTER(ReflForward), I, P]),
+        ("gsr_surfel_forward_eval", I, [ALLOC_FN, P, I, I, I, P, I, I, P, P, P, P, P, P, F, P, P, P, P, P, F, F, I, P, P, P, P, P,
+                                        ctypes.POINTER(ReflForward), I, P]),
+        ("gsr_surfel_backward", I, _SURFEL_BWD),
+        ("gsr_surfel_backward_accum", I, _SURFEL_BWD[:-2] + [I, I, P]),
+        ("gsr_surfel_backward_ex", I, _SURFEL_BWD[:-2] + [I, P, I, P])]),
+    ("gsr_hip.h", "csrc/gsr_gauss.hip", False, [
+        ("gsr_gauss_forward", I, [ALLOC_FN, P, I, I, I, P, I, I, P, P, P, P, P, P, P, F, P, P, P, P, P, F, F, I, P, P, P, P, I, P, I, P]),
+        ("gsr_gauss_backward", I, _GAUSS_BWD),
+        ("gsr_gauss_backward_accum", I, _GAUSS_BWD[:-2] + [I, I, P])]),
+    ("gsr_hip.h", "csrc/gsr_cubemap.hip", False, [
+        ("gsr_cubemap_forward", I, [P, P, P, P, U32, U32, U32, U32, U32, P]),
+        ("gsr_cubemap_backward", I, [P, P, P, P, P, P, U32, U32, U32, U32, U32, P]),
+        ("gsr_deferred_reflection_forward", I, _REFL_FWD),
+        ("gsr_deferred_reflection_forward_ex", I, _REFL_FWD[:-1] + [P, P]),
+        ("gsr_deferred_reflection_forward_keys", I, _REFL_FWD[:-1] + [P, P, P]),
+        ("gsr_deferred_reflection_scratch_floats", c_size_t, [U32, I, I, I]),
+        ("gsr_deferred_reflection_backward", I, _REFL_BWD),
+        ("gsr_deferred_reflection_backward_accum", I, _REFL_BWD[:-1] + [I, P]),
+        ("gsr_deferred_reflection_backward_ex", I, _REFL_BWD[:-1] + [I, I, P, P]),
+        ("gsr_deferred_reflection_backward_keys", I, _REFL_BWD[:-1] + [I, I, P, P, I, P]),
+        ("gsr_side_join", I, [P]),
+        ("gsr_normal_world_forward", I, [P, P, I, I, P, P]),
+        ("gsr_normal_world_backward", I, [P, P, I, I, P, P, P])]),
+    ("gsr_hip.h", "csrc/gsr_loss.hip", False, [
+        ("gsr_ssim_l1_scratch_floats", c_size_t, [I, I, I]),
+        ("gsr_ssim_l1_forward", I, [P, P, I, I, I, F, F, P, P, P, P, P, P, P]),
+        ("gsr_ssim_l1_backward", I, [P, P, I, I, I, P, P, P, P, P, P])]),
+    ("gsr_hip.h", "csrc/gsr_train.hip", False, [
+        ("gsr_normal_loss_scratch_floats", c_size_t, []),
+        ("gsr_normal_loss_forward", I, [P, P, P, I, I, P, P, P]),
+        ("gsr_normal_loss_backward", I, [P, P, P, I, I, P, P, P, P]),
+        ("gsr_adam_step", I, _ADAM),
+        ("gsr_adam_step_range", I, _ADAM[:-1] + [U64, U64, P])]),
+    ("gsr_hip.h", "csrc/gsr_surface.hip", False, [
+        ("gsr_surface_forward", I, [P, P, F, I, I, P, P, P]),
+        ("gsr_surface_backward", I, [P, P, F, I, I, P, P, P, P, P])]),
+    ("gsr_hip.h", "csrc/gsr_densify.hip", False, [
+        ("gsr_densification_stats", I, [I, P, P, P, P, P, P, P, P, P]),
+        ("gsr_gather_rows", I, _ROWS_BY_MAP),
+        ("gsr_split_children", I, [I, I, I, P, P, P, P, P, P, P, P])]),
+    # simple_knn refuses to import without these two, while the rasterizers keep working
+    ("gsr_hip.h", "csrc/gsr_knn.hip", True, [
+        ("gsr_knn_mean_dist", I, [I, P, P, P, c_size_t, P]),
+        ("gsr_knn_scratch_bytes", c_size_t, [I])]),
+    # the evaluation metrics: utils.image_utils, utils.mae_utils and gsr_eval
+    ("gsr_hip.h", "csrc/gsr_metrics.hip", True, [
+        ("gsr_image_metrics", I, [P, P, I, I, I, I, P, P, P, P, P, c_size_t, P, P, P]),
+        ("gsr_image_metrics_scratch_floats", c_size_t, [I, I, I]),
+        ("gsr_normal_mae_scratch_floats", c_size_t, [I, I]),
+        ("gsr_normal_mae", I, [P, P, I, I, F, F, F, P, P, c_size_t, P, P])]),
+    # the viewer presentation: utils.image_utils
+    ("gsr_hip.h", "csrc/gsr_viewer.hip", True, [
+        ("gsr_present_view", I, [P, I, I, I, I, P, P, P, P, c_size_t, P]),
+        ("gsr_present_view_scratch_floats", c_size_t, [I, I, I, I])]),
+    # the composited loss and the SSIM-map gradient: utils.loss_utils
+    ("gsr_hip.h", "csrc/gsr_loss.hip", True, [
+        ("gsr_photometric_forward", I, [P, P, P, P, P, I, I, I, F, F, P, P, P, P, P, P]),
+        ("gsr_photometric_scratch_floats", c_size_t, [I, I, I]),
+        ("gsr_photometric_backward", I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P, P]),
+        ("gsr_ssim_map_backward", I, [P, P, I, I, I, P, P, P, P, P, P])]),
+    # the raw-parameter step: gsr_train.RawTrainState
+    ("gsr_hip_train.h", "csrc/gsr_train.hip", True, [
+        ("gsr_adam_act_step", I, [P, P, P, P, P, U64, U64, ctypes.POINTER(ActSegment), I, F, F, F, I, U64, U64, P]),
+        ("gsr_activate", I, [P, P, U64, U64, ctypes.POINTER(ActSegment), I, P])]),
+    # the env-scope masks and the reflection-mask loss: utils.loss_utils.env_scope_masks, refl_scope_loss
+    ("gsr_hip_scope.h", "csrc/gsr_scope.hip", True, [
+        ("gsr_env_scope_forward", I, [I, P, P, F, F, F, F, P, P, P, P, P]),
+        ("gsr_env_scope_scratch_floats", c_size_t, []),
+        ("gsr_env_scope_backward", I, [I, P, P, P, P, I, P])]),
+    # the environment map's bicubic resize and its sharpening in sigmoid space: gsr_envmap
+    ("gsr_hip_envmap.h", "csrc/gsr_envmap.hip", True, [
+        ("gsr_envmap_resize", I, [P, P, I, I, I, P]),
+        ("gsr_envmap_sharpen", I, [P, P, I, I, F, F, F, P])]),
+    # the densification plan on the device, prune_points, the scatter of the split children: gsr_densify
+    ("gsr_hip_densify.h", "csrc/gsr_densify.hip", True, [
+        ("gsr_densify_plan_select", I, [I, ctypes.POINTER(DensifyPlan), P, P, P, P, P, P, c_size_t, P, P, P]),
+        ("gsr_densify_plan_scratch_bytes", c_size_t, [I, I]),
+        ("gsr_densify_plan_rows", I, [I, ctypes.POINTER(DensifyPlan), P, c_size_t, P, P, P, P, P, I, P, P, P, P, P]),
+        ("gsr_prune_rows", I, [I, P, P, c_size_t, P, P, P]),
+        ("gsr_scatter_rows", I, _ROWS_BY_MAP)]),
+    # add_densification_stats under the reference's boolean filter: scene.GaussianModel (one commit younger than the five above)
+    ("gsr_hip_densify.h", "csrc/gsr_densify.hip", True, [
+        ("gsr_densification_stats_filter", I, [I, P, P, P, P, P, P, P, P])]),
+]
+
+ENTRIES_BY_HEADER = {}          # {header file name: [entry names]}, what tests/test_cabi.py holds each header to
+for _header, _, _, _rows in ABI:
+    ENTRIES_BY_HEADER.setdefault(_header, []).extend(name for name, _, _ in _rows)
+EXPORTED = ENTRIES_BY_HEADER["gsr_hip.h"]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f"{LIB_PATH} not found: the HIP extension has not been built. Run "
             f"`python {os.path.join(_HERE, 'csrc', 'build.py')}` (hipcc, gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    P = c_void_p
-    lib.gsr_last_error.restype = c_char_p
     lib.gsr_version.restype = c_int
     if lib.gsr_version() != GSR_ABI_VERSION:
         # an entry point never changes its signature, but a library built from another header may lack (or, once, have changed) symbols
         # this binding calls: refuse it instead of passing shifted arguments
         raise ImportError(f"{LIB_PATH} reports ABI version {lib.gsr_version()}, this binding was written against {GSR_ABI_VERSION} "
                           f"(include/gsr_hip.h): rebuild with `python {os.path.join(_HERE, 'csrc', 'build.py')} --force`")
-    lib.gsr_surfel_forward.restype = c_int
-    lib.gsr_surfel_forward.argtypes = [ALLOC_FN, P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, P, c_float, P, P, P, P, P,
-                                       c_float, c_float, c_int, P, P, P, P, P, c_int, P]
-    lib.gsr_surfel_backward.restype = c_int
-    lib.gsr_surfel_backward.argtypes = [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P, c_float, c_float,
-                                        P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, P]
-    lib.gsr_surfel_backward_accum.restype = c_int
-    lib.gsr_surfel_backward_accum.argtypes = lib.gsr_surfel_backward.argtypes[:-2] + [c_int, c_int, P]
-    lib.gsr_surfel_backward_ex.restype = c_int
-    lib.gsr_surfel_backward_ex.argtypes = lib.gsr_surfel_backward.argtypes[:-2] + [c_int, P, c_int, P]
-    lib.gsr_surfel_forward_refl.restype = c_int
-    lib.gsr_surfel_forward_refl.argtypes = lib.gsr_surfel_forward.argtypes[:-2] + [ctypes.POINTER(ReflForward), c_int, P]
-    lib.gsr_surfel_forward_eval.restype = c_int
-    lib.gsr_surfel_forward_eval.argtypes = [ALLOC_FN, P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, c_float, P, P, P, P, P,
-                                            c_float, c_float, c_int, P, P, P, P, P, ctypes.POINTER(ReflForward), c_int, P]
-    lib.gsr_gauss_forward.restype = c_int
-    lib.gsr_gauss_forward.argtypes = [ALLOC_FN, P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, P, c_float, P, P, P, P, P,
-                                      c_float, c_float, c_int, P, P, P, P, c_int, P, c_int, P]
-    lib.gsr_gauss_backward.restype = c_int
-    lib.gsr_gauss_backward.argtypes = [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, P, c_float, P, P, P, P, P, c_float,
-                                       c_float, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, P]
-    lib.gsr_gauss_backward_accum.restype = c_int
-    lib.gsr_gauss_backward_accum.argtypes = lib.gsr_gauss_backward.argtypes[:-2] + [c_int, c_int, P]
-    lib.gsr_mark_visible.restype = c_int
-    lib.gsr_mark_visible.argtypes = [c_int, P, P, P, P, P]
-    lib.gsr_debug_fetch.restype = c_int
-    lib.gsr_debug_fetch.argtypes = [c_int, c_char_p, c_int, c_int, c_int, c_int, P, P, P, P, P]
-    lib.gsr_cubemap_forward.restype = c_int
-    lib.gsr_cubemap_forward.argtypes = [P, P, P, P, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, P]
-    lib.gsr_cubemap_backward.restype = c_int
-    lib.gsr_cubemap_backward.argtypes = [P, P, P, P, P, P, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, P]
-    lib.gsr_deferred_reflection_forward.restype = c_int
-    lib.gsr_deferred_reflection_forward.argtypes = [P, P, P, P, P, P, c_uint32, c_int, c_int, P, P, P, P]
-    lib.gsr_deferred_reflection_backward.restype = c_int
-    lib.gsr_deferred_reflection_scratch_floats.restype = c_size_t
-    lib.gsr_deferred_reflection_scratch_floats.argtypes = [c_uint32, c_int, c_int, c_int]
-    lib.gsr_deferred_reflection_backward.argtypes = [P, P, P, P, P, P, c_uint32, c_int, c_int, P, P, P, P, P, P, P, P, P, c_size_t, P]
-    lib.gsr_deferred_reflection_backward_accum.restype = c_int
-    lib.gsr_deferred_reflection_backward_accum.argtypes = lib.gsr_deferred_reflection_backward.argtypes[:-1] + [c_int, P]
-    lib.gsr_deferred_reflection_backward_ex.restype = c_int
-    lib.gsr_deferred_reflection_backward_ex.argtypes = lib.gsr_deferred_reflection_backward.argtypes[:-1] + [c_int, c_int, P, P]
-    lib.gsr_deferred_reflection_backward_keys.restype = c_int
-    lib.gsr_deferred_reflection_backward_keys.argtypes = lib.gsr_deferred_reflection_backward.argtypes[:-1] + [c_int, c_int, P, P, c_int, P]
-    lib.gsr_deferred_reflection_forward_ex.restype = c_int
-    lib.gsr_deferred_reflection_forward_ex.argtypes = lib.gsr_deferred_reflection_forward.argtypes[:-1] + [P, P]
-    lib.gsr_deferred_reflection_forward_keys.restype = c_int
-    lib.gsr_deferred_reflection_forward_keys.argtypes = lib.gsr_deferred_reflection_forward.argtypes[:-1] + [P, P, P]
-    lib.gsr_side_join.restype = c_int
-    lib.gsr_side_join.argtypes = [P]
-    lib.gsr_normal_world_forward.restype = c_int
-    lib.gsr_normal_world_forward.argtypes = [P, P, c_int, c_int, P, P]
-    lib.gsr_normal_world_backward.restype = c_int
-    lib.gsr_normal_world_backward.argtypes = [P, P, c_int, c_int, P, P, P]
-    lib.gsr_ssim_l1_forward.restype = c_int
-    lib.gsr_ssim_l1_scratch_floats.restype = c_size_t
-    lib.gsr_ssim_l1_scratch_floats.argtypes = [c_int, c_int, c_int]
-    lib.gsr_ssim_l1_forward.argtypes = [P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P]
-    lib.gsr_ssim_l1_backward.restype = c_int
-    lib.gsr_ssim_l1_backward.argtypes = [P, P, c_int, c_int, c_int, P, P, P, P, P, P]
-    lib.gsr_normal_loss_scratch_floats.restype = c_size_t
-    lib.gsr_normal_loss_scratch_floats.argtypes = []
-    lib.gsr_normal_loss_forward.restype = c_int
-    lib.gsr_normal_loss_forward.argtypes = [P, P, P, c_int, c_int, P, P, P]
-    lib.gsr_normal_loss_backward.restype = c_int
-    lib.gsr_normal_loss_backward.argtypes = [P, P, P, c_int, c_int, P, P, P, P]
-    lib.gsr_surface_forward.restype = c_int
-    lib.gsr_surface_forward.argtypes = [P, P, c_float, c_int, c_int, P, P, P]
-    lib.gsr_surface_backward.restype = c_int
-    lib.gsr_surface_backward.argtypes = [P, P, c_float, c_int, c_int, P, P, P, P, P]
-    lib.gsr_densification_stats.restype = c_int
-    lib.gsr_densification_stats.argtypes = [c_int, P, P, P, P, P, P, P, P, P]
-    lib.gsr_gather_rows.restype = c_int
-    lib.gsr_gather_rows.argtypes = [P, P, P, ctypes.c_uint64, ctypes.POINTER(GatherGroup), c_int, P]
-    lib.gsr_split_children.restype = c_int
-    lib.gsr_split_children.argtypes = [c_int, c_int, c_int, P, P, P, P, P, P, P, P]
-    lib.gsr_adam_step.restype = c_int
-    lib.gsr_adam_step.argtypes = [P, P, P, P, ctypes.c_uint64, ctypes.POINTER(AdamSegment), c_int, c_float, c_float, c_float, c_int, P]
-    lib.gsr_adam_step_range.restype = c_int
-    lib.gsr_adam_step_range.argtypes = lib.gsr_adam_step.argtypes[:-1] + [ctypes.c_uint64, ctypes.c_uint64, P]
-    lib.gsr_set_option.restype = c_int
-    lib.gsr_set_option.argtypes = [c_char_p, c_int]
-    lib.gsr_profile_enable.restype = c_int
-    lib.gsr_profile_enable.argtypes = [c_int]
-    lib.gsr_profile_collect.restype = c_int
-    lib.gsr_profile_collect.argtypes = [P, P]
-    if hasattr(lib, "gsr_knn_mean_dist"):
-        # (added under ABI 102 without a version change: a library built before it lacks these two, and simple_knn refuses to import
-        # while the rasterizers keep working)
-        lib.gsr_knn_scratch_bytes.restype = c_size_t
-        lib.gsr_knn_scratch_bytes.argtypes = [c_int]
-        lib.gsr_knn_mean_dist.restype = c_int
-        lib.gsr_knn_mean_dist.argtypes = [c_int, P, P, P, c_size_t, P]
-    if hasattr(lib, "gsr_image_metrics"):
-        # (likewise: a library built before the evaluation metrics lacks these four; utils.image_utils, utils.mae_utils and gsr_eval
-        # then refuse to import)
-        lib.gsr_image_metrics_scratch_floats.restype = c_size_t
-        lib.gsr_image_metrics_scratch_floats.argtypes = [c_int, c_int, c_int]
-        lib.gsr_image_metrics.restype = c_int
-        lib.gsr_image_metrics.argtypes = [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P, P, P]
-        lib.gsr_normal_mae_scratch_floats.restype = c_size_t
-        lib.gsr_normal_mae_scratch_floats.argtypes = [c_int, c_int]
-        lib.gsr_normal_mae.restype = c_int
-        lib.gsr_normal_mae.argtypes = [P, P, c_int, c_int, c_float, c_float, c_float, P, P, c_size_t, P, P]
-    if hasattr(lib, "gsr_present_view"):
-        # (likewise: a library built before the viewer presentation lacks these two; utils.image_utils then refuses to import)
-        lib.gsr_present_view_scratch_floats.restype = c_size_t
-        lib.gsr_present_view_scratch_floats.argtypes = [c_int, c_int, c_int, c_int]
-        lib.gsr_present_view.restype = c_int
-        lib.gsr_present_view.argtypes = [P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]
-    if hasattr(lib, "gsr_photometric_forward"):
-        # (likewise: a library built before the composited loss and the SSIM-map gradient lacks these four; utils.loss_utils then
-        # refuses to import)
-        lib.gsr_photometric_scratch_floats.restype = c_size_t
-        lib.gsr_photometric_scratch_floats.argtypes = [c_int, c_int, c_int]
-        lib.gsr_photometric_forward.restype = c_int
-        lib.gsr_photometric_forward.argtypes = [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P]
-        lib.gsr_photometric_backward.restype = c_int
-        lib.gsr_photometric_backward.argtypes = [P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P]
-        lib.gsr_ssim_map_backward.restype = c_int
-        lib.gsr_ssim_map_backward.argtypes = [P, P, c_int, c_int, c_int, P, P, P, P, P, P]
-    if hasattr(lib, "gsr_adam_act_step"):
-        # (likewise, declared in include/gsr_hip_train.h: a library built before the raw-parameter step lacks these two;
-        # gsr_train.RawTrainState then refuses to be built)
-        lib.gsr_adam_act_step.restype = c_int
-        lib.gsr_adam_act_step.argtypes = [P, P, P, P, P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ActSegment), c_int, c_float, c_float,
-                                          c_float, c_int, ctypes.c_uint64, ctypes.c_uint64, P]
-        lib.gsr_activate.restype = c_int
-        lib.gsr_activate.argtypes = [P, P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ActSegment), c_int, P]
-    if hasattr(lib, "gsr_env_scope_forward"):
-        # (likewise, declared in include/gsr_hip_scope.h: a library built before the env-scope pass lacks these three;
-        # utils.loss_utils.env_scope_masks and refl_scope_loss then refuse to run)
-        lib.gsr_env_scope_scratch_floats.restype = c_size_t
-        lib.gsr_env_scope_scratch_floats.argtypes = []
-        lib.gsr_env_scope_forward.restype = c_int
-        lib.gsr_env_scope_forward.argtypes = [c_int, P, P, c_float, c_float, c_float, c_float, P, P, P, P, P]
-        lib.gsr_env_scope_backward.restype = c_int
-        lib.gsr_env_scope_backward.argtypes = [c_int, P, P, P, P, c_int, P]
-    if hasattr(lib, "gsr_envmap_resize"):
-        # (likewise, declared in include/gsr_hip_envmap.h: a library built before the environment-map transforms lacks these two;
-        # gsr_envmap.resize_env_map, double_env_map and filter_env_map then refuse to run)
-        lib.gsr_envmap_resize.restype = c_int
-        lib.gsr_envmap_resize.argtypes = [P, P, c_int, c_int, c_int, P]
-        lib.gsr_envmap_sharpen.restype = c_int
-        lib.gsr_envmap_sharpen.argtypes = [P, P, c_int, c_int, c_float, c_float, c_float, P]
-    if hasattr(lib, "gsr_densify_plan_select"):
-        # (likewise, declared in include/gsr_hip_densify.h: a library built before the device-side densification plan lacks these five;
-        # gsr_densify.densify_and_prune(plan="device") and gsr_densify.prune_points then refuse to run)
-        lib.gsr_densify_plan_scratch_bytes.restype = c_size_t
-        lib.gsr_densify_plan_scratch_bytes.argtypes = [c_int, c_int]
-        lib.gsr_densify_plan_select.restype = c_int
-        lib.gsr_densify_plan_select.argtypes = [c_int, ctypes.POINTER(DensifyPlan), P, P, P, P, P, P, c_size_t, P, P, P]
-        lib.gsr_densify_plan_rows.restype = c_int
-        lib.gsr_densify_plan_rows.argtypes = [c_int, ctypes.POINTER(DensifyPlan), P, c_size_t, P, P, P, P, P, c_int, P, P, P, P, P]
-        lib.gsr_prune_rows.restype = c_int
-        lib.gsr_prune_rows.argtypes = [c_int, P, P, c_size_t, P, P, P]
-        lib.gsr_scatter_rows.restype = c_int
-        lib.gsr_scatter_rows.argtypes = [P, P, P, ctypes.c_uint64, ctypes.POINTER(GatherGroup), c_int, P]
-    if hasattr(lib, "gsr_densification_stats_filter"):
-        # (likewise, declared in include/gsr_hip_densify_stats.h: a library built before the statistics under a boolean filter lacks it;
-        # scene.GaussianModel.add_densification_stats then refuses to run without `radii`)
-        lib.gsr_densification_stats_filter.restype = c_int
-        lib.gsr_densification_stats_filter.argtypes = [c_int, P, P, P, P, P, P, P, P]
+    for _, _, later, rows in ABI:
+        if later and not hasattr(lib, rows[0][0]):
+            continue
+        for name, restype, argtypes in rows:
+            fn = getattr(lib, name)         # (an AttributeError names the symbol a frozen group lacks)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
     return lib
 
 
 lib = _load()
 
 
-def require_entry(library, name, source_file):
-    """The check in front of an entry added under ABI 102 without a version change (the `hasattr` blocks above): `library` is the
-    calling module's `lib`, `source_file` the file under this directory the entry lives in."""
+def require_entry(library, name):
+    """The check in front of an entry of a `later` group of ABI: `library` is the calling module's `lib` (a module that cannot work without
+    the group calls this at import, with the group's first entry)."""
     if not hasattr(library, name):
+        source_file = next(source for _, source, _, rows in ABI if any(name == row[0] for row in rows))
         raise ImportError(f"{LIB_PATH} does not export {name} ({source_file}): it was built before that entry was added; "
                           f"rebuild with `python {os.path.join(_HERE, 'csrc', 'build.py')} --force`.  There is no torch fallback.")
 
@@ -279,31 +243,6 @@ def compiled_binding():
 
 
 PYBIND = compiled_binding()
-
-EXPORTED = ["gsr_last_error", "gsr_version", "gsr_surfel_forward", "gsr_surfel_backward", "gsr_surfel_backward_accum", "gsr_surfel_backward_ex",
-            "gsr_surfel_forward_refl", "gsr_surfel_forward_eval", "gsr_deferred_reflection_backward_keys", "gsr_deferred_reflection_forward_keys",
-            "gsr_deferred_reflection_backward_accum", "gsr_deferred_reflection_backward_ex", "gsr_deferred_reflection_forward_ex", "gsr_side_join", "gsr_normal_world_forward", "gsr_normal_world_backward", "gsr_gauss_forward", "gsr_gauss_backward", "gsr_gauss_backward_accum",
-            "gsr_mark_visible", "gsr_debug_fetch", "gsr_cubemap_forward", "gsr_cubemap_backward", "gsr_deferred_reflection_forward",
-            "gsr_deferred_reflection_scratch_floats", "gsr_deferred_reflection_backward", "gsr_ssim_l1_scratch_floats", "gsr_ssim_l1_forward", "gsr_ssim_l1_backward", "gsr_normal_loss_scratch_floats", "gsr_normal_loss_forward", "gsr_normal_loss_backward", "gsr_adam_step", "gsr_adam_step_range", "gsr_densification_stats", "gsr_gather_rows", "gsr_split_children", "gsr_surface_forward", "gsr_surface_backward", "gsr_profile_enable",
-            "gsr_profile_collect", "gsr_set_option", "gsr_knn_scratch_bytes", "gsr_knn_mean_dist",
-            "gsr_image_metrics_scratch_floats", "gsr_image_metrics", "gsr_normal_mae_scratch_floats", "gsr_normal_mae",
-            "gsr_present_view_scratch_floats", "gsr_present_view",
-            "gsr_photometric_scratch_floats", "gsr_photometric_forward", "gsr_photometric_backward", "gsr_ssim_map_backward"]
-
-# the entries of include/gsr_hip_train.h (the raw-parameter step), added under ABI 102 and kept apart from the list above
-EXPORTED_TRAIN = ["gsr_adam_act_step", "gsr_activate"]
-
-# the entries of include/gsr_hip_scope.h (the env-scope masks and the reflection-mask loss), likewise
-EXPORTED_SCOPE = ["gsr_env_scope_scratch_floats", "gsr_env_scope_forward", "gsr_env_scope_backward"]
-
-# the entries of include/gsr_hip_envmap.h (the environment map's bicubic resize and its sharpening in sigmoid space), likewise
-EXPORTED_ENVMAP = ["gsr_envmap_resize", "gsr_envmap_sharpen"]
-
-# the entries of include/gsr_hip_densify.h (the densification plan on the device, prune_points, the scatter of the split children), likewise
-EXPORTED_DENSIFY = ["gsr_densify_plan_scratch_bytes", "gsr_densify_plan_select", "gsr_densify_plan_rows", "gsr_prune_rows", "gsr_scatter_rows"]
-
-# the entry of include/gsr_hip_densify_stats.h (add_densification_stats under the reference's boolean filter), likewise
-EXPORTED_DENSIFY_STATS = ["gsr_densification_stats_filter"]
 
 STAGES = ["preprocess", "scan_readback", "emit_keys", "sort", "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "refl_fwd",
           "refl_bwd", "cubemap_fwd", "cubemap_bwd", "loss_fwd", "loss_bwd", "adam", "surface_fwd", "surface_bwd", "refl_bwd_tail"]

@@ -173,7 +173,7 @@ def _plan_device(state, stats, max_grad, mean, extent, max_screen_size, percent_
     _plan_torch.  Host reads: the 16 bytes of select's counts (they size the children and the maps), and with max_screen_size the 16
     bytes of the rows' counts (the number of rows kept).  No boolean index, no nonzero."""
     for name in ("gsr_densify_plan_select", "gsr_densify_plan_rows", "gsr_scatter_rows"):
-        require_entry(lib, name, "csrc/gsr_densify.hip")
+        require_entry(lib, name)
     if not max_grad > 0:
         raise ValueError("densify_and_prune(plan='device'): max_grad must be positive (a clone enters the split test with gradient 0)")
     old = state.params
@@ -289,7 +289,7 @@ def prune_points(state, mask, stats=None, group=None):
     gsr_prune_rows; the host reads its 16 bytes of counts (they size the new store).  A sharded state gathers its moments over `group`,
     as densify_and_prune does."""
     for name in ("gsr_prune_rows", "gsr_densify_plan_scratch_bytes"):
-        require_entry(lib, name, "csrc/gsr_densify.hip")
+        require_entry(lib, name)
     old = state.params
     dev = old.flat.device
     names = [k for k in PER_GAUSSIAN if k in old.names]

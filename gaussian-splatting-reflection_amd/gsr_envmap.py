@@ -23,7 +23,7 @@ def _check_state(state, what):
     if state.shard is not None and state.shard[1] > 1:
         # a rank holds only its chunk of the moments, and the chunk borders move with the layout: gsr_densify._whole_moments territory
         raise NotImplementedError(f"{what} on a sharded state (shard=(rank, world_size)) is not implemented")
-    _gsr.require_entry(lib, "gsr_envmap_resize", "csrc/gsr_envmap.hip")
+    _gsr.require_entry(lib, "gsr_envmap_resize")
 
 
 def resize_env_map(state, new_resolution):

@@ -15,11 +15,9 @@ import math
 import numpy as np
 import torch
 
-from _gsr import GSR_PRESENT_CLAMP, GSR_PRESENT_QUANT8, check, f32c, lib, ptr, require_cuda, stream_ptr
+from _gsr import GSR_PRESENT_CLAMP, GSR_PRESENT_QUANT8, check, f32c, lib, ptr, require_cuda, require_entry, stream_ptr
 
-if not hasattr(lib, "gsr_image_metrics"):
-    raise ImportError("libgsr_hip.so does not export gsr_image_metrics / gsr_normal_mae: it was built before the evaluation metrics "
-                      "(csrc/gsr_metrics.hip); rebuild with csrc/build.py --force")
+require_entry(lib, "gsr_image_metrics")       # the evaluation metrics (gsr_normal_mae comes with it)
 
 
 def _plane(t, name, H, W):

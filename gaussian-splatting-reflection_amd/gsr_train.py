@@ -224,7 +224,7 @@ class GaussianTrainState:
             # every rank would add the whole term to its buffer and the reduce-scatter would sum it world_size times
             raise NotImplementedError("refl_scope_loss on a sharded state (shard=(rank, world_size)) is not implemented")
         from utils import loss_utils as lu
-        _gsr.require_entry(lu.lib, "gsr_env_scope_forward", "csrc/gsr_scope.hip")
+        _gsr.require_entry(lu.lib, "gsr_env_scope_forward")
         with torch.no_grad():
             x = lu._scope_xyz(self.p["means3D"])
             refl = self._activated("refl_strengths").detach()
@@ -253,7 +253,7 @@ class RawAdam(FlatAdam):
     gsr_adam_act_step; activate() fills `act` from the raw buffer alone (gsr_activate)."""
 
     def __init__(self, params, grads_flat, groups, act, act_slices, betas=(0.9, 0.999), eps=1e-15):
-        _gsr.require_entry(lib, "gsr_adam_act_step", "csrc/gsr_train.hip")
+        _gsr.require_entry(lib, "gsr_adam_act_step")
         super().__init__(params, grads_flat, groups, betas=betas, eps=eps)
         if act.data_ptr() % 16:
             raise ValueError("the activated buffer must be 16-byte aligned")
@@ -317,7 +317,7 @@ class RawTrainState(GaussianTrainState):
         if shard is not None:
             raise NotImplementedError("RawTrainState(shard=...): the sharded exchange of the activated copy is not implemented; "
                                       "gsr_adam_act_step takes a range for it")
-        _gsr.require_entry(lib, "gsr_adam_act_step", "csrc/gsr_train.hip")
+        _gsr.require_entry(lib, "gsr_adam_act_step")
         super().__init__(tensors, device, spatial_lr_scale=spatial_lr_scale, lrs=lrs, _params=_params, shard=None)
         self.a = {}
         for k, (a, b) in self.optimizer.act_slices.items():

@@ -269,7 +269,7 @@ class GaussianModel:
         self._need_state("add_densification_stats")
         if radii is not None:
             return self._stats.update(viewspace_point_tensor.grad, radii, render_weight)
-        require_entry(lib, "gsr_densification_stats_filter", "csrc/gsr_densify.hip")
+        require_entry(lib, "gsr_densification_stats_filter")
         s = self._stats
         P = s.buf.shape[1]
         g = viewspace_point_tensor.grad.float().contiguous()

@@ -14,9 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import _gsr  # noqa: E402
 from _gsr import check, f32c, lib, ptr, stream_ptr  # noqa: E402
 
-if not hasattr(lib, "gsr_knn_mean_dist"):
-    raise ImportError(f"{_gsr.LIB_PATH} was built without gsr_knn_mean_dist (simple_knn): rebuild with "
-                      f"`python {os.path.join(os.path.dirname(_gsr.LIB_PATH), 'csrc', 'build.py')} --force`")
+_gsr.require_entry(lib, "gsr_knn_mean_dist")
 
 
 def distCUDA2(points):

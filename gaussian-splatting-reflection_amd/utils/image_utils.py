@@ -25,12 +25,10 @@ import os
 import numpy as np
 import torch
 
-from _gsr import GSR_VIEW_COLORMAP, GSR_VIEW_HALF, GSR_VIEW_SOBEL, check, f32c, lib, ptr, require_cuda, stream_ptr
+from _gsr import GSR_VIEW_COLORMAP, GSR_VIEW_HALF, GSR_VIEW_SOBEL, check, f32c, lib, ptr, require_cuda, require_entry, stream_ptr
 from gsr_eval import MetricsTable
 
-if not hasattr(lib, "gsr_present_view"):
-    raise ImportError("libgsr_hip.so does not export gsr_present_view: it was built before the viewer presentation "
-                      "(csrc/gsr_viewer.hip); rebuild with csrc/build.py --force")
+require_entry(lib, "gsr_present_view")       # the viewer presentation
 
 TURBO_LUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "turbo_lut.txt")
 

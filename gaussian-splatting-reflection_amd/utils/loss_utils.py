@@ -15,9 +15,7 @@ from torch.autograd.function import once_differentiable
 
 from _gsr import check, check_sink_tensor, f32c, lib, ptr, require_cuda, require_entry, stream_ptr
 
-if not hasattr(lib, "gsr_photometric_forward"):
-    raise ImportError("libgsr_hip.so does not export gsr_photometric_forward: it was built before the composited loss "
-                      "(csrc/gsr_loss.hip); rebuild with csrc/build.py --force")
+require_entry(lib, "gsr_photometric_forward")       # the composited loss and the SSIM-map gradient
 
 C1 = 0.01 ** 2
 C2 = 0.03 ** 2
@@ -371,7 +369,7 @@ def env_scope_masks(xyz, center, radius):
         outside = ((xyz - center[None]) ** 2).sum(-1) > radius ** 2      (train.py:61-63, get_outside_msk)
     with the float32 roundings of those expressions.  Neither is the other's negation: a centre exactly on the sphere or with a NaN
     coordinate is in neither.  `center`: three numbers (passed by value: no device copy) or a tensor."""
-    require_entry(lib, "gsr_env_scope_forward", "csrc/gsr_scope.hip")
+    require_entry(lib, "gsr_env_scope_forward")
     x = _scope_xyz(xyz)
     inside, outside, _ = _scope_forward(x, None, _scope_sphere(center, radius))
     return inside, outside
@@ -416,7 +414,7 @@ def refl_scope_loss(refl, xyz, center, radius, grad_sink=None, accumulate=False)
     grad_sink: a contiguous float32 tensor of refl's shape; the backward then writes (accumulate=False: every element, zeros where the
     point is not outside) or adds (accumulate=True: outside rows only) dL/drefl straight into it and autograd receives None for refl —
     the semantics of the rasterizer's sinks (_raster_api.GradSink)."""
-    require_entry(lib, "gsr_env_scope_forward", "csrc/gsr_scope.hip")
+    require_entry(lib, "gsr_env_scope_forward")
     if accumulate and grad_sink is None:
         raise ValueError("refl_scope_loss: accumulate=True needs a grad_sink to add to")
     require_cuda(refl, "refl")

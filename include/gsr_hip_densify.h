@@ -37,7 +37,6 @@
 #define GSR_HIP_DENSIFY_H_
 
 #include "gsr_hip.h"
-#include "gsr_hip_densify_stats.h"   /* the statistics under a boolean filter, declared in a header of its own */
 
 #ifdef __cplusplus
 extern "C" {
@@ -99,6 +98,23 @@ int gsr_prune_rows(int P, const uint8_t* remove /* [P] */, void* scratch, size_t
  * n_rows == 0 or num_groups == 0: a no-op.  GSR_E_INVALID: num_groups < 0 or > 16, a NULL argument, a zero-width group. */
 int gsr_scatter_rows(const float* src, float* dst, const int* slot, uint64_t n_rows, const gsr_gather_group* groups, int num_groups,
                      void* stream);
+
+/* The per-view densification statistics under a boolean filter:
+ *     GaussianModel.add_densification_stats(viewspace_point_tensor, update_filter, render_weight)   (scene/gaussian_model.py:579-584)
+ * as the reference's loop calls it every iteration (train.py:244).  gsr_densification_stats of gsr_hip.h takes the int32 radii and also
+ * keeps the running maximum max_radii2D (train.py:243 fused in); this entry takes the filter the caller already holds and leaves
+ * max_radii2D to the caller's own line.  Added under ABI 102 after the five entries above, likewise by name.  The kernel runs on the
+ * caller's stream, nothing synchronises with the host and nothing is allocated.
+ *
+ * For every row i < P, in float32:
+ *     update_filter[i] != 0 :  xyz_gradient_accum[i] += sqrtf(gx^2 + gy^2 + gz^2) of grad_means2D[i, 0..2];  denom[i] += 1
+ *     gaussian_weights[i] > 0:  accum_w[i] += gaussian_weights[i];                                            denom_w[i] += 1
+ * the arithmetic gsr_densification_stats applies to the rows with radii > 0, bit for bit (one device function serves both kernels).
+ * Rows with the filter off and a weight that is not positive keep their bits.  update_filter is bytes, torch.bool storage.
+ * P == 0: a no-op, returns 0.  GSR_E_INVALID: P < 0; for P > 0 any NULL buffer. */
+int gsr_densification_stats_filter(int P, const float* grad_means2D /* [P,3] */, const uint8_t* update_filter /* [P] */,
+                                   const float* gaussian_weights /* [P] */, float* xyz_gradient_accum, float* denom, float* accum_w,
+                                   float* denom_w, void* stream);
 
 #ifdef __cplusplus
 }

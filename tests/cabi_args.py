@@ -14,12 +14,9 @@ and the explicit Cases hold the either/or groups, the "needs its partner" pairs,
 limits.  Every case must be refused with GSR_E_INVALID, a message that names the entry (or its family: the _accum, _ex, _keys and _refl
 forms report under their base name) and no call of the allocation callback; the untouched row must NOT be refused.
 
-`python cabi_args.py` is the child process of tests/test_cabi_refusals.py: it hides every GPU, asks the HIP runtime for the device count,
-and only with none visible makes the calls — a missing check plus a fake pointer must never reach a device."""
+tests/test_cabi_refusals.py makes the calls in a child process (tests/cabi_child.py) that hides every GPU (HIDE_GPUS), asks the HIP runtime
+for the device count (_visible_devices), and only with none visible goes on — a missing check plus a fake pointer must never reach a device."""
 import ctypes
-import json
-import os
-import sys
 
 FAKE = 0x7f0000000000        # 256-byte aligned, never touched
 GSR_E_INVALID = -1
@@ -421,36 +418,17 @@ def _call(ctx, row, changes):
         values.append(v)
     assert len(values) == len(fn.argtypes), (row.entry, len(values), len(fn.argtypes))
     del ctx.allocs[:]
-    rc = fn(*values)
-    msg = ctx.gsr.lib.gsr_last_error()
-    return int(rc), (msg.decode(errors="replace") if msg else ""), len(ctx.allocs)
+    return int(fn(*values)), len(ctx.allocs)
 
 
-def main(argv):
-    """Prints one JSON line per call: BEGIN before it (so that a crash names its case), the result after it.  `--after ENTRY CASE` resumes
-    behind a case that took the process down."""
-    os.environ.update(HIDE_GPUS)
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.join(os.path.dirname(here), "gaussian-splatting-reflection_amd"))
-    import _gsr
-    n = _visible_devices()
-    if n != 0:
-        print(json.dumps({"devices": n}), flush=True)
-        return 0
-    print(json.dumps({"devices": 0}), flush=True)
-    todo = case_ids()
-    if "--after" in argv:
-        i = argv.index("--after")
-        todo = todo[todo.index((argv[i + 1], argv[i + 2])) + 1:]
-    ctx = _Ctx(_gsr)
-    for entry, cid in todo:
-        row = ROWS[entry]
-        changes = {} if cid == WELL_FORMED else next(c for c in row.cases if c.id == cid).changes
-        print(json.dumps({"begin": [entry, cid]}), flush=True)
-        rc, msg, allocs = _call(ctx, row, changes)
-        print(json.dumps({"done": [entry, cid], "rc": rc, "msg": msg, "allocs": allocs}), flush=True)
-    return 0
+_ctx = None
 
 
-if __name__ == "__main__":
-    sys.exit(main(sys.argv[1:]))
+def call(gsr, entry, case):
+    """One call of the table for tests/cabi_child.py's loop: (rc, {"allocs": requests the allocation callback saw})."""
+    global _ctx
+    _ctx = _ctx or _Ctx(gsr)
+    row = ROWS[entry]
+    changes = {} if case == WELL_FORMED else next(c for c in row.cases if c.id == case).changes
+    rc, allocs = _call(_ctx, row, changes)
+    return rc, {"allocs": allocs}

@@ -1,85 +1,28 @@
-"""The densification-plan entries (include/gsr_hip_densify.h: gsr_densify_plan_scratch_bytes, gsr_densify_plan_select,
-gsr_densify_plan_rows, gsr_prune_rows, gsr_scatter_rows) on a machine without a GPU: the header parses as include/gsr_hip.h does, the
-library exports the five, the ctypes prototypes and the plan struct match, the scratch query is what its contract says, and every refusal
-the header lists returns GSR_E_INVALID with a message naming the entry.  The calls are made with fake pointers in ONE child process that
-hides every GPU and asks the HIP runtime for the device count first (tests/cabi_args.py's guard, by import); with a device still visible
-nothing is called.  `python test_cabi_densify.py` is that child."""
+"""The densification entries (include/gsr_hip_densify.h: gsr_densify_plan_scratch_bytes, gsr_densify_plan_select, gsr_densify_plan_rows,
+gsr_prune_rows, gsr_scatter_rows, and gsr_densification_stats_filter, whose cases tests/test_gaussian_model_host.py holds) on a machine
+without a GPU: the header declares these six, the scratch query is what its contract says, the Python layer asks for a rebuild when the
+entries are missing, and every refusal the header lists returns GSR_E_INVALID with a message naming the entry.  (That the header, the
+library and the binding agree is tests/test_cabi.py's, for every header.)  The calls are made with fake pointers in a child process that
+sees no GPU (tests/cabi_child.py); `python test_cabi_densify.py` is that child."""
 import ctypes
-import json
-import os
-import re
-import subprocess
 import sys
 
 import pytest
 
-import cabi_args
-from cabi_args import FAKE, GSR_E_INVALID
+import cabi_child
+import cabi_header
+from cabi_args import FAKE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-HEADER = os.path.join(ROOT, "include", "gsr_hip_densify.h")
-ENTRIES = ("gsr_densify_plan_scratch_bytes", "gsr_densify_plan_select", "gsr_densify_plan_rows", "gsr_prune_rows", "gsr_scatter_rows")
-
-
-def _source():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+ENTRIES = ("gsr_densify_plan_scratch_bytes", "gsr_densify_plan_select", "gsr_densify_plan_rows", "gsr_prune_rows", "gsr_scatter_rows",
+           "gsr_densification_stats_filter")
 
 
-def _protos():
-    """[(return type, entry, argument text)] with the regex of tests/test_cabi.py."""
-    return re.findall(r"(int|size_t|const char\*)\s+(gsr_\w+)\s*\(([^;]*?)\)\s*;", _source(), flags=re.S)
+def test_header_declares_the_six_entries():
+    assert sorted(n for _, n, _ in cabi_header.protos("gsr_hip_densify.h")) == sorted(ENTRIES)
 
 
-def test_header_declares_the_entries_and_includes_the_main_header():
-    assert sorted(n for _, n, _ in _protos()) == sorted(ENTRIES)
-    assert re.search(r'#include "gsr_hip\.h"', open(HEADER).read())
-    assert "GSR_ABI_VERSION" not in open(HEADER).read()            # the version is the main header's, and stays
-
-
-def test_library_exports_them_and_the_lists_are_disjoint(hip_lib_built):
+def test_the_plan_struct_is_twelve_words(hip_lib_built):
     import _gsr
-    raw = ctypes.CDLL(_gsr.LIB_PATH)
-    for n in ENTRIES:
-        assert hasattr(raw, n), f"{n} declared in gsr_hip_densify.h but not exported by libgsr_hip.so"
-    assert sorted(_gsr.EXPORTED_DENSIFY) == sorted(ENTRIES)
-    for other in (_gsr.EXPORTED, _gsr.EXPORTED_TRAIN, _gsr.EXPORTED_SCOPE, _gsr.EXPORTED_ENVMAP):
-        assert not set(_gsr.EXPORTED_DENSIFY) & set(other)
-    for other in ("gsr_hip.h", "gsr_hip_train.h", "gsr_hip_scope.h", "gsr_hip_envmap.h"):
-        text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", other)).read(), flags=re.S)
-        for n in ENTRIES:
-            assert n not in text, (n, other)
-    assert _gsr.lib.gsr_version() == _gsr.GSR_ABI_VERSION == 102
-
-
-def test_ctypes_signatures_and_the_plan_struct_match_the_header(hip_lib_built):
-    import _gsr
-
-    def ctype(arg):
-        arg = arg.strip()
-        if arg.startswith("const gsr_densify_plan*"):
-            return ctypes.POINTER(_gsr.DensifyPlan)
-        if arg.startswith("const gsr_gather_group*"):
-            return ctypes.POINTER(_gsr.GatherGroup)
-        if "*" in arg:
-            return ctypes.c_void_p
-        for pre, t in (("float", ctypes.c_float), ("uint64_t", ctypes.c_uint64), ("size_t", ctypes.c_size_t), ("int", ctypes.c_int)):
-            if arg.startswith(pre):
-                return t
-        raise ValueError(arg)
-
-    for ret, name, args in _protos():
-        fn = getattr(_gsr.lib, name)
-        assert [ctype(a) for a in args.split(",")] == list(fn.argtypes), name
-        assert fn.restype is (ctypes.c_size_t if ret == "size_t" else ctypes.c_int), name
-    body = re.search(r"typedef struct \{([^}]*)\}\s*gsr_densify_plan;", _source(), flags=re.S).group(1)
-    fields = []
-    for decl in (d.strip() for d in body.split(";") if d.strip()):
-        ctype_, name = decl.split()
-        base = {"float": ctypes.c_float, "int": ctypes.c_int}[ctype_]
-        m = re.fullmatch(r"(\w+)\[(\d+)\]", name)
-        fields.append((m.group(1), base * int(m.group(2))) if m else (name, base))
-    assert fields == [(n, t) for n, t in _gsr.DensifyPlan._fields_]
     assert ctypes.sizeof(_gsr.DensifyPlan) == 12 * 4
 
 
@@ -109,7 +52,7 @@ def test_python_layer_asks_for_a_rebuild_when_the_entries_are_missing(hip_lib_bu
     real = gsr_densify.lib
 
     class Old:
-        """A library built before the densification plan: everything but the five entries."""
+        """A library built before the densification plan: everything but the entries of its header."""
         def __getattr__(self, name):
             if name in ENTRIES:
                 raise AttributeError(name)
@@ -203,74 +146,41 @@ def _changes(entry, case):
     raise KeyError(case)
 
 
-def _child():
-    os.environ.update(cabi_args.HIDE_GPUS)
-    sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-reflection_amd"))
-    import _gsr
-    n = cabi_args._visible_devices()
-    print(json.dumps({"devices": n}), flush=True)
-    if n != 0:
-        return 0
-    keep = []
-    for entry, case, _ in cases():
-        args = dict(BASE[entry], **_changes(entry, case))
-        if "plan" in args and args["plan"] is not None:
-            f = dict(PLAN0, **args["plan"])
-            plan = _gsr.DensifyPlan(f["max_grad"], f["min_weight"], f["dense_limit"], f["big_near"], f["big_far"], f["extent2"],
-                                    (ctypes.c_float * 3)(*f["mean"]), f["size_prune"], f["N"], f["scale_dims"])
-            keep.append(plan)
-            args["plan"] = ctypes.byref(plan)
-            N = f["N"]
-        else:
-            N = N0
-        sb = args.get("scratch_bytes")
-        if isinstance(sb, str):
-            query = int(_gsr.lib.gsr_densify_plan_scratch_bytes(args["P"], 1 if sb.startswith("query1") else N))
-            query = query or 1 << 40          # (sizes the query itself refuses: the entry must refuse them whatever the scratch)
-            args["scratch_bytes"] = query - 1 if sb.endswith("-1") else query
-        if args.get("groups") is not None:
-            arr = (_gsr.GatherGroup * 17)(*[_gsr.GatherGroup(*(args["groups"][0] if i == 0 else (0, 0, 1))) for i in range(17)])
-            keep.append(arr)
-            args["groups"] = arr
-        print(json.dumps({"begin": [entry, case]}), flush=True)
-        rc = getattr(_gsr.lib, entry)(*[args[k] for k in ARGS[entry]])
-        msg = _gsr.lib.gsr_last_error()
-        print(json.dumps({"done": [entry, case], "rc": int(rc), "msg": msg.decode(errors="replace") if msg else ""}), flush=True)
-    return 0
+_keep = []
+
+
+def _call(gsr, entry, case):
+    args = dict(BASE[entry], **_changes(entry, case))
+    if "plan" in args and args["plan"] is not None:
+        f = dict(PLAN0, **args["plan"])
+        plan = gsr.DensifyPlan(f["max_grad"], f["min_weight"], f["dense_limit"], f["big_near"], f["big_far"], f["extent2"],
+                               (ctypes.c_float * 3)(*f["mean"]), f["size_prune"], f["N"], f["scale_dims"])
+        _keep.append(plan)
+        args["plan"] = ctypes.byref(plan)
+        N = f["N"]
+    else:
+        N = N0
+    sb = args.get("scratch_bytes")
+    if isinstance(sb, str):
+        query = int(gsr.lib.gsr_densify_plan_scratch_bytes(args["P"], 1 if sb.startswith("query1") else N))
+        query = query or 1 << 40          # (sizes the query itself refuses: the entry must refuse them whatever the scratch)
+        args["scratch_bytes"] = query - 1 if sb.endswith("-1") else query
+    if args.get("groups") is not None:
+        arr = (gsr.GatherGroup * 17)(*[gsr.GatherGroup(*(args["groups"][0] if i == 0 else (0, 0, 1))) for i in range(17)])
+        _keep.append(arr)
+        args["groups"] = arr
+    return getattr(gsr.lib, entry)(*[args[k] for k in ARGS[entry]])
 
 
 @pytest.fixture(scope="module")
 def outcomes(hip_lib_built):
-    env = dict(os.environ, **cabi_args.HIDE_GPUS)
-    p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
-    done, begun = {}, None
-    for line in p.stdout.splitlines():
-        if not line.startswith("{"):
-            continue
-        rec = json.loads(line)
-        if "devices" in rec and rec["devices"] != 0:
-            return None
-        if "begin" in rec:
-            begun = tuple(rec["begin"])
-        elif "done" in rec:
-            done[tuple(rec["done"])] = rec
-            begun = None
-    assert p.returncode == 0 and begun is None, f"the child ended in {begun} (exit {p.returncode}):\n{p.stderr[-2000:]}"
-    return done
+    return cabi_child.run(__file__)
 
 
 @pytest.mark.parametrize("entry, case, expect", cases(), ids=lambda v: v)
 def test_refusal(outcomes, entry, case, expect):
-    if outcomes is None:
-        pytest.skip("a GPU is still visible to the child process although the visible-devices variables hide them: nothing is called")
-    got = outcomes.get((entry, case))
-    assert got is not None, "the child never reached this call"
-    if expect == "refused":
-        assert got["rc"] == GSR_E_INVALID, (entry, case, got)
-        assert got["msg"].startswith(entry), (entry, case, got["msg"])
-    else:
-        assert got["rc"] == 0, (entry, case, got)
+    cabi_child.check(outcomes, entry, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(_child())
+    sys.exit(cabi_child.serve([c[:2] for c in cases()], _call))

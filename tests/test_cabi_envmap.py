@@ -1,72 +1,15 @@
-"""The environment-map entries (include/gsr_hip_envmap.h: gsr_envmap_resize, gsr_envmap_sharpen) on a machine without a GPU: the header
-parses as include/gsr_hip.h does, the library exports the two, the ctypes prototypes match, and every refusal the header lists returns
-GSR_E_INVALID with a message naming the entry.  The calls are made with fake pointers in ONE child process that hides every GPU and asks
-the HIP runtime for the device count first (tests/cabi_args.py's guard, by import); with a device still visible nothing is called.
-`python test_cabi_envmap.py` is that child."""
-import ctypes
-import json
-import os
-import re
-import subprocess
+"""The environment-map entries (include/gsr_hip_envmap.h: gsr_envmap_resize, gsr_envmap_sharpen) on a machine without a GPU: every refusal
+the header lists returns GSR_E_INVALID with a message naming the entry, and the Python layer asks for a rebuild when the entries are
+missing.  (That the header, the library and the binding agree is tests/test_cabi.py's, for every header.)  The calls are made with fake
+pointers in a child process that sees no GPU (tests/cabi_child.py); `python test_cabi_envmap.py` is that child."""
 import sys
 
 import pytest
 
-import cabi_args
-from cabi_args import FAKE, GSR_E_INVALID
+import cabi_child
+from cabi_args import FAKE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-HEADER = os.path.join(ROOT, "include", "gsr_hip_envmap.h")
 ENTRIES = ("gsr_envmap_resize", "gsr_envmap_sharpen")
-
-
-def _source():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _protos():
-    """[(return type, entry, argument text)] with the regex of tests/test_cabi.py."""
-    return re.findall(r"(int|size_t|const char\*)\s+(gsr_\w+)\s*\(([^;]*?)\)\s*;", _source(), flags=re.S)
-
-
-def test_header_declares_the_two_entries_and_includes_the_main_header():
-    assert sorted(n for _, n, _ in _protos()) == sorted(ENTRIES)
-    assert re.search(r'#include "gsr_hip\.h"', open(HEADER).read())
-    assert "GSR_ABI_VERSION" not in open(HEADER).read()            # the version is the main header's, and stays
-
-
-def test_library_exports_them_and_the_lists_are_disjoint(hip_lib_built):
-    import _gsr
-    raw = ctypes.CDLL(_gsr.LIB_PATH)
-    for n in ENTRIES:
-        assert hasattr(raw, n), f"{n} declared in gsr_hip_envmap.h but not exported by libgsr_hip.so"
-    assert sorted(_gsr.EXPORTED_ENVMAP) == sorted(ENTRIES)
-    for other in (_gsr.EXPORTED, _gsr.EXPORTED_TRAIN, _gsr.EXPORTED_SCOPE):
-        assert not set(_gsr.EXPORTED_ENVMAP) & set(other)
-    for other in ("gsr_hip.h", "gsr_hip_train.h", "gsr_hip_scope.h"):
-        text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", other)).read(), flags=re.S)
-        for n in ENTRIES:
-            assert n not in text, (n, other)
-    assert _gsr.lib.gsr_version() == _gsr.GSR_ABI_VERSION == 102
-
-
-def test_ctypes_signatures_match_header(hip_lib_built):
-    import _gsr
-
-    def ctype(arg):
-        arg = arg.strip()
-        if "*" in arg:
-            return ctypes.c_void_p
-        for pre, t in (("float", ctypes.c_float), ("size_t", ctypes.c_size_t), ("int", ctypes.c_int)):
-            if arg.startswith(pre):
-                return t
-        raise ValueError(arg)
-
-    for ret, name, args in _protos():
-        fn = getattr(_gsr.lib, name)
-        assert [ctype(a) for a in args.split(",")] == list(fn.argtypes), name
-        assert fn.restype is ctypes.c_int, name
 
 
 def test_python_layer_asks_for_a_rebuild_when_the_entries_are_missing(hip_lib_built, monkeypatch):
@@ -152,56 +95,21 @@ def _changes(entry, case):
     raise KeyError(case)
 
 
-def _child():
-    os.environ.update(cabi_args.HIDE_GPUS)
-    sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-reflection_amd"))
-    import _gsr
-    n = cabi_args._visible_devices()
-    print(json.dumps({"devices": n}), flush=True)
-    if n != 0:
-        return 0
-    for entry, case, _ in cases():
-        args = dict(BASE[entry], **_changes(entry, case))
-        names = RESIZE_ARGS if entry == "gsr_envmap_resize" else SHARPEN_ARGS
-        print(json.dumps({"begin": [entry, case]}), flush=True)
-        rc = getattr(_gsr.lib, entry)(*[args[k] for k in names])
-        msg = _gsr.lib.gsr_last_error()
-        print(json.dumps({"done": [entry, case], "rc": int(rc), "msg": msg.decode(errors="replace") if msg else ""}), flush=True)
-    return 0
+def _call(gsr, entry, case):
+    args = dict(BASE[entry], **_changes(entry, case))
+    names = RESIZE_ARGS if entry == "gsr_envmap_resize" else SHARPEN_ARGS
+    return getattr(gsr.lib, entry)(*[args[k] for k in names])
 
 
 @pytest.fixture(scope="module")
 def outcomes(hip_lib_built):
-    env = dict(os.environ, **cabi_args.HIDE_GPUS)
-    p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
-    done, begun = {}, None
-    for line in p.stdout.splitlines():
-        if not line.startswith("{"):
-            continue
-        rec = json.loads(line)
-        if "devices" in rec and rec["devices"] != 0:
-            return None
-        if "begin" in rec:
-            begun = tuple(rec["begin"])
-        elif "done" in rec:
-            done[tuple(rec["done"])] = rec
-            begun = None
-    assert p.returncode == 0 and begun is None, f"the child ended in {begun} (exit {p.returncode}):\n{p.stderr[-2000:]}"
-    return done
+    return cabi_child.run(__file__)
 
 
 @pytest.mark.parametrize("entry, case, expect", cases(), ids=lambda v: v)
 def test_refusal(outcomes, entry, case, expect):
-    if outcomes is None:
-        pytest.skip("a GPU is still visible to the child process although the visible-devices variables hide them: nothing is called")
-    got = outcomes.get((entry, case))
-    assert got is not None, "the child never reached this call"
-    if expect == "refused":
-        assert got["rc"] == GSR_E_INVALID, (entry, case, got)
-        assert got["msg"].startswith(entry), (entry, case, got["msg"])
-    else:
-        assert got["rc"] != GSR_E_INVALID, (entry, case, got)
+    cabi_child.check(outcomes, entry, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(_child())
+    sys.exit(cabi_child.serve([c[:2] for c in cases()], _call))

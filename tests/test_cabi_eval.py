@@ -1,6 +1,5 @@
-"""The inference-only surfel forward's C entry (gsr_surfel_forward_eval, ABI 102) on a machine without a GPU: declared, exported and
-bound with the header's argument list, and every refusal of it and of the training forward (gsr_surfel_forward_refl) happens before the
-first allocation or device call.  Also: the build digest covers every local header the sources include, so that an edit to any of them
+"""The inference-only surfel forward's C entry (gsr_surfel_forward_eval, ABI 102) on a machine without a GPU: every refusal of it and of
+the training forward (gsr_surfel_forward_refl) happens before the first allocation or device call.  Also: the build digest covers every local header the sources include, so that an edit to any of them
 rebuilds the library."""
 import ctypes
 import os
@@ -8,43 +7,22 @@ import re
 
 import pytest
 
+import cabi_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gaussian-splatting-reflection_amd", "csrc")
-HEADER = os.path.join(ROOT, "include", "gsr_hip.h")
 GSR_E_INVALID = -1
 
 
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def test_eval_entry_is_declared_exported_and_bound(hip_lib_built):
+def test_eval_entry_takes_31_arguments(hip_lib_built):
     import _gsr
-    m = re.search(r"int\s+gsr_surfel_forward_eval\s*\(([^;]*?)\)\s*;", _header(), flags=re.S)
-    assert m, "gsr_surfel_forward_eval is not declared in gsr_hip.h"
-    assert hasattr(ctypes.CDLL(_gsr.LIB_PATH), "gsr_surfel_forward_eval")
-    assert "gsr_surfel_forward_eval" in _gsr.EXPORTED
-    P, F, I = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
-    want = []
-    for arg in (a.strip() for a in m.group(1).split(",")):
-        if arg.startswith("gsr_alloc_fn"):
-            want.append(_gsr.ALLOC_FN)
-        elif arg.startswith("const gsr_refl_forward*"):
-            want.append(ctypes.POINTER(_gsr.ReflForward))
-        elif "*" in arg:
-            want.append(P)
-        elif arg.startswith("float"):
-            want.append(F)
-        else:
-            assert arg.startswith("int"), arg
-            want.append(I)
-    assert len(want) == 31
-    assert list(_gsr.lib.gsr_surfel_forward_eval.argtypes) == want
+    args = {name: a for _, name, a in cabi_header.protos("gsr_hip.h")}["gsr_surfel_forward_eval"]
+    assert len(args) == 31 == len(_gsr.lib.gsr_surfel_forward_eval.argtypes)
 
 
 def test_abi_version_is_102(hip_lib_built):
     import _gsr
-    hdr = open(HEADER).read()
+    hdr = cabi_header.text("gsr_hip.h")
     assert int(re.search(r"#define GSR_ABI_VERSION (\d+)", hdr).group(1)) == 102
     assert _gsr.GSR_ABI_VERSION == 102
     assert _gsr.lib.gsr_version() == 102

@@ -1,25 +1,17 @@
-"""scene.GaussianModel and gsr_densification_stats_filter (include/gsr_hip_densify_stats.h) on a machine without a GPU: the class is
-importable under both of the reference's names and behaves as the reference's before it has points; the header declares the entry, the
-library exports it, the ctypes prototype matches, and every refusal the header lists returns GSR_E_INVALID with a message naming the
-entry.  The calls are made with fake pointers in ONE child process that hides every GPU and asks the HIP runtime for the device count first
-(tests/cabi_args.py's guard, as tests/test_cabi_densify.py uses it); with a device still visible nothing is called.
-`python test_gaussian_model_host.py` is that child."""
-import ctypes
+"""scene.GaussianModel and gsr_densification_stats_filter (include/gsr_hip_densify.h) on a machine without a GPU: the class is importable
+under both of the reference's names and behaves as the reference's before it has points; the header names the entry's arguments as this
+file does, and every refusal the header lists returns GSR_E_INVALID with a message naming the entry.  (That the header, the library and
+the binding agree is tests/test_cabi.py's, for every header.)  The calls are made with fake pointers in a child process that sees no GPU
+(tests/cabi_child.py); `python test_gaussian_model_host.py` is that child."""
 import inspect
-import json
-import os
-import re
-import subprocess
 import sys
 
 import pytest
 
-import cabi_args
-from cabi_args import FAKE, GSR_E_INVALID
+import cabi_child
+import cabi_header
+from cabi_args import FAKE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-HEADER = os.path.join(ROOT, "include", "gsr_hip_densify_stats.h")
 ENTRY = "gsr_densification_stats_filter"
 ARGS = ("P", "grad_means2D", "update_filter", "gaussian_weights", "xyz_gradient_accum", "denom", "accum_w", "denom_w", "stream")
 POINTERS = ARGS[1:-1]
@@ -75,81 +67,29 @@ def test_a_model_without_points_is_the_reference_s_empty_model(hip_lib_built):
 
 
 # ------------------------------------------------------------------------------------------------- the entry
-def _protos():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return re.findall(r"(int|size_t|const char\*)\s+(gsr_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)
-
-
-def test_header_library_and_prototype_agree(hip_lib_built):
-    import _gsr
-    protos = _protos()
-    assert [n for _, n, _ in protos] == [ENTRY]
-    ret, _, args = protos[0]
-    assert [re.sub(r".*[\s\*]", "", a.strip()) for a in args.split(",")] == list(ARGS)
-    assert "GSR_ABI_VERSION" not in open(HEADER).read() and _gsr.lib.gsr_version() == _gsr.GSR_ABI_VERSION == 102
-    assert hasattr(ctypes.CDLL(_gsr.LIB_PATH), ENTRY), f"{ENTRY} is not exported by libgsr_hip.so"
-    fn = getattr(_gsr.lib, ENTRY)
-    assert list(fn.argtypes) == [ctypes.c_void_p if "*" in a else ctypes.c_int for a in args.split(",")] and fn.restype is ctypes.c_int and ret == "int"
-    assert _gsr.EXPORTED_DENSIFY_STATS == [ENTRY]
-    for other in (_gsr.EXPORTED, _gsr.EXPORTED_TRAIN, _gsr.EXPORTED_SCOPE, _gsr.EXPORTED_ENVMAP, _gsr.EXPORTED_DENSIFY):
-        assert ENTRY not in other
-    # a host that includes the densification header has the whole interface
-    assert re.search(r'#include "gsr_hip_densify_stats\.h"', open(os.path.join(ROOT, "include", "gsr_hip_densify.h")).read())
+def test_header_names_the_arguments_in_this_order():
+    args = {name: a for _, name, a in cabi_header.protos("gsr_hip_densify.h")}[ENTRY]
+    assert cabi_header.arg_names(args) == list(ARGS)
 
 
 def cases():
     return [(k, "refused") for k in REFUSED] + [(k, "noop") for k in NOOPS]
 
 
-def _child():
-    os.environ.update(cabi_args.HIDE_GPUS)
-    sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-reflection_amd"))
-    import _gsr
-    n = cabi_args._visible_devices()
-    print(json.dumps({"devices": n}), flush=True)
-    if n != 0:
-        return 0
-    for case, _ in cases():
-        args = dict(BASE, **(REFUSED[case] if case in REFUSED else NOOPS[case]))
-        print(json.dumps({"begin": case}), flush=True)
-        rc = getattr(_gsr.lib, ENTRY)(*[args[k] for k in ARGS])
-        msg = _gsr.lib.gsr_last_error()
-        print(json.dumps({"done": case, "rc": int(rc), "msg": msg.decode(errors="replace") if msg else ""}), flush=True)
-    return 0
+def _call(gsr, entry, case):
+    args = dict(BASE, **(REFUSED[case] if case in REFUSED else NOOPS[case]))
+    return getattr(gsr.lib, entry)(*[args[k] for k in ARGS])
 
 
 @pytest.fixture(scope="module")
 def outcomes(hip_lib_built):
-    env = dict(os.environ, **cabi_args.HIDE_GPUS)
-    p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
-    done, begun = {}, None
-    for line in p.stdout.splitlines():
-        if not line.startswith("{"):
-            continue
-        rec = json.loads(line)
-        if "devices" in rec and rec["devices"] != 0:
-            return None
-        if "begin" in rec:
-            begun = rec["begin"]
-        elif "done" in rec:
-            done[rec["done"]] = rec
-            begun = None
-    assert p.returncode == 0 and begun is None, f"the child ended in {begun} (exit {p.returncode}):\n{p.stderr[-2000:]}"
-    return done
+    return cabi_child.run(__file__)
 
 
 @pytest.mark.parametrize("case, expect", cases(), ids=lambda v: v)
 def test_refusal(outcomes, case, expect):
-    if outcomes is None:
-        pytest.skip("a GPU is still visible to the child process although the visible-devices variables hide them: nothing is called")
-    got = outcomes.get(case)
-    assert got is not None, "the child never reached this call"
-    if expect == "refused":
-        assert got["rc"] == GSR_E_INVALID, (case, got)
-        assert got["msg"].startswith(ENTRY), (case, got["msg"])
-    else:
-        assert got["rc"] == 0, (case, got)
+    cabi_child.check(outcomes, ENTRY, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(_child())
+    sys.exit(cabi_child.serve([(ENTRY, case) for case, _ in cases()], _call))

@@ -2,21 +2,13 @@
 header's argument lists, every refusal happens before any device work, the drop-in module imports and validates its input, and
 gsr_init.load_point_cloud reads the reference's input clouds."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gsr_hip.h")
 GSR_E_INVALID = -1
 FAKE = 0x7f0000000000          # 256-byte aligned, never dereferenced: every call below must fail validation first
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
 @pytest.mark.parametrize("name, ret, args", [
@@ -24,16 +16,11 @@ def _header():
     ("gsr_knn_mean_dist", "int", [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 ])
 def test_knn_entries_are_declared_exported_and_bound(hip_lib_built, name, ret, args):
+    """The two signatures, spelled out (tests/test_cabi.py holds every entry to its header and to the library's exports)."""
     import _gsr
-    m = re.search(r"(\w+)\s+%s\s*\(([^;]*?)\)\s*;" % name, _header(), flags=re.S)
-    assert m, f"{name} is not declared in gsr_hip.h"
-    assert m.group(1) == ret
-    assert hasattr(ctypes.CDLL(_gsr.LIB_PATH), name)
-    assert name in _gsr.EXPORTED
     fn = getattr(_gsr.lib, name)
     assert list(fn.argtypes) == args
     assert fn.restype == (ctypes.c_size_t if ret == "size_t" else ctypes.c_int)
-    assert _gsr.lib.gsr_version() == 102
 
 
 def test_scratch_bytes_covers_the_point_arrays(hip_lib_built):
