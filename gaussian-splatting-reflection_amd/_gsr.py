@@ -173,6 +173,12 @@ ABI = [
     # add_densification_stats under the reference's boolean filter: scene.GaussianModel (one commit younger than the five above)
     ("gsr_hip_densify.h", "csrc/gsr_densify.hip", True, [
         ("gsr_densification_stats_filter", I, [I, P, P, P, P, P, P, P, P])]),
+    # TSDF fusion of rendered depth maps and the iso-surface as an indexed mesh: gsr_mesh, utils.mesh_utils
+    ("gsr_hip_mesh.h", "csrc/gsr_mesh.hip", True, [
+        ("gsr_tsdf_integrate", I, [P, P, P, I, I, I, F, F, F, F, P, P, P, F, I, I, P, P, F, F, P]),
+        ("gsr_mesh_scratch_bytes", c_size_t, [I, I, I]),
+        ("gsr_mesh_count", I, [P, P, I, I, I, F, P, c_size_t, P, P]),
+        ("gsr_mesh_emit", I, [P, P, P, I, I, I, F, F, F, F, F, P, P, P, P, U64, U64, P])]),
 ]
 
 ENTRIES_BY_HEADER = {}          # {header file name: [entry names]}, what tests/test_cabi.py holds each header to

@@ -1,0 +1,542 @@
+// Mesh extraction (include/gsr_hip_mesh.h has the contracts): TSDF fusion of one rendered depth map into a dense voxel grid, and the
+// iso-surface of the grid as an indexed mesh by marching tetrahedra on the Kuhn split.
+//
+// gsr_tsdf_integrate is a streaming pass: per node ~40 flops, one gathered depth read and two to five plane reads and writes.  A
+// workgroup is four waves; a wave owns a run of 64 nodes along x (one 256-byte line per plane and instruction) and walks TSDF_KZ slices of
+// z with it, the parts of the dot products that do not depend on z hoisted.  Every skip rule is decided from registers and the gathered
+// depth before a plane is touched, so a node outside the view costs a dozen instructions and no traffic.  (A per-wave test of the wave's
+// box against the frustum, leaving before the node loop, was built and measured: 0.217 ms with it, 0.215 ms without, for a 1080p view
+// into 512^3 from a face of the box — it costs as much as the eight skips it saves, and is gone.  DESIGN.md, "Mesh extraction".)
+//
+// The extraction is five kernels over the nodes in linear order, 256 per block, no atomics and no waiting between workgroups:
+//   classify    node -> valid | inside << 1                                                           (reads tsdf and weight once)
+//   count       node -> the 7-bit mask of the lattice edges leaving it that carry a vertex, bit 7 = its cell is valid, and the cell's
+//               triangle count, from the 27 classes around it; block sums of both counts
+//   spine       ONE block scans the block sums (64-bit carries: the totals are exact) and writes counts[0..1]
+//   offsets     node -> exclusive vertex and triangle offsets (block scan + the block's base)
+//   emit        node -> its vertices, and its cell's triangles with the vertex indices looked up at the cell's corners
+// Offsets are 32-bit: they are exact whenever the totals are below 2^31, and gsr_mesh_emit refuses larger ones.
+#include <cmath>
+#include <initializer_list>
+#include "gsr_internal.hpp"
+#include "../../include/gsr_hip_mesh.h"
+
+namespace gsr {
+
+#define TSDF_KZ 8                 // z slices a wave walks
+#define TSDF_ROWS 4               // waves (rows of y) per block
+#define TSDF_MAX_GRID 65536u      // blocks per launch; the kernel strides over the rest
+
+struct TsdfArgs {
+	float* tsdf; float* weight; float* color;
+	const float* depth; const float* rgb; const float* alpha;
+	const float* view; const float* proj;
+	int nx, ny, nz, W, H;
+	float ox, oy, oz, voxel, alpha_min, sdf_trunc, depth_trunc;
+	uint32_t bx, bxy, nblocks;    // blocks along x, in one slab of TSDF_KZ slices, in all (< 2^28, see gsr_tsdf_integrate)
+};
+
+__global__ void __launch_bounds__(64 * TSDF_ROWS)
+tsdf_integrate_kernel(const TsdfArgs a) {
+	float V[4], P[12];            // the rows of the two matrices the kernel needs: view z; projection x, y, w
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		V[c] = a.view[4 * c + 2];
+		P[c] = a.proj[4 * c];
+		P[4 + c] = a.proj[4 * c + 1];
+		P[8 + c] = a.proj[4 * c + 3];
+	}
+	const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+	const size_t plane = (size_t)a.nx * a.ny, vol = plane * a.nz;
+	for (uint32_t b = blockIdx.x; b < a.nblocks; b += gridDim.x) {
+		const uint32_t slab = b / a.bxy, bxy = b - slab * a.bxy, brow = bxy / a.bx;
+		const int k0 = (int)slab * TSDF_KZ;
+		const int i0 = (int)(bxy - brow * a.bx) * 64, j = (int)brow * TSDF_ROWS + row;
+		if (j >= a.ny) continue;                                   // (the whole wave: no lane of it has a node)
+		const int i = i0 + lane;
+		const int k1 = min(k0 + TSDF_KZ, a.nz);
+		if (i >= a.nx) continue;
+		const float X = fmaf(a.voxel, (float)i, a.ox), Y = fmaf(a.voxel, (float)j, a.oy);
+		// the part of the four dot products that does not change along z
+		const float zxy = fmaf(V[0], X, fmaf(V[1], Y, V[3]));
+		const float xxy = fmaf(P[0], X, fmaf(P[1], Y, P[3]));
+		const float yxy = fmaf(P[4], X, fmaf(P[5], Y, P[7]));
+		const float wxy = fmaf(P[8], X, fmaf(P[9], Y, P[11]));
+		size_t node = (size_t)k0 * plane + (size_t)j * a.nx + i;       // < 2^31
+#pragma unroll 2
+		for (int k = k0; k < k1; k++, node += plane) {
+			const float Z = fmaf(a.voxel, (float)k, a.oz);
+			const float z = fmaf(V[2], Z, zxy), pw = fmaf(P[10], Z, wxy);
+			if (!(z > 0.f && pw > 0.f)) continue;
+			const float fx = ((fmaf(P[2], Z, xxy) / pw + 1.f) * (float)a.W - 1.f) * 0.5f;
+			const float fy = ((fmaf(P[6], Z, yxy) / pw + 1.f) * (float)a.H - 1.f) * 0.5f;
+			const float ru = rintf(fx), rv = rintf(fy);
+			if (!(ru >= 0.f && ru < (float)a.W && rv >= 0.f && rv < (float)a.H)) continue;      // (NaN: skipped)
+			const size_t pix = (size_t)(int)rv * a.W + (int)ru;
+			const float d = a.depth[pix];
+			if (!(d > 0.f && d <= a.depth_trunc)) continue;
+			if (a.alpha && !(a.alpha[pix] >= a.alpha_min)) continue;
+			const float sdf = d - z;
+			if (sdf < -a.sdf_trunc) continue;
+			const float t = fminf(1.f, sdf / a.sdf_trunc);
+			const float w = a.weight[node], w1 = w + 1.f;
+			a.tsdf[node] = (a.tsdf[node] * w + t) / w1;
+			if (a.color) {
+				const size_t hw = (size_t)a.W * a.H;
+#pragma unroll
+				for (int c = 0; c < 3; c++) a.color[c * vol + node] = (a.color[c * vol + node] * w + a.rgb[c * hw + pix]) / w1;
+			}
+			a.weight[node] = w1;
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------------------ the iso-surface
+#define MESH_BLOCK 256
+#define NODE_VALID 1u
+#define NODE_INSIDE 2u
+#define CELL_VALID 0x80u          // bit 7 of a node's vertex mask: the cell whose low corner it is is valid
+
+// scratch of gsr_mesh_count, shared with gsr_mesh_emit: offsets in bytes, each a multiple of 256
+struct MeshScratch {
+	size_t cls, vmask, tcnt, vert_off, tri_off, part, vbase, tbase, bytes;
+	uint32_t nblocks;
+};
+static MeshScratch mesh_scratch(uint64_t N) {
+	MeshScratch s;
+	s.nblocks = (uint32_t)((N + MESH_BLOCK - 1) / MESH_BLOCK);
+	size_t off = 0;
+	auto take = [&](size_t bytes) { size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
+	s.cls = take(N);                       // uint8  node class
+	s.vmask = take(N);                     // uint8  vertex mask | CELL_VALID
+	s.tcnt = take(N);                      // uint8  triangles of the node's cell (0..12)
+	s.vert_off = take(4 * N);              // uint32 exclusive vertex offset of the node
+	s.tri_off = take(4 * N);               // uint32 exclusive triangle offset of the node's cell
+	s.part = take(4 * (size_t)s.nblocks);  // uint32 block sums: vertices | triangles << 16
+	s.vbase = take(4 * (size_t)s.nblocks); // uint32 vertices in front of the block
+	s.tbase = take(4 * (size_t)s.nblocks); // uint32 triangles in front of the block
+	s.bytes = off;
+	return s;
+}
+
+// Case table of a positively oriented tetrahedron, indexed by the inside mask over (p0..p3): bits 0-1 the triangle count, then three
+// bits per corner, the edges numbered 01, 02, 03, 12, 13, 23 = 0..5 (include/gsr_hip_mesh.h states the rule; tests/mesh_ref.py generates
+// the same table from it).
+__constant__ uint32_t TET_CASES[16] = {0x00000u, 0x00221u, 0x00381u, 0x70c46u, 0x00565u, 0xad30au, 0x34582u, 0x00589u,
+                                       0x004a9u, 0x94522u, 0xa9a0eu, 0x003a5u, 0x50c66u, 0x00461u, 0x00141u, 0x00000u};
+// the two ends of edge 0..5 as local vertices, two bits each: lo in bits 0-1, hi in bits 2-3
+#define EDGE_ENDS(e) ((0xed9c84u >> (4 * (e))) & 15u)      // 01 -> 0x4, 02 -> 0x8, 03 -> 0xc, 12 -> 0x9, 13 -> 0xd, 23 -> 0xe
+// direction number of a corner difference given as bits (x = 1, y = 2, z = 4): 100, 010, 110, 001, 101, 011, 111 -> 0, 1, 3, 2, 4, 5, 6
+#define DIR_OF_BITS(m) ((0x65423100u >> (4 * (m))) & 7u)
+
+__device__ __forceinline__ uint32_t tet_triangles(uint32_t inside4) { return TET_CASES[inside4] & 3u; }
+
+// corner offsets (bits x = 1, y = 2, z = 4) of p0..p3 of tetrahedron t, one nibble each
+__device__ __forceinline__ uint32_t tet_corner_bits(int t) {
+	// (a, b) = (0,1) (0,2) (1,0) (1,2) (2,0) (2,1): the second axis is the (t & 1)'th of the two that are not a
+	const int a = t >> 1;
+	const int b2 = (a == 0) ? 1 + (t & 1) : (a == 1) ? 2 * (t & 1) : (t & 1);
+	const uint32_t p1 = 1u << a, p2 = p1 | (1u << b2);
+	return (p1 << 4) | (p2 << 8) | (7u << 12);
+}
+
+__device__ __forceinline__ void node_ijk(uint32_t n, int nx, int ny, int& i, int& j, int& k) {
+	const uint32_t row = n / (uint32_t)nx;
+	i = (int)(n - row * (uint32_t)nx);
+	k = (int)(row / (uint32_t)ny);
+	j = (int)(row - (uint32_t)k * (uint32_t)ny);
+}
+
+__global__ void __launch_bounds__(MESH_BLOCK)
+mesh_classify_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, uint32_t N, float min_weight, uint8_t* __restrict__ cls) {
+	const uint32_t n = blockIdx.x * MESH_BLOCK + threadIdx.x;
+	if (n >= N) return;
+	cls[n] = (uint8_t)((weight[n] >= min_weight ? NODE_VALID : 0u) | (tsdf[n] < 0.f ? NODE_INSIDE : 0u));
+}
+
+// Sum over the block of a value below 2^16 per thread in each half of `v`; valid in every thread.
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {
+#pragma unroll
+	for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s);
+	if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+	__syncthreads();
+	v = lds[0] + lds[1] + lds[2] + lds[3];
+	__syncthreads();
+	return v;
+}
+
+// Exclusive scan over the block (MESH_BLOCK threads) of `v`.
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* lds) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	uint32_t inc = v;
+#pragma unroll
+	for (int s = 1; s < 64; s <<= 1) {
+		const uint32_t up = __shfl_up(inc, s);
+		if (lane >= s) inc += up;
+	}
+	if (lane == 63) lds[wave] = inc;
+	__syncthreads();
+	uint32_t base = 0;
+	for (int w = 0; w < wave; w++) base += lds[w];
+	__syncthreads();
+	return base + inc - v;
+}
+
+__global__ void __launch_bounds__(MESH_BLOCK)
+mesh_count_kernel(const uint8_t* __restrict__ cls, uint32_t N, int nx, int ny, int nz, uint8_t* __restrict__ vmask, uint8_t* __restrict__ tcnt,
+                  uint32_t* __restrict__ part) {
+	__shared__ uint32_t lds[4];
+	const uint32_t n = blockIdx.x * MESH_BLOCK + threadIdx.x;
+	uint32_t vm = 0, nt = 0;
+	// an invalid node starts no vertex and its cell is invalid: most of a fused volume is unobserved, and leaves here after one byte
+	if (n < N && !(cls[n] & NODE_VALID)) {
+		vmask[n] = 0;
+		tcnt[n] = 0;
+	} else if (n < N) {
+		int i, j, k;
+		node_ijk(n, nx, ny, i, j, k);
+		// valid and inside bits of the 27 nodes around n, bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); outside the grid: invalid
+		uint32_t valid = 0, inside = 0;
+#pragma unroll
+		for (int dz = -1; dz <= 1; dz++)
+#pragma unroll
+			for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+				for (int dx = -1; dx <= 1; dx++) {
+					const int x = i + dx, y = j + dy, z = k + dz;
+					if (x < 0 || y < 0 || z < 0 || x >= nx || y >= ny || z >= nz) continue;
+					const uint32_t c = cls[(size_t)n + (ptrdiff_t)dx + (ptrdiff_t)dy * nx + (ptrdiff_t)dz * ((ptrdiff_t)nx * ny)];
+					const int bit = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1);
+					valid |= (c & NODE_VALID) << bit;
+					inside |= ((c & NODE_INSIDE) >> 1) << bit;
+				}
+		// the eight nodes of the cell whose low corner is the node at bit 0: bits {0,1} + {0,3} + {0,9}
+		const uint32_t CELL = 1u | 2u | 8u | 16u | 512u | 1024u | 4096u | 8192u;
+		// cell_ok bit (cz * 4 + cy * 2 + cx) for the cell with low corner n - (1,1,1) + (cx, cy, cz)
+		uint32_t cell_ok = 0;
+#pragma unroll
+		for (int c = 0; c < 8; c++) {
+			const int low = (c >> 2) * 9 + ((c >> 1) & 1) * 3 + (c & 1);
+			if (((valid >> low) & CELL) == CELL) cell_ok |= 1u << c;
+		}
+		const uint32_t centre = 13;
+		const uint32_t in0 = (inside >> centre) & 1u;
+#pragma unroll
+		for (int e = 0; e < 7; e++) {
+			const int db = (e < 3) ? (1 << e) : (e == 3) ? 3 : (e == 4) ? 5 : (e == 5) ? 6 : 7;     // x = 1, y = 2, z = 4
+			const int far = centre + (db & 1) + ((db >> 1) & 1) * 3 + (db >> 2) * 9;
+			if (!((valid >> centre) & (valid >> far) & 1u) || ((inside >> far) & 1u) == in0) continue;
+			// cells that hold the edge: low corner n on the axes of the edge (cell coordinate 1), n or n - 1 on the others
+			uint32_t held = 0;
+#pragma unroll
+			for (int c = 0; c < 8; c++)
+				if ((c & db) == db) held |= (cell_ok >> c) & 1u;
+			if (held) vm |= 1u << e;
+		}
+		if ((cell_ok >> 7) & 1u) {           // the node's own cell
+			vm |= CELL_VALID;
+			// inside bits of the cell's corners, bit (x + 2y + 4z)
+			uint32_t corner = 0;
+#pragma unroll
+			for (int c = 0; c < 8; c++) corner |= ((inside >> (centre + (c & 1) + ((c >> 1) & 1) * 3 + (c >> 2) * 9)) & 1u) << c;
+#pragma unroll
+			for (int t = 0; t < 6; t++) {
+				const uint32_t p = tet_corner_bits(t);
+				const uint32_t m = (corner & 1u) | (((corner >> ((p >> 4) & 7u)) & 1u) << 1) | (((corner >> ((p >> 8) & 7u)) & 1u) << 2) |
+				                   (((corner >> 7) & 1u) << 3);
+				nt += tet_triangles(m);
+			}
+		}
+		vmask[n] = (uint8_t)vm;
+		tcnt[n] = (uint8_t)nt;
+	}
+	const uint32_t sum = block_sum(__popc(vm & 0x7fu) | (nt << 16), lds);
+	if (threadIdx.x == 0) part[blockIdx.x] = sum;
+}
+
+// One block: exclusive scan of the block sums, 1024 per round, with 64-bit carries; the totals go to counts[0..1].
+__global__ void __launch_bounds__(1024)
+mesh_spine_kernel(const uint32_t* __restrict__ part, uint32_t nblocks, uint32_t* __restrict__ vbase, uint32_t* __restrict__ tbase,
+                  unsigned long long* __restrict__ counts) {
+	__shared__ uint32_t wv[16], wt[16];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	unsigned long long carry_v = 0, carry_t = 0;
+	for (uint32_t at = 0; at < nblocks; at += 1024) {
+		const uint32_t b = at + threadIdx.x;
+		const uint32_t p = b < nblocks ? part[b] : 0u;
+		const uint32_t v = p & 0xffffu, t = p >> 16;
+		uint32_t iv = v, it = t;                                    // (a round sums to at most 1024 * 3072)
+#pragma unroll
+		for (int s = 1; s < 64; s <<= 1) {
+			const uint32_t uv = __shfl_up(iv, s), ut = __shfl_up(it, s);
+			if (lane >= s) { iv += uv; it += ut; }
+		}
+		if (lane == 63) { wv[wave] = iv; wt[wave] = it; }
+		__syncthreads();
+		uint32_t bv = 0, bt = 0, round_v = 0, round_t = 0;
+		for (int w = 0; w < 16; w++) {
+			if (w < wave) { bv += wv[w]; bt += wt[w]; }
+			round_v += wv[w];
+			round_t += wt[w];
+		}
+		if (b < nblocks) {
+			vbase[b] = (uint32_t)(carry_v + bv + iv - v);
+			tbase[b] = (uint32_t)(carry_t + bt + it - t);
+		}
+		carry_v += round_v;
+		carry_t += round_t;
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) { counts[0] = carry_v; counts[1] = carry_t; }
+}
+
+__global__ void __launch_bounds__(MESH_BLOCK)
+mesh_offsets_kernel(const uint8_t* __restrict__ vmask, const uint8_t* __restrict__ tcnt, uint32_t N, const uint32_t* __restrict__ vbase,
+                    const uint32_t* __restrict__ tbase, uint32_t* __restrict__ vert_off, uint32_t* __restrict__ tri_off) {
+	__shared__ uint32_t lds[4];
+	const uint32_t n = blockIdx.x * MESH_BLOCK + threadIdx.x;
+	const uint32_t v = n < N ? (uint32_t)__popc(vmask[n] & 0x7fu) : 0u, t = n < N ? (uint32_t)tcnt[n] : 0u;
+	const uint32_t ex = block_exclusive(v | (t << 16), lds);         // (a block sums to at most 1792 | 3072 << 16)
+	if (n < N) {
+		vert_off[n] = vbase[blockIdx.x] + (ex & 0xffffu);
+		tri_off[n] = tbase[blockIdx.x] + (ex >> 16);
+	}
+}
+
+struct EmitArgs {
+	const float* tsdf; const float* color;
+	const uint8_t* cls; const uint8_t* vmask; const uint32_t* vert_off; const uint32_t* tri_off;
+	float* verts; float* vcolor; int* faces;
+	uint32_t N, nV, nT;
+	int nx, ny, nz;
+	float ox, oy, oz, voxel;
+};
+
+__global__ void __launch_bounds__(MESH_BLOCK)
+mesh_emit_kernel(const EmitArgs a) {
+	const uint32_t n = blockIdx.x * MESH_BLOCK + threadIdx.x;
+	if (n >= a.N) return;
+	const uint32_t vm = a.vmask[n];
+	if (vm == 0) return;
+	int i, j, k;
+	node_ijk(n, a.nx, a.ny, i, j, k);
+	const size_t sx = 1, sy = (size_t)a.nx, sz = (size_t)a.nx * a.ny;
+	if (vm & 0x7fu) {
+		const float ta = a.tsdf[n];
+		const float ax = fmaf(a.voxel, (float)i, a.ox), ay = fmaf(a.voxel, (float)j, a.oy), az = fmaf(a.voxel, (float)k, a.oz);
+		uint32_t at = a.vert_off[n];
+		for (int e = 0; e < 7; e++) {
+			if (!((vm >> e) & 1u)) continue;
+			const int db = (e < 3) ? (1 << e) : (e == 3) ? 3 : (e == 4) ? 5 : (e == 5) ? 6 : 7;
+			const int dx = db & 1, dy = (db >> 1) & 1, dz = db >> 2;
+			const size_t m = (size_t)n + dx * sx + dy * sy + dz * sz;      // in the grid: the count kernel set the bit only there
+			const float tb = a.tsdf[m];
+			const float f = ta / (ta - tb);
+			const uint32_t vi = at++;
+			if (vi >= a.nV) continue;                                      // (never with the counts of this scratch: no row beyond nV)
+			const float bx = fmaf(a.voxel, (float)(i + dx), a.ox), by = fmaf(a.voxel, (float)(j + dy), a.oy), bz = fmaf(a.voxel, (float)(k + dz), a.oz);
+			float* o = a.verts + 3 * (size_t)vi;
+			o[0] = ax + (bx - ax) * f;
+			o[1] = ay + (by - ay) * f;
+			o[2] = az + (bz - az) * f;
+			if (a.vcolor) {
+				const size_t vol = sz * a.nz;
+#pragma unroll
+				for (int c = 0; c < 3; c++) {
+					const float ca = a.color[c * vol + n], cb = a.color[c * vol + m];
+					a.vcolor[3 * (size_t)vi + c] = ca + (cb - ca) * f;
+				}
+			}
+		}
+	}
+	if (vm & CELL_VALID) {
+		// the cell's corners (bit x + 2y + 4z): inside bits, and for the seven that start an edge their vertex masks and offsets
+		uint32_t corner = 0, cmask[8], coff[8];
+#pragma unroll
+		for (int c = 0; c < 8; c++) {
+			const size_t m = (size_t)n + (c & 1) * sx + ((c >> 1) & 1) * sy + (c >> 2) * sz;
+			corner |= (((uint32_t)a.cls[m] >> 1) & 1u) << c;
+			cmask[c] = c < 7 ? (uint32_t)a.vmask[m] : 0u;
+			coff[c] = c < 7 ? a.vert_off[m] : 0u;
+		}
+		uint32_t at = a.tri_off[n];
+		for (int t = 0; t < 6; t++) {
+			const uint32_t p = tet_corner_bits(t);
+			const uint32_t m = (corner & 1u) | (((corner >> ((p >> 4) & 7u)) & 1u) << 1) | (((corner >> ((p >> 8) & 7u)) & 1u) << 2) |
+			                   (((corner >> 7) & 1u) << 3);
+			uint32_t code = TET_CASES[m];
+			const uint32_t ntri = code & 3u;
+			code >>= 2;
+			const bool positive = (t == 0 || t == 3 || t == 4);
+			for (uint32_t r = 0; r < ntri; r++) {
+				int id[3];
+#pragma unroll
+				for (int q = 0; q < 3; q++, code >>= 3) {
+					const uint32_t ends = EDGE_ENDS(code & 7u);
+					const uint32_t lo = (p >> (4 * (ends & 3u))) & 7u, hi = (p >> (4 * (ends >> 2))) & 7u;      // corner bits of the edge's ends
+					const uint32_t dir = DIR_OF_BITS(hi ^ lo);
+					// the selects below keep cmask / coff in registers (a dynamic index would spill them to scratch memory)
+					uint32_t cm = 0, co = 0;
+#pragma unroll
+					for (int c = 0; c < 7; c++)
+						if (lo == (uint32_t)c) { cm = cmask[c]; co = coff[c]; }
+					id[q] = (int)(co + __popc(cm & ((1u << dir) - 1u)));
+				}
+				const uint32_t ti = at++;
+				if (ti >= a.nT) continue;                                  // (never with the counts of this scratch)
+				int* o = a.faces + 3 * (size_t)ti;
+				o[0] = id[0];
+				o[1] = positive ? id[1] : id[2];
+				o[2] = positive ? id[2] : id[1];
+			}
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+static inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
+static inline bool positive_finite(float v) { return std::isfinite(v) && v > 0.f; }
+
+// The volume's size limits.  Returns 0 and the node count, or GSR_E_INVALID with the message set.
+static int volume_check(const char* entry, int nx, int ny, int nz, uint64_t* N) {
+	if (nx < 2 || ny < 2 || nz < 2) {
+		set_error("%s: every dimension of the volume must be at least 2 (got %d x %d x %d)", entry, nx, ny, nz);
+		return GSR_E_INVALID;
+	}
+	const uint64_t limit = (uint64_t)1 << 31;
+	const uint64_t xy = (uint64_t)nx * (uint64_t)ny;               // < 2^62
+	if (xy >= limit || xy * (uint64_t)nz >= limit) {
+		set_error("%s: nx * ny * nz must be below 2^31 (got %d x %d x %d)", entry, nx, ny, nz);
+		return GSR_E_INVALID;
+	}
+	*N = xy * (uint64_t)nz;
+	return 0;
+}
+
+static int grid_check(const char* entry, float ox, float oy, float oz, float voxel) {
+	if (!positive_finite(voxel)) { set_error("%s: voxel must be positive and finite (got %g)", entry, (double)voxel); return GSR_E_INVALID; }
+	if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz)) { set_error("%s: the origin is not finite", entry); return GSR_E_INVALID; }
+	return 0;
+}
+
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" int gsr_tsdf_integrate(float* tsdf, float* weight, float* color, int nx, int ny, int nz, float ox, float oy, float oz, float voxel,
+                                  const float* depth, const float* rgb, const float* alpha, float alpha_min, int W, int H,
+                                  const float* viewmatrix, const float* projmatrix, float sdf_trunc, float depth_trunc, void* stream_) {
+	const char* entry = "gsr_tsdf_integrate";
+	hipStream_t stream = (hipStream_t)stream_;
+	if (!tsdf || !weight || !depth || !viewmatrix || !projmatrix) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
+	if ((color != nullptr) != (rgb != nullptr)) { set_error("%s: color and rgb must both be given or both be NULL", entry); return GSR_E_INVALID; }
+	for (const void* p : {(const void*)tsdf, (const void*)weight, (const void*)color, (const void*)depth, (const void*)rgb, (const void*)alpha,
+	                      (const void*)viewmatrix, (const void*)projmatrix})
+		if (misaligned(p, 4)) { set_error("%s: pointers must be 4-byte aligned (got %p)", entry, p); return GSR_E_INVALID; }
+	uint64_t N;
+	if (int rc = volume_check(entry, nx, ny, nz, &N)) return rc;
+	if (int rc = grid_check(entry, ox, oy, oz, voxel)) return rc;
+	if (W < 1 || H < 1 || (uint64_t)W * (uint64_t)H >= ((uint64_t)1 << 31)) {
+		set_error("%s: invalid image size %d x %d", entry, W, H);
+		return GSR_E_INVALID;
+	}
+	if (!positive_finite(sdf_trunc) || !positive_finite(depth_trunc)) {
+		set_error("%s: sdf_trunc and depth_trunc must be positive and finite (got %g, %g)", entry, (double)sdf_trunc, (double)depth_trunc);
+		return GSR_E_INVALID;
+	}
+	if (!std::isfinite(alpha_min)) { set_error("%s: alpha_min is not finite", entry); return GSR_E_INVALID; }
+	TsdfArgs a;
+	a.tsdf = tsdf; a.weight = weight; a.color = color; a.depth = depth; a.rgb = rgb; a.alpha = alpha; a.view = viewmatrix; a.proj = projmatrix;
+	a.nx = nx; a.ny = ny; a.nz = nz; a.W = W; a.H = H;
+	a.ox = ox; a.oy = oy; a.oz = oz; a.voxel = voxel; a.alpha_min = alpha_min; a.sdf_trunc = sdf_trunc; a.depth_trunc = depth_trunc;
+	a.bx = ((uint32_t)nx + 63u) / 64u;
+	a.bxy = a.bx * (((uint32_t)ny + TSDF_ROWS - 1u) / TSDF_ROWS);
+	// (for n >= 2 each of ceil(n / 64), ceil(n / 4) and ceil(n / 8) is at most n / 2: the product is at most nx ny nz / 8 < 2^28)
+	a.nblocks = a.bxy * (((uint32_t)nz + TSDF_KZ - 1u) / TSDF_KZ);
+	// at most 2^16 blocks are launched (a thousand waves per CU) and each strides over the blocks beyond: a volume of 2 x 2 x 2^29 nodes
+	// has 2^26 blocks of its own
+	const uint32_t grid = a.nblocks < TSDF_MAX_GRID ? a.nblocks : TSDF_MAX_GRID;
+	tsdf_integrate_kernel<<<grid, 64 * TSDF_ROWS, 0, stream>>>(a);
+	GSR_LAUNCH_CHECK(0, stream);
+	return 0;
+}
+
+extern "C" size_t gsr_mesh_scratch_bytes(int nx, int ny, int nz) {
+	if (nx < 2 || ny < 2 || nz < 2) return 0;
+	const uint64_t limit = (uint64_t)1 << 31, xy = (uint64_t)nx * (uint64_t)ny;
+	if (xy >= limit || xy * (uint64_t)nz >= limit) return 0;
+	return mesh_scratch(xy * (uint64_t)nz).bytes;
+}
+
+extern "C" int gsr_mesh_count(const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, void* scratch, size_t scratch_bytes,
+                              uint64_t* counts, void* stream_) {
+	const char* entry = "gsr_mesh_count";
+	hipStream_t stream = (hipStream_t)stream_;
+	if (!tsdf || !weight || !scratch || !counts) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
+	if (misaligned(tsdf, 4) || misaligned(weight, 4)) { set_error("%s: tsdf and weight must be 4-byte aligned", entry); return GSR_E_INVALID; }
+	if (misaligned(scratch, 16)) { set_error("%s: scratch must be 16-byte aligned (got %p)", entry, scratch); return GSR_E_INVALID; }
+	if (misaligned(counts, 8)) { set_error("%s: counts must be 8-byte aligned (got %p)", entry, (void*)counts); return GSR_E_INVALID; }
+	uint64_t N64;
+	if (int rc = volume_check(entry, nx, ny, nz, &N64)) return rc;
+	if (std::isnan(min_weight)) { set_error("%s: min_weight is NaN", entry); return GSR_E_INVALID; }
+	const MeshScratch s = mesh_scratch(N64);
+	if (scratch_bytes < s.bytes) {
+		set_error("%s: scratch of %zu bytes, gsr_mesh_scratch_bytes(%d, %d, %d) = %zu", entry, scratch_bytes, nx, ny, nz, s.bytes);
+		return GSR_E_INVALID;
+	}
+	char* base = (char*)scratch;
+	const uint32_t N = (uint32_t)N64;
+	uint8_t* cls = (uint8_t*)(base + s.cls);
+	uint8_t* vmask = (uint8_t*)(base + s.vmask);
+	uint8_t* tcnt = (uint8_t*)(base + s.tcnt);
+	uint32_t* part = (uint32_t*)(base + s.part);
+	uint32_t* vbase = (uint32_t*)(base + s.vbase);
+	uint32_t* tbase = (uint32_t*)(base + s.tbase);
+	mesh_classify_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(tsdf, weight, N, min_weight, cls);
+	GSR_LAUNCH_CHECK(0, stream);
+	mesh_count_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(cls, N, nx, ny, nz, vmask, tcnt, part);
+	GSR_LAUNCH_CHECK(0, stream);
+	mesh_spine_kernel<<<1, 1024, 0, stream>>>(part, s.nblocks, vbase, tbase, (unsigned long long*)counts);
+	GSR_LAUNCH_CHECK(0, stream);
+	mesh_offsets_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(vmask, tcnt, N, vbase, tbase, (uint32_t*)(base + s.vert_off), (uint32_t*)(base + s.tri_off));
+	GSR_LAUNCH_CHECK(0, stream);
+	return 0;
+}
+
+extern "C" int gsr_mesh_emit(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, float ox, float oy, float oz,
+                             float voxel, float min_weight, const void* scratch, float* verts, float* vcolor, int* faces, uint64_t nV, uint64_t nT,
+                             void* stream_) {
+	const char* entry = "gsr_mesh_emit";
+	hipStream_t stream = (hipStream_t)stream_;
+	(void)min_weight;             // the classification is the one gsr_mesh_count left in the scratch
+	if (!tsdf || !weight || !scratch) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
+	for (const void* p : {(const void*)tsdf, (const void*)weight, (const void*)color, (const void*)verts, (const void*)vcolor, (const void*)faces})
+		if (misaligned(p, 4)) { set_error("%s: pointers must be 4-byte aligned (got %p)", entry, p); return GSR_E_INVALID; }
+	if (misaligned(scratch, 16)) { set_error("%s: scratch must be 16-byte aligned (got %p)", entry, scratch); return GSR_E_INVALID; }
+	uint64_t N64;
+	if (int rc = volume_check(entry, nx, ny, nz, &N64)) return rc;
+	if (int rc = grid_check(entry, ox, oy, oz, voxel)) return rc;
+	const uint64_t limit = (uint64_t)1 << 31;
+	if (nV >= limit || nT >= limit || 3 * nT >= limit) {
+		set_error("%s: nV and 3 * nT must be below 2^31 (got %llu vertices, %llu triangles)", entry, (unsigned long long)nV, (unsigned long long)nT);
+		return GSR_E_INVALID;
+	}
+	if (nV == 0) return 0;
+	if (!verts || (nT > 0 && !faces)) { set_error("%s: invalid argument (NULL verts or faces)", entry); return GSR_E_INVALID; }
+	if ((color != nullptr) != (vcolor != nullptr)) { set_error("%s: color and vcolor must both be given or both be NULL", entry); return GSR_E_INVALID; }
+	const MeshScratch s = mesh_scratch(N64);
+	const char* base = (const char*)scratch;
+	EmitArgs a;
+	a.tsdf = tsdf; a.color = color;
+	a.cls = (const uint8_t*)(base + s.cls);
+	a.vmask = (const uint8_t*)(base + s.vmask);
+	a.vert_off = (const uint32_t*)(base + s.vert_off);
+	a.tri_off = (const uint32_t*)(base + s.tri_off);
+	a.verts = verts; a.vcolor = vcolor; a.faces = faces;
+	a.N = (uint32_t)N64; a.nV = (uint32_t)nV; a.nT = (uint32_t)nT;
+	a.nx = nx; a.ny = ny; a.nz = nz;
+	a.ox = ox; a.oy = oy; a.oz = oz; a.voxel = voxel;
+	mesh_emit_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(a);
+	GSR_LAUNCH_CHECK(0, stream);
+	return 0;
+}

@@ -1,0 +1,120 @@
+"""TSDF fusion of rendered surface depth and mesh extraction on the device (include/gsr_hip_mesh.h; csrc/gsr_mesh.hip).
+
+A surfel model exists to yield a surface: `render()` writes `surf_depth` per view, `TSDFVolume.integrate` fuses such maps into a dense
+voxel grid, `TSDFVolume.extract` pulls the iso-surface out as an indexed triangle mesh (marching tetrahedra), and `save_mesh_ply` writes
+it.  Everything stays on the device; the one read-back is the 16 bytes that hold the vertex and triangle counts.  The reference took
+this from open3d (ScalableTSDFVolume) on the host; utils/mesh_utils.py has its GaussianExtractor on top of this module.
+"""
+import collections
+
+import numpy as np
+import torch
+
+import _gsr
+from _gsr import check, f32c, lib, ptr, stream_ptr
+
+_gsr.require_entry(lib, "gsr_tsdf_integrate")
+
+Mesh = collections.namedtuple("Mesh", "vertices faces colors")     # float32 [nV, 3], int32 [nT, 3], float32 [nV, 3] or None: device tensors
+MAX_NODES = 2 ** 31 - 1
+
+
+class TSDFVolume:
+    """A dense volume of dims = (nx, ny, nz) nodes, node (i, j, k) at origin + voxel_size * (i, j, k): float32 planes tsdf [nz, ny, nx],
+    weight [nz, ny, nx] and, with color=True, color [3, nz, ny, nx] on `device`, all zero when fresh."""
+
+    def __init__(self, origin, voxel_size, dims, device, color=True):
+        self.origin = tuple(float(c) for c in origin)
+        self.voxel_size = float(voxel_size)
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.origin) != 3 or len(self.dims) != 3:
+            raise ValueError("TSDFVolume: origin and dims have three components")
+        nx, ny, nz = self.dims
+        if min(self.dims) < 2 or nx * ny * nz > MAX_NODES:
+            raise ValueError(f"TSDFVolume: every dimension must be at least 2 and nx * ny * nz below 2^31 (got {self.dims})")
+        if not (np.isfinite(self.voxel_size) and self.voxel_size > 0):
+            raise ValueError(f"TSDFVolume: voxel_size must be positive and finite (got {voxel_size})")
+        self.device = torch.device(device)
+        self.tsdf = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.color = torch.zeros((3, nz, ny, nx), dtype=torch.float32, device=self.device) if color else None
+
+    def reset(self):
+        for t in (self.tsdf, self.weight, self.color):
+            if t is not None:
+                t.zero_()
+
+    def integrate(self, depth, camera, rgb=None, alpha=None, alpha_min=0.5, sdf_trunc=None, depth_trunc=None):
+        """Fuses one view (gsr_tsdf_integrate): depth [H, W] or [1, H, W] (render()'s surf_depth), `camera` any object render() accepts
+        (world_view_transform, full_proj_transform, image_width, image_height), rgb [3, H, W] when the volume holds colour, alpha
+        [H, W] or [1, H, W] to leave out pixels below alpha_min.  sdf_trunc defaults to five voxels; depth_trunc has no default.  Runs
+        on the current stream; nothing is read back."""
+        if depth_trunc is None:
+            raise ValueError("TSDFVolume.integrate: depth_trunc is required")
+        sdf_trunc = 5.0 * self.voxel_size if sdf_trunc is None else float(sdf_trunc)
+        H, W = int(camera.image_height), int(camera.image_width)
+
+        def plane(t, name, channels):
+            t = f32c(t, name)
+            if tuple(t.shape) == (H, W) and channels == 1:
+                return t
+            if tuple(t.shape) != (channels, H, W):
+                raise ValueError(f"TSDFVolume.integrate: {name} must be [{channels}, {H}, {W}] (got {tuple(t.shape)})")
+            return t
+        depth = plane(depth, "depth", 1)
+        if (rgb is None) != (self.color is None):
+            raise ValueError("TSDFVolume.integrate: rgb is given exactly when the volume holds colour")
+        rgb = None if rgb is None else plane(rgb, "rgb", 3)
+        alpha = None if alpha is None else plane(alpha, "alpha", 1)
+        view, proj = f32c(camera.world_view_transform, "world_view_transform"), f32c(camera.full_proj_transform, "full_proj_transform")
+        for t, name in ((depth, "depth"), (rgb, "rgb"), (alpha, "alpha"), (view, "world_view_transform"), (proj, "full_proj_transform")):
+            if t is not None and t.device != self.tsdf.device:
+                raise ValueError(f"TSDFVolume.integrate: {name} is on {t.device}, the volume on {self.tsdf.device}")
+        nx, ny, nz = self.dims
+        with torch.cuda.device(self.device):
+            check(lib.gsr_tsdf_integrate(ptr(self.tsdf), ptr(self.weight), ptr(self.color), nx, ny, nz, *self.origin, self.voxel_size, ptr(depth),
+                                         ptr(rgb), ptr(alpha), float(alpha_min), W, H, ptr(view), ptr(proj), sdf_trunc, float(depth_trunc),
+                                         stream_ptr(self.device)), "gsr_tsdf_integrate")
+
+    def extract(self, min_weight=1.0):
+        """The iso-surface tsdf = 0 over the cells whose eight nodes have weight >= min_weight, as Mesh(vertices, faces, colors) on the
+        device; an empty surface gives empty tensors.  Waits once, for the two counts."""
+        nx, ny, nz = self.dims
+        dev = self.device
+        scratch = torch.empty(int(lib.gsr_mesh_scratch_bytes(nx, ny, nz)), dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.gsr_mesh_count(ptr(self.tsdf), ptr(self.weight), nx, ny, nz, float(min_weight), ptr(scratch), scratch.numel(), ptr(counts),
+                                     stream_ptr(dev)), "gsr_mesh_count")
+            nV, nT = (int(c) for c in counts.tolist())
+            verts = torch.empty((nV, 3), dtype=torch.float32, device=dev)
+            faces = torch.empty((nT, 3), dtype=torch.int32, device=dev)
+            colors = None if self.color is None else torch.empty((nV, 3), dtype=torch.float32, device=dev)
+            check(lib.gsr_mesh_emit(ptr(self.tsdf), ptr(self.weight), ptr(self.color), nx, ny, nz, *self.origin, self.voxel_size, float(min_weight),
+                                    ptr(scratch), ptr(verts), ptr(colors), ptr(faces), nV, nT, stream_ptr(dev)), "gsr_mesh_emit")
+        return Mesh(verts, faces, colors)
+
+
+def save_mesh_ply(path, mesh):
+    """Binary little-endian PLY: x y z float per vertex, with colours also red green blue uchar, quantised as
+    utils.image_utils.present_bytes quantises (trunc(clamp(c, 0, 1) * 255)); faces as `list uchar int vertex_indices`."""
+    verts = mesh.vertices.detach().to("cpu", torch.float32).numpy()
+    faces = mesh.faces.detach().to("cpu", torch.int32).numpy()
+    fields = [("xyz", "<f4", 3)]
+    props = ["property float x", "property float y", "property float z"]
+    if mesh.colors is not None:
+        fields.append(("rgb", "u1", 3))
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    v = np.zeros(len(verts), dtype=np.dtype(fields))
+    v["xyz"] = verts
+    if mesh.colors is not None:
+        v["rgb"] = (mesh.colors.detach().nan_to_num(0.0).clamp(0.0, 1.0) * 255.0).to(torch.uint8).cpu().numpy()
+    f = np.zeros(len(faces), dtype=np.dtype([("n", "u1"), ("idx", "<i4", 3)]))
+    f["n"] = 3
+    f["idx"] = faces
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(verts)}"] + props + [
+        f"element face {len(faces)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(f.tobytes())

@@ -1,0 +1,89 @@
+"""utils/mesh_utils.py of the reference: GaussianExtractor, with the bounded TSDF mesh extraction its docstring promises.
+
+The reference kept the constructor, clean() and reconstruction() and dropped the extraction together with its open3d and trimesh
+imports; here the extraction is gsr_mesh.TSDFVolume (csrc/gsr_mesh.hip): the rendered maps stay on the device, the fusion and the
+iso-surface run there, and the mesh comes back as device tensors (gsr_mesh.save_mesh_ply writes it).  export_image is not provided: it
+needs the reference's utils/render_utils.
+"""
+import math
+from functools import partial
+
+import torch
+
+import gsr_mesh
+
+
+class GaussianExtractor:
+    """GaussianExtractor(gaussians, render, pipe, bg_color=None) of the reference: renders a model from a stack of cameras and turns
+    the rendered surface depth into a mesh.
+
+        extractor = GaussianExtractor(gaussians, render, pipe)
+        extractor.reconstruction(cameras)
+        mesh = extractor.extract_mesh_bounded(voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3)
+
+    `render` is gaussian_renderer.render (or a function with its signature); the background defaults to black and lives on the
+    current CUDA device, as in the reference."""
+
+    def __init__(self, gaussians, render, pipe, bg_color=None):
+        self.gaussians = gaussians
+        background = torch.tensor([0, 0, 0] if bg_color is None else bg_color, dtype=torch.float32, device="cuda")
+        self.render = partial(render, pipe=pipe, bg_color=background)
+        self.clean()
+
+    def clean(self):
+        """Drops everything the last reconstruction() kept."""
+        self.viewpoint_stack = []
+        self.rgbmaps, self.depthmaps, self.alphamaps, self.normals, self.depth_normals = [], [], [], [], []
+
+    @torch.no_grad()
+    def reconstruction(self, viewpoint_stack):
+        """Renders every camera of `viewpoint_stack` and keeps, per view and ON THE DEVICE: `render` (rgbmaps), `surf_depth` (depthmaps),
+        `rend_alpha` (alphamaps) and `rend_normal` normalised over its channels (normals).  (The reference moves the colour to the host
+        and keeps nothing else but the normals; its extraction, which would have read the rest, is gone.)"""
+        self.clean()
+        self.viewpoint_stack = viewpoint_stack
+        for cam in viewpoint_stack:
+            pkg = self.render(cam, self.gaussians)
+            self.rgbmaps.append(pkg["render"])
+            self.depthmaps.append(pkg["surf_depth"])
+            self.alphamaps.append(pkg["rend_alpha"])
+            self.normals.append(torch.nn.functional.normalize(pkg["rend_normal"], dim=0))
+
+    def camera_bounds(self):
+        """(centre, radius) of the sphere about the mean of the camera centres that holds them all."""
+        if not self.viewpoint_stack:
+            raise ValueError("GaussianExtractor: reconstruction() has seen no cameras")
+        centres = torch.stack([c.camera_center.detach().reshape(3).double().cpu() for c in self.viewpoint_stack])
+        centre = centres.mean(dim=0)
+        return centre, float((centres - centre).norm(dim=1).max())
+
+    @torch.no_grad()
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True, bounds=None):
+        """The bounded TSDF extraction upstream 2DGS calls by this name (the `mask_backgrond` spelling is upstream's): every kept view
+        is fused into one dense volume of `voxel_size` nodes over `bounds` = ((xmin, ymin, zmin), (xmax, ymax, zmax)), truncated at
+        `sdf_trunc` and ignoring depths beyond `depth_trunc`; with mask_backgrond, pixels whose rendered alpha is below 0.5 are left
+        out.  bounds=None: the box around the sphere about the mean camera centre that holds every camera centre.  Returns
+        gsr_mesh.Mesh(vertices, faces, colors) on the device.  A box that needs 2^31 nodes or more: ValueError."""
+        if not self.depthmaps:
+            raise ValueError("GaussianExtractor.extract_mesh_bounded: call reconstruction() first")
+        if bounds is None:
+            centre, radius = self.camera_bounds()
+            lo, hi = [float(c) - radius for c in centre], [float(c) + radius for c in centre]
+        else:
+            lo, hi = [float(c) for c in bounds[0]], [float(c) for c in bounds[1]]
+        voxel_size = float(voxel_size)
+        if not voxel_size > 0:
+            raise ValueError(f"extract_mesh_bounded: voxel_size must be positive (got {voxel_size})")
+        dims = [max(2, int(math.ceil((h - l) / voxel_size)) + 1) for l, h in zip(lo, hi)]
+        nodes = dims[0] * dims[1] * dims[2]
+        if nodes > gsr_mesh.MAX_NODES:
+            # the edge count per axis scales with 1 / voxel_size: the smallest voxel whose node count fits, with a little room for the ceil
+            fit = voxel_size * (nodes / gsr_mesh.MAX_NODES) ** (1.0 / 3.0) * 1.01
+            raise ValueError(f"extract_mesh_bounded: a volume of {dims[0]} x {dims[1]} x {dims[2]} = {nodes} nodes is beyond the 2^31 - 1 of a "
+                             f"dense volume; voxel_size >= {fit:.6g} fits these bounds (or pass smaller bounds)")
+        device = self.depthmaps[0].device
+        volume = gsr_mesh.TSDFVolume(lo, voxel_size, dims, device, color=True)
+        for cam, depth, rgb, alpha in zip(self.viewpoint_stack, self.depthmaps, self.rgbmaps, self.alphamaps):
+            volume.integrate(depth, cam, rgb=rgb, alpha=alpha if mask_backgrond else None, alpha_min=0.5, sdf_trunc=sdf_trunc,
+                             depth_trunc=depth_trunc)
+        return volume.extract()

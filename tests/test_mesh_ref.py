@@ -1,0 +1,152 @@
+"""The float64 restatement of the mesh extraction (tests/mesh_ref.py) pinned by known answers, on a machine without a GPU: the topology of
+the marching-tetrahedra surface of analytic grids, the PLY writer's round trip, and the condition under which tests/test_gpu_mesh.py may
+leave nodes out of its comparison (the unstable share of the integrate fixture)."""
+import numpy as np
+import pytest
+
+import mesh_ref as M
+
+
+@pytest.fixture(scope="module")
+def sphere():
+    return M.extract(*M.sphere_grid(), M.GRID_ORIGIN, M.GRID_VOXEL)
+
+
+def test_case_table_follows_the_rule():
+    """Every case has the triangles its inside count asks for, over the edges that join an inside to an outside corner; tetrahedra 0, 3
+    and 4 are the positively oriented ones."""
+    for mask, tris in M.TRIANGLES.items():
+        inside = [v for v in range(4) if mask >> v & 1]
+        assert len(tris) == {0: 0, 1: 1, 2: 2, 3: 1, 4: 0}[len(inside)]
+        cut = {(lo, hi) for lo in range(4) for hi in range(lo + 1, 4) if (lo in inside) != (hi in inside)}
+        assert {e for t in tris for e in t} == (cut if tris else set())
+    assert [M.tet_positive(t) for t in range(6)] == [True, False, False, True, True, False]
+    # the six tetrahedra tile the cell: their volumes add up to it
+    vol = sum(abs(np.linalg.det(np.diff(np.array(M.tet_corners(t), float), axis=0))) / 6 for t in range(6))
+    assert vol == pytest.approx(1.0)
+
+
+def test_sphere_is_a_closed_oriented_surface_of_genus_0(sphere):
+    V, C, F = sphere
+    t = M.topology(F, len(V))
+    assert t["boundary"] == 0 and t["nonmanifold"] == 0            # every undirected edge lies in exactly two faces
+    assert t["repeated_directed"] == 0                              # every directed edge appears once
+    assert t["euler"] == 2
+    assert t["unreferenced"] == 0
+    assert (len(V), len(F)) == (754, 1504)
+    vol = M.signed_volume(V - V.mean(0), F)
+    assert vol > 0
+    assert vol == pytest.approx(4 / 3 * np.pi * (3.7 * M.GRID_VOXEL) ** 3, rel=0.05)
+    # orientation: every face normal points away from the centre
+    centre = np.array(M.GRID_ORIGIN, np.float32).astype(float) + float(np.float32(M.GRID_VOXEL)) * np.array(M.CENTRE)
+    a, b, c = (V[F[:, k]] for k in range(3))
+    n = np.cross(b - a, c - a)
+    assert (np.einsum("ij,ij->i", n, (a + b + c) / 3 - centre) > 0).all()
+    # vertices lie on the sphere to within the linear interpolation's error: along a lattice edge of length L <= sqrt(3) the distance to
+    # the centre is convex with a second derivative of at most 1 / (R - L), so its chord misses it by at most L^2 / (8 (R - L)) = 0.19
+    r = np.linalg.norm(V - centre, axis=1) / M.GRID_VOXEL
+    assert np.abs(r - 3.7).max() < 3 / (8 * (3.7 - np.sqrt(3)))
+    assert C.shape == V.shape and C.min() >= 0 and C.max() <= 1
+
+
+def test_torus_has_genus_1():
+    V, _, F = M.extract(*M.torus_grid(), M.GRID_ORIGIN, M.GRID_VOXEL)
+    t = M.topology(F, len(V))
+    assert (t["boundary"], t["nonmanifold"], t["repeated_directed"], t["unreferenced"]) == (0, 0, 0, 0)
+    assert t["euler"] == 0
+    assert M.signed_volume(V - V.mean(0), F) > 0
+
+
+def test_an_unobserved_node_column_opens_the_surface(sphere):
+    V, _, F = M.extract(*M.sphere_grid(cut_x=9), M.GRID_ORIGIN, M.GRID_VOXEL)
+    t = M.topology(F, len(V))
+    assert t["boundary"] == 92 and t["nonmanifold"] == 0 and t["repeated_directed"] == 0
+    assert t["unreferenced"] == 0                                   # no orphan vertices beside the hole
+    assert 0 < len(F) < len(sphere[2])
+    # nothing of the surface lies in the two cell layers that touch the unobserved column
+    x = (V[:, 0] - float(np.float32(M.GRID_ORIGIN[0]))) / float(np.float32(M.GRID_VOXEL))
+    assert not ((x > 8 + 1e-9) & (x < 10 - 1e-9)).any()
+
+
+def test_zero_tsdf_nodes_are_outside_and_the_surface_stays_closed():
+    """A node with tsdf == 0 is outside; the zero-area triangles at it are kept, so the surface stays closed."""
+    tsdf, weight, color = M.sphere_grid(radius=3.0)
+    i = np.arange(17)[None, None, :] - 8.0
+    j = np.arange(13)[None, :, None] - 6.0
+    k = np.arange(11)[:, None, None] - 5.0
+    tsdf = (np.sqrt(i * i + j * j + k * k) - 3.0).astype(np.float32)       # centred on a node: six nodes have tsdf == 0 exactly
+    assert (tsdf == 0).sum() >= 6
+    V, _, F = M.extract(tsdf, weight, None, M.GRID_ORIGIN, M.GRID_VOXEL)
+    t = M.topology(F, len(V))
+    assert (t["boundary"], t["nonmanifold"], t["unreferenced"], t["euler"]) == (0, 0, 0, 2)
+    a, b, c = (V[F[:, k]] for k in range(3))
+    assert (np.linalg.norm(np.cross(b - a, c - a), axis=1) == 0).any()
+
+
+def test_all_positive_and_all_invalid_grids_are_empty():
+    tsdf, weight, color = M.sphere_grid()
+    for t, w in ((np.abs(tsdf) + 1, weight), (tsdf, np.zeros_like(weight))):
+        V, C, F = M.extract(t, w, color, M.GRID_ORIGIN, M.GRID_VOXEL)
+        assert V.shape == (0, 3) and C.shape == (0, 3) and F.shape == (0, 3)
+
+
+def test_integrate_fixture_stays_inside_the_unstable_cap():
+    """tests/test_gpu_mesh.py leaves the nodes out at which float32 may decide a skip rule differently; the cap on their share, 1 % of the
+    nodes, is a condition on the fixture, met by the restatement alone.  The fixture also has to exercise every skip rule."""
+    steps = M.integrate_reference()
+    nodes = steps[0][0].size
+    for tsdf, weight, color, written, unstable in steps:
+        assert unstable.sum() <= 0.01 * nodes, unstable.sum() / nodes
+        assert written.sum() > 50
+    tsdf, weight, color, _, _ = steps[-1]
+    assert set(np.unique(weight)) == {0.0, 1.0, 2.0, 3.0}
+    assert (tsdf < 0).any() and (tsdf == 1).any() and ((tsdf > 0) & (tsdf < 1)).any()
+    assert ((weight > 0) == (np.abs(color).sum(0) > 0)).all()
+    assert (weight == 0).mean() > 0.5                     # most of a volume is outside any one camera
+
+
+def test_integrate_known_answer_on_axis():
+    """One view down the z axis of a wall at depth 1: a node at depth z gets min(1, (1 - z) / trunc), nodes more than trunc behind the
+    wall and nodes outside the image are not written."""
+    import cameras
+    cam = cameras.hwk_camera(8, 6, 8.0, 8.0, 4.0, 3.0)
+    vol = M.Volume((5, 4, 9), (-0.2, -0.15, 0.25), 0.125, color=False)
+    depth = np.ones((6, 8), np.float32)
+    written, _ = M.integrate(vol, depth, None, None, 0.5, cam["viewmatrix"], cam["projmatrix"], 0.25, 5.0)
+    z = 0.25 + 0.125 * np.arange(9)
+    expect = np.minimum(1.0, (1.0 - z) / 0.25)
+    seen = written.any(axis=(1, 2))
+    assert list(seen) == list(z <= 1.25)
+    for k in np.nonzero(seen)[0]:
+        assert vol.tsdf[k][written[k]] == pytest.approx(expect[k], abs=1e-12)
+    assert not written[:, 0, 0].all() and (vol.weight[written] == 1).all() and (vol.weight[~written] == 0).all()
+
+
+def test_ply_round_trip(hip_lib_built, tmp_path, sphere):
+    import torch
+    import gsr_mesh
+    V, C, F = sphere
+    mesh = gsr_mesh.Mesh(torch.from_numpy(V.astype(np.float32)), torch.from_numpy(F), torch.from_numpy(C.astype(np.float32) * 1.2 - 0.1))
+    path = tmp_path / "sphere.ply"
+    gsr_mesh.save_mesh_ply(str(path), mesh)
+    v, c, f = M.read_ply(str(path))
+    assert (v == V.astype(np.float32)).all() and (f == F).all()
+    assert (c == np.trunc(np.clip(C.astype(np.float32) * np.float32(1.2) - np.float32(0.1), 0, 1) * np.float32(255)).astype(np.uint8)).all()
+    gsr_mesh.save_mesh_ply(str(path), gsr_mesh.Mesh(mesh.vertices, mesh.faces, None))
+    v, c, f = M.read_ply(str(path))
+    assert c is None and (v == V.astype(np.float32)).all() and (f == F).all()
+    empty = gsr_mesh.Mesh(torch.zeros((0, 3)), torch.zeros((0, 3), dtype=torch.int32), torch.zeros((0, 3)))
+    gsr_mesh.save_mesh_ply(str(path), empty)
+    v, c, f = M.read_ply(str(path))
+    assert v.shape == (0, 3) and c.shape == (0, 3) and f.shape == (0, 3)
+
+
+def test_extractor_refuses_a_box_beyond_the_dense_limit(hip_lib_built):
+    from utils.mesh_utils import GaussianExtractor
+    ex = GaussianExtractor.__new__(GaussianExtractor)
+    ex.clean()
+    ex.depthmaps = [None]
+    with pytest.raises(ValueError, match=r"2501 x 2501 x 2501 = 15643757501 nodes.*voxel_size >= 0\.00[78]"):
+        ex.extract_mesh_bounded(voxel_size=0.004, bounds=((-5, -5, -5), (5, 5, 5)))
+    with pytest.raises(ValueError, match="reconstruction"):
+        GaussianExtractor.camera_bounds(ex)
