@@ -179,6 +179,11 @@ ABI = [
         ("gsr_mesh_scratch_bytes", c_size_t, [I, I, I]),
         ("gsr_mesh_count", I, [P, P, I, I, I, F, P, c_size_t, P, P]),
         ("gsr_mesh_emit", I, [P, P, P, I, I, I, F, F, F, F, F, P, P, P, P, U64, U64, P])]),
+    # connected-component clean-up of an indexed mesh: gsr_mesh.clean_mesh, utils.mesh_utils.post_process_mesh
+    ("gsr_hip_meshclean.h", "csrc/gsr_meshclean.hip", True, [
+        ("gsr_mesh_clean_count", I, [P, U64, U64, U64, U64, P, P, P, c_size_t, P, P]),
+        ("gsr_mesh_clean_scratch_bytes", c_size_t, [U64, U64]),
+        ("gsr_mesh_clean_emit", I, [P, P, P, U64, U64, P, P, P, P, U64, U64, P])]),
 ]
 
 ENTRIES_BY_HEADER = {}          # {header file name: [entry names]}, what tests/test_cabi.py holds each header to

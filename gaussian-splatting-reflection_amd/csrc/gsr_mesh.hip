@@ -19,6 +19,7 @@
 #include <cmath>
 #include <initializer_list>
 #include "gsr_internal.hpp"
+#include "gsr_scan.hpp"
 #include "../../include/gsr_hip_mesh.h"
 
 namespace gsr {
@@ -92,7 +93,7 @@ tsdf_integrate_kernel(const TsdfArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ the iso-surface
-#define MESH_BLOCK 256
+#define MESH_BLOCK SCAN_BLOCK      // the block of the two-level scan (gsr_scan.hpp: block_sum, block_exclusive, scan_spine_kernel)
 #define NODE_VALID 1u
 #define NODE_INSIDE 2u
 #define CELL_VALID 0x80u          // bit 7 of a node's vertex mask: the cell whose low corner it is is valid
@@ -152,34 +153,6 @@ mesh_classify_kernel(const float* __restrict__ tsdf, const float* __restrict__ w
 	const uint32_t n = blockIdx.x * MESH_BLOCK + threadIdx.x;
 	if (n >= N) return;
 	cls[n] = (uint8_t)((weight[n] >= min_weight ? NODE_VALID : 0u) | (tsdf[n] < 0.f ? NODE_INSIDE : 0u));
-}
-
-// Sum over the block of a value below 2^16 per thread in each half of `v`; valid in every thread.
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {
-#pragma unroll
-	for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s);
-	if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-	__syncthreads();
-	v = lds[0] + lds[1] + lds[2] + lds[3];
-	__syncthreads();
-	return v;
-}
-
-// Exclusive scan over the block (MESH_BLOCK threads) of `v`.
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* lds) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = v;
-#pragma unroll
-	for (int s = 1; s < 64; s <<= 1) {
-		const uint32_t up = __shfl_up(inc, s);
-		if (lane >= s) inc += up;
-	}
-	if (lane == 63) lds[wave] = inc;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wave; w++) base += lds[w];
-	__syncthreads();
-	return base + inc - v;
 }
 
 __global__ void __launch_bounds__(MESH_BLOCK)
@@ -252,42 +225,6 @@ mesh_count_kernel(const uint8_t* __restrict__ cls, uint32_t N, int nx, int ny, i
 	}
 	const uint32_t sum = block_sum(__popc(vm & 0x7fu) | (nt << 16), lds);
 	if (threadIdx.x == 0) part[blockIdx.x] = sum;
-}
-
-// One block: exclusive scan of the block sums, 1024 per round, with 64-bit carries; the totals go to counts[0..1].
-__global__ void __launch_bounds__(1024)
-mesh_spine_kernel(const uint32_t* __restrict__ part, uint32_t nblocks, uint32_t* __restrict__ vbase, uint32_t* __restrict__ tbase,
-                  unsigned long long* __restrict__ counts) {
-	__shared__ uint32_t wv[16], wt[16];
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	unsigned long long carry_v = 0, carry_t = 0;
-	for (uint32_t at = 0; at < nblocks; at += 1024) {
-		const uint32_t b = at + threadIdx.x;
-		const uint32_t p = b < nblocks ? part[b] : 0u;
-		const uint32_t v = p & 0xffffu, t = p >> 16;
-		uint32_t iv = v, it = t;                                    // (a round sums to at most 1024 * 3072)
-#pragma unroll
-		for (int s = 1; s < 64; s <<= 1) {
-			const uint32_t uv = __shfl_up(iv, s), ut = __shfl_up(it, s);
-			if (lane >= s) { iv += uv; it += ut; }
-		}
-		if (lane == 63) { wv[wave] = iv; wt[wave] = it; }
-		__syncthreads();
-		uint32_t bv = 0, bt = 0, round_v = 0, round_t = 0;
-		for (int w = 0; w < 16; w++) {
-			if (w < wave) { bv += wv[w]; bt += wt[w]; }
-			round_v += wv[w];
-			round_t += wt[w];
-		}
-		if (b < nblocks) {
-			vbase[b] = (uint32_t)(carry_v + bv + iv - v);
-			tbase[b] = (uint32_t)(carry_t + bt + it - t);
-		}
-		carry_v += round_v;
-		carry_t += round_t;
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) { counts[0] = carry_v; counts[1] = carry_t; }
 }
 
 __global__ void __launch_bounds__(MESH_BLOCK)
@@ -496,7 +433,7 @@ extern "C" int gsr_mesh_count(const float* tsdf, const float* weight, int nx, in
 	GSR_LAUNCH_CHECK(0, stream);
 	mesh_count_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(cls, N, nx, ny, nz, vmask, tcnt, part);
 	GSR_LAUNCH_CHECK(0, stream);
-	mesh_spine_kernel<<<1, 1024, 0, stream>>>(part, s.nblocks, vbase, tbase, (unsigned long long*)counts);
+	scan_spine_kernel<<<1, 1024, 0, stream>>>(part, s.nblocks, vbase, tbase, (unsigned long long*)counts);
 	GSR_LAUNCH_CHECK(0, stream);
 	mesh_offsets_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(vmask, tcnt, N, vbase, tbase, (uint32_t*)(base + s.vert_off), (uint32_t*)(base + s.tri_off));
 	GSR_LAUNCH_CHECK(0, stream);

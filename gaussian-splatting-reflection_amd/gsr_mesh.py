@@ -1,9 +1,14 @@
-"""TSDF fusion of rendered surface depth and mesh extraction on the device (include/gsr_hip_mesh.h; csrc/gsr_mesh.hip).
+"""TSDF fusion of rendered surface depth, mesh extraction and mesh clean-up on the device (include/gsr_hip_mesh.h, csrc/gsr_mesh.hip;
+include/gsr_hip_meshclean.h, csrc/gsr_meshclean.hip).
 
 A surfel model exists to yield a surface: `render()` writes `surf_depth` per view, `TSDFVolume.integrate` fuses such maps into a dense
 voxel grid, `TSDFVolume.extract` pulls the iso-surface out as an indexed triangle mesh (marching tetrahedra), and `save_mesh_ply` writes
 it.  Everything stays on the device; the one read-back is the 16 bytes that hold the vertex and triangle counts.  The reference took
 this from open3d (ScalableTSDFVolume) on the host; utils/mesh_utils.py has its GaussianExtractor on top of this module.
+
+`clean_mesh` is the step upstream runs on that mesh before writing it: the connected triangle clusters are labelled, the largest kept,
+the small ones and the vertices nobody references any more dropped; `cluster_connected_triangles` gives the labels alone.  Its one
+read-back is the 48 bytes of its six counts.
 """
 import collections
 
@@ -17,6 +22,7 @@ _gsr.require_entry(lib, "gsr_tsdf_integrate")
 
 Mesh = collections.namedtuple("Mesh", "vertices faces colors")     # float32 [nV, 3], int32 [nT, 3], float32 [nV, 3] or None: device tensors
 MAX_NODES = 2 ** 31 - 1
+CleanInfo = collections.namedtuple("CleanInfo", "vertices faces components kept_components threshold ignored_faces")     # the six counts of gsr_mesh_clean_count
 
 
 class TSDFVolume:
@@ -93,6 +99,70 @@ class TSDFVolume:
             check(lib.gsr_mesh_emit(ptr(self.tsdf), ptr(self.weight), ptr(self.color), nx, ny, nz, *self.origin, self.voxel_size, float(min_weight),
                                     ptr(scratch), ptr(verts), ptr(colors), ptr(faces), nV, nT, stream_ptr(dev)), "gsr_mesh_emit")
         return Mesh(verts, faces, colors)
+
+
+def _clean_count(mesh, cluster_to_keep, min_triangles, want_labels):
+    """gsr_mesh_clean_count on the current stream of the mesh's device: (faces as passed, scratch, counts [6] int64 on the device, tri_label,
+    tri_size).  The entries are looked up here, not at import: everything else in this module works with a library built before them."""
+    _gsr.require_entry(lib, "gsr_mesh_clean_count")
+    cluster_to_keep, min_triangles = int(cluster_to_keep), int(min_triangles)
+    verts, faces = mesh.vertices, mesh.faces
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"clean_mesh: vertices must be [nV, 3] and faces int32 [nT, 3] (got {tuple(verts.shape)}, {faces.dtype} {tuple(faces.shape)})")
+    if faces.device != verts.device or (mesh.colors is not None and (mesh.colors.device != verts.device or mesh.colors.shape != verts.shape)):
+        raise ValueError("clean_mesh: vertices, faces and colors must lie on one device, colors shaped as vertices")
+    dev = verts.device
+    nV, nT = int(verts.shape[0]), int(faces.shape[0])
+    if nV >= 2 ** 31 or 3 * nT >= 2 ** 31:
+        raise ValueError(f"clean_mesh: nV and 3 * nT must be below 2^31 (got {nV} vertices, {nT} faces)")
+    faces = faces.contiguous()
+    scratch = torch.empty(int(lib.gsr_mesh_clean_scratch_bytes(nV, nT)), dtype=torch.uint8, device=dev)
+    counts = torch.empty(6, dtype=torch.int64, device=dev)
+    tri_label = torch.empty(nT, dtype=torch.int32, device=dev) if want_labels else None
+    tri_size = torch.empty(nT, dtype=torch.int32, device=dev) if want_labels else None
+    with torch.cuda.device(dev):
+        check(lib.gsr_mesh_clean_count(ptr(faces), nV, nT, min(cluster_to_keep, 2 ** 64 - 1), min(min_triangles, 2 ** 64 - 1), ptr(tri_label),
+                                       ptr(tri_size), ptr(scratch), scratch.numel(), ptr(counts), stream_ptr(dev)), "gsr_mesh_clean_count")
+    return faces, scratch, counts, tri_label, tri_size
+
+
+def cluster_connected_triangles(mesh):
+    """(tri_label, tri_size), int32 [nT] on the mesh's device: per face the label of its connected component (the smallest vertex index
+    in it) and the number of faces in that component; a face with an index outside [0, nV) or a repeated index gets -1 and 0.  Two faces
+    are connected when they share a VERTEX (open3d's function of this name asks for a shared edge; include/gsr_hip_meshclean.h).  Runs on
+    the current stream; nothing is read back."""
+    _, _, _, tri_label, tri_size = _clean_count(mesh, 1, 0, True)
+    return tri_label, tri_size
+
+
+def clean_mesh(mesh, cluster_to_keep=1000, min_triangles=50, return_info=False):
+    """The mesh without its floaters (include/gsr_hip_meshclean.h): the faces of the `cluster_to_keep` largest connected components (ties
+    with the last of them included, fewer components: all of them) that have at least `min_triangles` faces, in their order, and the
+    vertices (and colours) those faces name, in their order, bit for bit; the faces index the new rows.  A new Mesh on the same device;
+    `mesh` is not changed.  return_info=True: (Mesh, CleanInfo), the six counts.  Runs on the current stream and waits once, for the
+    48 bytes of the counts; an empty mesh gives an empty Mesh without a launch."""
+    _gsr.require_entry(lib, "gsr_mesh_clean_count")
+    dev = mesh.vertices.device
+    nV, nT = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    has_color = mesh.colors is not None
+    if int(cluster_to_keep) < 1 or int(min_triangles) < 0:
+        raise ValueError(f"clean_mesh: cluster_to_keep must be at least 1 and min_triangles at least 0 (got {cluster_to_keep}, {min_triangles})")
+    if nV == 0 or nT == 0:
+        empty = Mesh(torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev),
+                     torch.empty((0, 3), dtype=torch.float32, device=dev) if has_color else None)
+        return (empty, CleanInfo(0, 0, 0, 0, 0, nT)) if return_info else empty
+    verts = f32c(mesh.vertices, "vertices")
+    colors = f32c(mesh.colors, "colors") if has_color else None
+    faces, scratch, counts, _, _ = _clean_count(mesh, cluster_to_keep, min_triangles, False)
+    info = CleanInfo(*(int(c) & (2 ** 64 - 1) for c in counts.tolist()))
+    with torch.cuda.device(dev):
+        verts_out = torch.empty((info.vertices, 3), dtype=torch.float32, device=dev)
+        faces_out = torch.empty((info.faces, 3), dtype=torch.int32, device=dev)
+        colors_out = torch.empty((info.vertices, 3), dtype=torch.float32, device=dev) if has_color else None
+        check(lib.gsr_mesh_clean_emit(ptr(verts), ptr(colors), ptr(faces), nV, nT, ptr(scratch), ptr(verts_out), ptr(colors_out), ptr(faces_out),
+                                      info.vertices, info.faces, stream_ptr(dev)), "gsr_mesh_clean_emit")
+    out = Mesh(verts_out, faces_out, colors_out)
+    return (out, info) if return_info else out
 
 
 def save_mesh_ply(path, mesh):

@@ -2,8 +2,9 @@
 
 The reference kept the constructor, clean() and reconstruction() and dropped the extraction together with its open3d and trimesh
 imports; here the extraction is gsr_mesh.TSDFVolume (csrc/gsr_mesh.hip): the rendered maps stay on the device, the fusion and the
-iso-surface run there, and the mesh comes back as device tensors (gsr_mesh.save_mesh_ply writes it).  export_image is not provided: it
-needs the reference's utils/render_utils.
+iso-surface run there, and the mesh comes back as device tensors (gsr_mesh.save_mesh_ply writes it).  post_process_mesh is upstream
+2DGS's clean-up of that mesh, on gsr_mesh.clean_mesh (csrc/gsr_meshclean.hip).  export_image is not provided: it needs the reference's
+utils/render_utils.
 """
 import math
 from functools import partial
@@ -11,6 +12,17 @@ from functools import partial
 import torch
 
 import gsr_mesh
+
+
+def post_process_mesh(mesh, cluster_to_keep=1000):
+    """post_process_mesh of upstream 2DGS: keeps the `cluster_to_keep` largest connected triangle clusters of `mesh`
+    (gsr_mesh.Mesh, device tensors) and none below 50 triangles, drops the vertices no kept face names, and prints upstream's two lines.
+    The mesh stays on the device (gsr_mesh.clean_mesh; clusters are joined over shared vertices, and a `cluster_to_keep` beyond the number
+    of clusters keeps them all where upstream raises)."""
+    out = gsr_mesh.clean_mesh(mesh, cluster_to_keep=cluster_to_keep, min_triangles=50)
+    print("num vertices raw {}".format(len(mesh.vertices)))
+    print("num vertices post {}".format(len(out.vertices)))
+    return out
 
 
 class GaussianExtractor:
