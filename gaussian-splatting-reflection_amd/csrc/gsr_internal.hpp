@@ -242,27 +242,7 @@ __device__ __forceinline__ void get_rect(float px, float py, int max_radius, int
 	y1 = (uint32_t)min(gy, max(0, f2i((py + r + 15.0f) / 16.0f)));
 }
 
-// ---- wave64 sums.  Classic GCN reduction: row_shr 1,2,4,8 inside each row of 16 lanes, then
-// row_bcast:15 / row_bcast:31 across the four rows; the total lands in lane 63.  hipcc does not fuse
-// __builtin_amdgcn_update_dpp into the add (it emits v_mov_b32_dpp + v_pk_add_f32 + a zeroing move), so the
-// multi-value forms below issue the fused `v_add_f32_dpp` directly: one VALU instruction per value per
-// step.  Values are interleaved inside one asm statement so that consecutive DPP reads of a register are
-// always >= 3 instructions after its last write (gfx9 VALU-write -> DPP-read hazard: 2 wait states; the
-// compiler's hazard recogniser does not look inside asm, hence the leading s_nop).
-#define GSR_DPP1(CTRL, i) "v_add_f32_dpp %" #i ", %" #i ", %" #i " " CTRL "\n\t"
-#define GSR_DPP4(CTRL) GSR_DPP1(CTRL, 0) GSR_DPP1(CTRL, 1) GSR_DPP1(CTRL, 2) GSR_DPP1(CTRL, 3)
-#define GSR_SHR1 "row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-#define GSR_SHR2 "row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-#define GSR_SHR4 "row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-#define GSR_SHR8 "row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-#define GSR_BC15 "row_bcast:15 row_mask:0xa bank_mask:0xf"
-#define GSR_BC31 "row_bcast:31 row_mask:0xc bank_mask:0xf"
-// Sum 4 independent values across the wave; totals valid in lane 63 only.  Must be called with all 64 lanes active.
-__device__ __forceinline__ void wave_sum4(float* v) {
-	asm volatile("s_nop 1\n\t" GSR_DPP4(GSR_SHR1) GSR_DPP4(GSR_SHR2) GSR_DPP4(GSR_SHR4) GSR_DPP4(GSR_SHR8) GSR_DPP4(GSR_BC15) GSR_DPP4(GSR_BC31)
-	             : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
-}
-
+// (The wave and block sums of the streaming kernels are in gsr_reduce.hpp.)
 // ---- in-row packed reduction (exchange-type DPP only).  An earlier version folded 64 -> 16 lanes with
 // v_permlane32_swap / v_permlane16_swap (fewer instructions); measured on MI355X those swaps cost ~4x a DPP add, so
 // that was the SLOWER way to pack on this part (ablation numbers in DESIGN.md).

@@ -16,6 +16,7 @@
 //     dL/dv[c] in one pass over the channels.  Global traffic per pixel, C = 3: forward 2 C + 2 reads and 3 C writes of 4 B (the
 //     composed path adds ~10 plane passes of 3 x 4 B each way around the same kernels); backward 5 C + 2 reads, C + 1 writes.
 #include "gsr_internal.hpp"
+#include "gsr_reduce.hpp"
 #include "gsr_ssim.hpp"
 
 namespace gsr {
@@ -39,7 +40,6 @@ loss_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2, 
                 float* __restrict__ dm_dsigma12) {
 	__shared__ float ta[SSIM_HALO][SSIM_HALO + 1], tb[SSIM_HALO][SSIM_HALO + 1];
 	__shared__ float hs[5][SSIM_HALO][SSIM_T + 1];
-	__shared__ float red[2][4];
 	const size_t plane = (size_t)blockIdx.z * H * W;
 	const int x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
 	{
@@ -82,15 +82,12 @@ loss_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2, 
 			}
 		}
 	}
-	// block sums -> one partial pair per block; pair_reduce_kernel adds them up in a fixed order
-	float r4[4] = {l1, ssim_sum, 0.f, 0.f};
-	wave_sum4(r4);
-	const int wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63) == 63) { red[0][wave] = r4[0]; red[1][wave] = r4[1]; }
-	__syncthreads();
-	if (threadIdx.x < 2) {
+	// one partial pair per block; sums_reduce_kernel adds them up in a fixed order
+	float sums[2] = {l1, ssim_sum};
+	if (block_sums(sums)) {
 		const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-		partials[2 * blk + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+		partials[2 * blk] = sums[0];
+		partials[2 * blk + 1] = sums[1];
 	}
 }
 
@@ -216,7 +213,7 @@ static void launch_loss_forward(const float* img1, const float* img2, int C, int
 	StageTimer st_(GSR_STAGE_LOSS_FWD, stream);
 	auto* const kernel = cp.alpha || cp.gt_mask ? loss_fwd_kernel<true> : loss_fwd_kernel<false>;
 	kernel<<<grid, 256, 0, stream>>>(img1, img2, H, W, ssim_window(), C1, C2, cp, scratch, ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
-	pair_reduce_kernel<<<1, 256, 0, stream>>>(scratch, (size_t)grid.x * grid.y * grid.z, sums);
+	sums_reduce_kernel<2, 2><<<1, 256, 0, stream>>>(scratch, (size_t)grid.x * grid.y * grid.z, sums);
 }
 template <bool PER_PIXEL>
 static void launch_plane_backward(const float* img1, const float* img2, int planes, int H, int W, const float* upstream, const float* dm_dmu1,

@@ -5,11 +5,11 @@
 //     are presented while they are staged into LDS, nothing is kept for a backward, and a view leaves three sums:
 //     sum (v - g)^2, sum |v - g| and sum ssim_map.  Global traffic: the reads alone, 8 B per pixel-channel (+ alpha / mask).
 //   * normal_mae_kernel: eval_mae.py / utils/mae_utils.py:3-29, the angle between predicted and ground-truth normals.
-// Block partials are added in a fixed order in double and written to one row of a caller-owned table: a test set needs one
-// read-back at its end, and every number is bitwise reproducible.
+// Block partials are added in a fixed order in double (block_sums and sums_reduce_kernel of gsr_reduce.hpp) and written to one row
+// of a caller-owned table: a test set needs one read-back at its end, and every number is bitwise reproducible.
 #include "gsr_internal.hpp"
+#include "gsr_reduce.hpp"
 #include "gsr_ssim.hpp"
-#include <algorithm>
 
 namespace gsr {
 
@@ -37,7 +37,6 @@ image_metrics_kernel(const float* __restrict__ img, const float* __restrict__ gt
                      float4* __restrict__ partials, uint8_t* __restrict__ img_u8, uint8_t* __restrict__ gt_u8) {
 	__shared__ float ta[SSIM_HALO][SSIM_HALO + 1], tb[SSIM_HALO][SSIM_HALO + 1];
 	__shared__ float hs[5][SSIM_HALO][SSIM_T + 1];
-	__shared__ float red[3][4];
 	const size_t plane = (size_t)blockIdx.z * H * W;
 	const int x0 = blockIdx.x * SSIM_T, y0 = blockIdx.y * SSIM_T;
 	{
@@ -81,37 +80,11 @@ image_metrics_kernel(const float* __restrict__ img, const float* __restrict__ gt
 			if (gt_u8) gt_u8[o] = (uint8_t)(unsigned int)(g * 255.0f + 0.5f);
 		}
 	}
-	float r4[4] = {sse, sad, ssim_sum, 0.f};
-	wave_sum4(r4);
-	const int wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63) == 63) { red[0][wave] = r4[0]; red[1][wave] = r4[1]; red[2][wave] = r4[2]; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
+	float sums[3] = {sse, sad, ssim_sum};
+	if (block_sums(sums)) {
 		const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-		partials[blk] = make_float4((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]),
-		                            (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]), 0.f);
+		partials[blk] = make_float4(sums[0], sums[1], sums[2], 0.f);
 	}
-}
-
-// second stage of both kernels: one workgroup adds the blocks' float4 partials in double, in a fixed order, into the row
-__global__ void __launch_bounds__(256) metrics_reduce_kernel(const float4* __restrict__ partials, size_t nblocks, double last, double* __restrict__ row) {
-	__shared__ double red[3][256];
-	double a = 0.0, b = 0.0, c = 0.0;
-	for (size_t i = threadIdx.x; i < nblocks; i += 256) {
-		const float4 p = partials[i];
-		a += (double)p.x; b += (double)p.y; c += (double)p.z;
-	}
-	red[0][threadIdx.x] = a; red[1][threadIdx.x] = b; red[2][threadIdx.x] = c;
-	__syncthreads();
-	for (int s = 128; s > 0; s >>= 1) {
-		if ((int)threadIdx.x < s) {
-#pragma unroll
-			for (int k = 0; k < 3; k++) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-		}
-		__syncthreads();
-	}
-	if (threadIdx.x < 3) row[threadIdx.x] = red[threadIdx.x][0];
-	if (threadIdx.x == 3) row[3] = last;
 }
 
 // utils/mae_utils.py:10-27 per pixel, in float32 as torch evaluates it.  A pixel is invalid where a norm is <= eps or the angle
@@ -119,7 +92,6 @@ __global__ void __launch_bounds__(256) metrics_reduce_kernel(const float4* __res
 __global__ void __launch_bounds__(256)
 normal_mae_kernel(const float* __restrict__ pred, const float* __restrict__ gt, size_t HW, float pred_div, float gt_div, float eps,
                   float4* __restrict__ partials, float* __restrict__ map) {
-	__shared__ float red[3][4];
 	float sum = 0.f, valid = 0.f, invalid = 0.f;
 	for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (size_t)gridDim.x * 256) {
 		float a[3], b[3];
@@ -139,21 +111,13 @@ normal_mae_kernel(const float* __restrict__ pred, const float* __restrict__ gt, 
 		if (map) map[p] = bad ? __int_as_float(0x7fc00000) : ang;
 	}
 	// (the counts stay exact in float32: a block of the 1024 sees at most 2^31 / 1024 = 2^21 pixels)
-	float r4[4] = {sum, valid, invalid, 0.f};
-	wave_sum4(r4);
-	const int wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63) == 63) { red[0][wave] = r4[0]; red[1][wave] = r4[1]; red[2][wave] = r4[2]; }
-	__syncthreads();
-	if (threadIdx.x == 0)
-		partials[blockIdx.x] = make_float4((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]),
-		                                   (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]), 0.f);
+	float sums[3] = {sum, valid, invalid};
+	if (block_sums(sums)) partials[blockIdx.x] = make_float4(sums[0], sums[1], sums[2], 0.f);
 }
 
 }  // namespace gsr
 
 using namespace gsr;
-
-#define NORMAL_MAE_BLOCKS 1024
 
 static size_t image_metrics_blocks(int C, int H, int W) { return (size_t)C * ssim_tiles(H) * ssim_tiles(W); }
 
@@ -185,14 +149,14 @@ extern "C" int gsr_image_metrics(const float* img, const float* gt, int C, int H
 	const Presentation pr = {alpha, gt_mask, background, (flags & GSR_PRESENT_CLAMP) != 0, (flags & GSR_PRESENT_QUANT8) != 0};
 	dim3 grid(ssim_tiles(W), ssim_tiles(H), C);
 	image_metrics_kernel<<<grid, 256, 0, stream>>>(img, gt, H, W, ssim_window(), (float)(0.01 * 0.01), (float)(0.03 * 0.03), pr, (float4*)scratch, img_u8, gt_u8);
-	metrics_reduce_kernel<<<1, 256, 0, stream>>>((const float4*)scratch, blocks, (double)C * H * W, row);
+	sums_reduce_kernel<3, 4, true><<<1, 256, 0, stream>>>(scratch, blocks, row, (double)C * H * W);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
 
 extern "C" size_t gsr_normal_mae_scratch_floats(int H, int W) {
 	if (H <= 0 || W <= 0) return 0;
-	return 4 * std::min<size_t>(NORMAL_MAE_BLOCKS, ((size_t)H * W + 255) / 256);
+	return 4 * (size_t)stream_blocks((size_t)H * W);
 }
 
 extern "C" int gsr_normal_mae(const float* pred, const float* gt, int H, int W, float pred_divisor, float gt_divisor, float eps, double* row,
@@ -203,14 +167,14 @@ extern "C" int gsr_normal_mae(const float* pred, const float* gt, int H, int W, 
 	if (!(pred_divisor > 0.f) || !(gt_divisor > 0.f) || !(eps >= 0.f)) { set_error("gsr_normal_mae: divisors must be positive and eps non-negative"); return GSR_E_INVALID; }
 	if (reinterpret_cast<uintptr_t>(row) & 7u) { set_error("gsr_normal_mae: the table row must be 8-byte aligned; got %p", (const void*)row); return GSR_E_INVALID; }
 	const size_t HW = (size_t)H * W;
-	const size_t blocks = std::min<size_t>(NORMAL_MAE_BLOCKS, (HW + 255) / 256);
+	const size_t blocks = stream_blocks(HW);
 	if (!scratch || scratch_floats < 4 * blocks) {
 		set_error("gsr_normal_mae: scratch of %zu floats given, gsr_normal_mae_scratch_floats(H,W) = %zu needed", scratch ? scratch_floats : (size_t)0, 4 * blocks);
 		return GSR_E_INVALID;
 	}
 	GSR_REQUIRE_ALIGNED16_IN("gsr_normal_mae", scratch, "scratch");
 	normal_mae_kernel<<<(unsigned)blocks, 256, 0, stream>>>(pred, gt, HW, pred_divisor, gt_divisor, eps, (float4*)scratch, error_map);
-	metrics_reduce_kernel<<<1, 256, 0, stream>>>((const float4*)scratch, blocks, (double)HW, row);
+	sums_reduce_kernel<3, 4, true><<<1, 256, 0, stream>>>(scratch, blocks, row, (double)HW);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }

@@ -3,13 +3,12 @@
 //   outside = sum((xyz - centre)^2, -1) > radius^2;   loss += 0.4 * refl[outside].mean()
 // six torch kernels, a nonzero and a host wait there; here one streaming pass each way (include/gsr_hip_scope.h).
 //   * forward: 12 B of xyz (+ 4 B of refl) read and 2 mask bytes written per point, one point per lane per trip of a grid-stride loop;
-//     each block leaves (sum of refl, count) over its outside points, pair_reduce_kernel adds the pairs in double in a fixed order.
+//     each block leaves (sum of refl, count) over its outside points, sums_reduce_kernel adds the pairs in double in a fixed order.
 //   * backward: 1 mask byte read and 4 B of gradient written per point (accumulate: read and written on outside rows only).
 #include <cmath>
 #include "gsr_internal.hpp"
 #include "../../include/gsr_hip_scope.h"
-#include "gsr_ssim.hpp"  // pair_reduce_kernel
-#include <algorithm>
+#include "gsr_reduce.hpp"
 
 namespace gsr {
 
@@ -40,14 +39,10 @@ env_scope_fwd_kernel(const float* __restrict__ means3D, const float* __restrict_
 		}
 	}
 	if (LOSS) {
-		__shared__ float red[2][4];
-		float r4[4] = {acc, cnt, 0.f, 0.f};
-		wave_sum4(r4);
-		if ((threadIdx.x & 63) == 63) { red[0][threadIdx.x >> 6] = r4[0]; red[1][threadIdx.x >> 6] = r4[1]; }
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			partials[2 * blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-			partials[2 * blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+		float sums[2] = {acc, cnt};
+		if (block_sums(sums)) {
+			partials[2 * blockIdx.x] = sums[0];
+			partials[2 * blockIdx.x + 1] = sums[1];
 		}
 	}
 }
@@ -75,8 +70,7 @@ env_scope_bwd_kernel(const uint8_t* __restrict__ outside, const float* __restric
 
 using namespace gsr;
 
-#define ENV_SCOPE_BLOCKS 1024      // as gsr_normal_loss_forward: enough blocks to fill the device, few enough for a one-block second stage
-extern "C" size_t gsr_env_scope_scratch_floats(void) { return 2 * ENV_SCOPE_BLOCKS; }
+extern "C" size_t gsr_env_scope_scratch_floats(void) { return 2 * STREAM_BLOCKS_MAX; }
 
 extern "C" int gsr_env_scope_forward(int P, const float* means3D, const float* refl, float cx, float cy, float cz, float radius2, uint8_t* inside,
                                      uint8_t* outside, float* sums, float* scratch, void* stream_) {
@@ -88,7 +82,7 @@ extern "C" int gsr_env_scope_forward(int P, const float* means3D, const float* r
 		// nothing is read and no mask is written; a caller that asks for the sums gets (0, 0): the second stage over no block at all
 		if (sums) {
 			StageTimer st_(GSR_STAGE_LOSS_FWD, stream);
-			pair_reduce_kernel<<<1, 256, 0, stream>>>(scratch, (size_t)0, sums);
+			sums_reduce_kernel<2, 2><<<1, 256, 0, stream>>>(scratch, (size_t)0, sums);
 			GSR_LAUNCH_CHECK(0, stream);
 		}
 		return 0;
@@ -100,12 +94,12 @@ extern "C" int gsr_env_scope_forward(int P, const float* means3D, const float* r
 	}
 	if (!refl && !inside && !outside) { set_error("gsr_env_scope_forward: nothing to do (no refl and both masks NULL)"); return GSR_E_INVALID; }
 	const size_t n = (size_t)P;
-	const unsigned blocks = (unsigned)std::min<size_t>(ENV_SCOPE_BLOCKS, (n + 255) / 256);
+	const unsigned blocks = stream_blocks(n);
 	{
 		StageTimer st_(GSR_STAGE_LOSS_FWD, stream);
 		if (refl) {
 			env_scope_fwd_kernel<true><<<blocks, 256, 0, stream>>>(means3D, refl, n, cx, cy, cz, radius2, inside, outside, scratch);
-			pair_reduce_kernel<<<1, 256, 0, stream>>>(scratch, (size_t)blocks, sums);      // sums[0] = sum of refl outside, sums[1] = their number
+			sums_reduce_kernel<2, 2><<<1, 256, 0, stream>>>(scratch, (size_t)blocks, sums);      // sums[0] = sum of refl outside, sums[1] = their number
 		} else {
 			env_scope_fwd_kernel<false><<<blocks, 256, 0, stream>>>(means3D, nullptr, n, cx, cy, cz, radius2, inside, outside, nullptr);
 		}

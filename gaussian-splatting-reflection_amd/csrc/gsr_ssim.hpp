@@ -1,7 +1,7 @@
 // The 11x11 Gaussian-window SSIM, written once for the loss kernels (gsr_loss.hip) and the evaluation metrics (gsr_metrics.hip):
 // the window, the 32x32 output tile with its 42x42 zero-padded halo in LDS, the halo loader, the two register-blocked forward
-// passes with the evaluation of one output row, the two adjoint passes of the backwards, and the fixed-order reduction of the
-// blocks' partial pairs.  Every device function is inlined into the kernel that calls it.
+// passes with the evaluation of one output row, and the two adjoint passes of the backwards.  Every device function is inlined
+// into the kernel that calls it.  (The sums of the blocks' partials are gsr_reduce.hpp's.)
 #pragma once
 #include <cmath>
 #include "gsr_internal.hpp"
@@ -162,21 +162,6 @@ __device__ __forceinline__ float adjoint_value(const float (&col)[3][SSIM_B + 10
 	return c0 + 2.f * x * c1 + y * c2;
 }
 
-// Second stage of every sum of block partial pairs (the losses' sum |x - y| and sum ssim, the normal loss's sum): one workgroup,
-// double accumulation, fixed order -> the sums are bitwise reproducible.  (Thousands of blocks adding into ONE address serialise
-// at the memory side: measured 0.32 ms for the 1080p loss with atomics, see DESIGN.md.)
-static __global__ void __launch_bounds__(256) pair_reduce_kernel(const float* __restrict__ partials, size_t nblocks, float* __restrict__ sums) {
-	__shared__ double red[2][256];
-	double a = 0.0, b = 0.0;
-	for (size_t i = threadIdx.x; i < nblocks; i += 256) { a += (double)partials[2 * i]; b += (double)partials[2 * i + 1]; }
-	red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-	__syncthreads();
-	for (int s = 128; s > 0; s >>= 1) {
-		if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) { sums[0] = (float)red[0][0]; sums[1] = (float)red[1][0]; }
-}
 #endif
 
 }  // namespace gsr

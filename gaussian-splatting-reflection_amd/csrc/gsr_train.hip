@@ -7,8 +7,7 @@
 #include <cstring>
 #include "gsr_internal.hpp"
 #include "../../include/gsr_hip_train.h"   // the raw-parameter step's entries (added under ABI 102, declared apart from gsr_hip.h)
-#include "gsr_ssim.hpp"  // pair_reduce_kernel, the second stage of the normal loss's sum
-#include <algorithm>
+#include "gsr_reduce.hpp"
 
 namespace gsr {
 
@@ -251,19 +250,15 @@ extern "C" int gsr_activate(const float* raw, float* act, uint64_t n, uint64_t n
 // the upstream gradient of that SUM as a one-float device tensor (no host synchronisation) and writes both gradients fully.
 __global__ void __launch_bounds__(256)
 normal_loss_fwd_kernel(const float* __restrict__ rend, const float* __restrict__ surf, const float* __restrict__ mask, size_t HW, float* __restrict__ partials) {
-	__shared__ float red[4];
 	float acc = 0.f;
 	for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (size_t)gridDim.x * 256) {
 		float e = 1.0f - (rend[p] * surf[p] + rend[HW + p] * surf[HW + p] + rend[2 * HW + p] * surf[2 * HW + p]);
 		if (mask) e *= mask[p];
 		acc += e;
 	}
-	float r4[4] = {acc, 0.f, 0.f, 0.f};
-	wave_sum4(r4);
-	if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = r4[0];
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		partials[2 * blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+	float sums[1] = {acc};
+	if (block_sums(sums)) {
+		partials[2 * blockIdx.x] = sums[0];
 		partials[2 * blockIdx.x + 1] = 0.f;
 	}
 }
@@ -280,16 +275,15 @@ normal_loss_bwd_kernel(const float* __restrict__ rend, const float* __restrict__
 		g_surf[c * HW + p] = g * r;
 	}
 }
-#define NORMAL_LOSS_BLOCKS 1024
-extern "C" size_t gsr_normal_loss_scratch_floats(void) { return 2 * NORMAL_LOSS_BLOCKS; }
+extern "C" size_t gsr_normal_loss_scratch_floats(void) { return 2 * STREAM_BLOCKS_MAX; }
 extern "C" int gsr_normal_loss_forward(const float* rend_normal, const float* surf_normal, const float* mask, int H, int W, float* sum2,
                                        float* scratch, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
 	if (H <= 0 || W <= 0 || !rend_normal || !surf_normal || !sum2 || !scratch) { set_error("gsr_normal_loss_forward: invalid argument"); return GSR_E_INVALID; }
 	const size_t HW = (size_t)H * W;
-	const unsigned blocks = (unsigned)std::min<size_t>(NORMAL_LOSS_BLOCKS, (HW + 255) / 256);
+	const unsigned blocks = stream_blocks(HW);
 	normal_loss_fwd_kernel<<<blocks, 256, 0, stream>>>(rend_normal, surf_normal, mask, HW, scratch);
-	pair_reduce_kernel<<<1, 256, 0, stream>>>(scratch, (size_t)blocks, sum2);         // sum2[0] = sum(normal_error), sum2[1] = 0
+	sums_reduce_kernel<2, 2><<<1, 256, 0, stream>>>(scratch, (size_t)blocks, sum2);         // sum2[0] = sum(normal_error), sum2[1] = 0
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
