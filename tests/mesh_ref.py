@@ -3,12 +3,17 @@ iso-surface on the Kuhn split.  Inputs are the float32-rounded arrays the device
 `inside`, `valid`, the orders of vertices and triangles, the split of a quad) follows the header, the arithmetic is float64.
 
   integrate(vol, view)          -> (written [nz,ny,nx] bool, unstable [nz,ny,nx] bool); vol's planes are updated in place
-  extract(tsdf, weight, ...)    -> (verts [nV,3] f64, colors [nV,3] f64 | None, faces [nT,3] int32)
+  extract(tsdf, weight, ...)    -> (verts [nV,3] f64, colors [nV,3] f64 | None, faces [nT,3] int32[, Ends: the end nodes of every vertex's edge])
+  extract_bounds(ends, voxel)   the bound on |device - extract()| per vertex and component that follows from the kernel's arithmetic
   TRIANGLES                     the 16-case table of a positively oriented tetrahedron, generated from the header's rule
   topology(faces, nV)           edge statistics of an indexed mesh, for the known-answer tests
   sphere_grid / torus_grid      the analytic grids of tests/test_mesh_ref.py and tests/test_gpu_mesh.py
+  random_lattice / config_lattice / stacked + stacked_mesh / long_column      grids without structure: random signs, exact zeros, scattered
+                                invalid nodes; the 256 corner configurations once each; lattices stacked along z, their mesh composed
+  coverage / held_classes       what a grid reaches: (tetrahedron, mask) pairs, corner configurations, edges held by none, some or all cells
   integrate_fixture()           the volume, cameras and depth maps of the integrate tests
 """
+import collections
 import itertools
 import math
 
@@ -16,6 +21,7 @@ import numpy as np
 
 DIRECTIONS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))       # lattice edge directions 0..6, (x, y, z)
 TETS = ((0, 1), (0, 2), (1, 0), (1, 2), (2, 0), (2, 1))                                         # (a, b) of tetrahedra 0..5
+Ends = collections.namedtuple("Ends", "a b ca cb")
 
 
 def _even(perm):
@@ -68,8 +74,9 @@ def tet_positive(t):
 
 
 # ------------------------------------------------------------------------------------------------- extraction
-def extract(tsdf, weight, color, origin, voxel, min_weight=1.0):
-    """tsdf, weight [nz, ny, nx] float32, color [3, nz, ny, nx] float32 or None."""
+def extract(tsdf, weight, color, origin, voxel, min_weight=1.0, ends=False):
+    """tsdf, weight [nz, ny, nx] float32, color [3, nz, ny, nx] float32 or None.  ends=True: a fourth result, Ends(a, b, ca, cb), the
+    positions [nV, 3] and colours [nV, 3] | None of the two end nodes of each vertex's lattice edge (what extract_bounds() is made of)."""
     tsdf, weight = np.asarray(tsdf, np.float32), np.asarray(weight, np.float32)
     nz, ny, nx = tsdf.shape
     with np.errstate(invalid="ignore"):
@@ -82,7 +89,7 @@ def extract(tsdf, weight, color, origin, voxel, min_weight=1.0):
     o = np.asarray(origin, np.float32).astype(np.float64)
     h = float(np.float32(voxel))
     index = {}                     # (node linear index, direction) -> vertex index
-    verts, cols = [], []
+    verts, cols, end_a, end_b, end_ca, end_cb = [], [], [], [], [], []
     for k, j, i in itertools.product(range(nz), range(ny), range(nx)):
         for e, (dx, dy, dz) in enumerate(DIRECTIONS):
             i2, j2, k2 = i + dx, j + dy, k + dz
@@ -104,9 +111,13 @@ def extract(tsdf, weight, color, origin, voxel, min_weight=1.0):
             b = o + h * np.array([i2, j2, k2], np.float64)
             index[((k * ny + j) * nx + i, e)] = len(verts)
             verts.append(a + (b - a) * f)
+            end_a.append(a)
+            end_b.append(b)
             if color is not None:
                 ca, cb = color[:, k, j, i].astype(np.float64), color[:, k2, j2, i2].astype(np.float64)
                 cols.append(ca + (cb - ca) * f)
+                end_ca.append(ca)
+                end_cb.append(cb)
     faces = []
     for k, j, i in itertools.product(range(nz - 1), range(ny - 1), range(nx - 1)):
         if not cell_ok[k, j, i]:
@@ -125,7 +136,11 @@ def extract(tsdf, weight, color, origin, voxel, min_weight=1.0):
                 faces.append(ids)
     V = np.array(verts, np.float64).reshape(-1, 3)
     C = None if color is None else np.array(cols, np.float64).reshape(-1, 3)
-    return V, C, np.array(faces, np.int32).reshape(-1, 3)
+    F = np.array(faces, np.int32).reshape(-1, 3)
+    if not ends:
+        return V, C, F
+    rows = lambda x: np.array(x, np.float64).reshape(-1, 3)
+    return V, C, F, Ends(rows(end_a), rows(end_b), None if color is None else rows(end_ca), None if color is None else rows(end_cb))
 
 
 def extract_vertices(tsdf, weight, origin, voxel, min_weight=1.0):
@@ -215,6 +230,181 @@ def torus_grid(R=4.3, r=1.6):
     q = np.sqrt((i - CENTRE[0]) ** 2 + (j - CENTRE[1]) ** 2) - R
     tsdf = (np.sqrt(q ** 2 + (k - CENTRE[2]) ** 2) - r).astype(np.float32)
     return tsdf, np.ones_like(tsdf), _colors()
+
+
+# ------------------------------------------------------------------------------------------------- random lattices
+U32 = 2.0 ** -24                       # float32's unit roundoff
+
+
+def extract_bounds(ends, voxel):
+    """(position bound [nV, 3], colour bound [nV, 3] | None) on |device - extract()| per component, from the kernel's arithmetic and not
+    from its results: a = fma(voxel, i, o) and b likewise (one rounding each), f = ta / (ta - tb) (two; ta and tb differ in sign, so
+    nothing cancels), a + (b - a) * f (a difference of at most one voxel, a product and a sum, or one fma): four roundings of a quantity
+    no larger than max(|a|, |b|) and four of one no larger than the voxel; for colours four of one no larger than max(|ca|, |cb|)."""
+    h = float(np.float32(voxel))
+    pos = U32 * (4.0 * np.maximum(np.abs(ends.a), np.abs(ends.b)) + 4.0 * h)
+    col = None if ends.ca is None else U32 * 4.0 * np.maximum(np.abs(ends.ca), np.abs(ends.cb))
+    return pos, col
+
+
+def random_lattice(dims, seed, p_invalid=0.0, specials=True):
+    """(tsdf, weight, color) float32 of a grid with no structure at all.  tsdf: magnitudes uniform in [0.05, 1] with a random sign; with
+    `specials` about 3 % of the nodes hold 0.0 and about 2 % hold -0.0 (both outside).  weight: a fraction p_invalid of the nodes draws
+    from {0, 0.5, NaN} (invalid at min_weight = 1), the rest from {1, 2} (1 == min_weight is valid)."""
+    nx, ny, nz = dims
+    shape = (nz, ny, nx)
+    rs = np.random.RandomState(seed)
+    tsdf = (rs.uniform(0.05, 1.0, shape) * rs.choice([-1.0, 1.0], shape)).astype(np.float32)
+    if specials:
+        u = rs.rand(*shape)
+        tsdf[u < 0.03] = np.float32(0.0)
+        tsdf[(u >= 0.03) & (u < 0.05)] = np.float32(-0.0)
+    invalid = rs.rand(*shape) < p_invalid
+    weight = np.where(invalid, rs.choice([0.0, 0.5, np.nan], shape), rs.choice([1.0, 2.0], shape)).astype(np.float32)
+    return tsdf, weight, rs.rand(3, *shape).astype(np.float32)
+
+
+def with_outside_border(grid):
+    """The grid with every border node outside (|tsdf|; a zero stays a zero): its surface cannot leave the grid, so it is closed."""
+    tsdf, weight, color = grid
+    tsdf = tsdf.copy()
+    inner = np.zeros(tsdf.shape, bool)
+    inner[1:-1, 1:-1, 1:-1] = True
+    tsdf[~inner] = np.abs(tsdf[~inner])
+    return tsdf, weight, color
+
+
+CONFIG_DIMS = (2, 2, 768)
+
+
+def config_lattice():
+    """(tsdf, weight, color) of a 2 x 2 x 768 grid that holds each of the 256 inside/outside configurations of a cell's corners once: cell
+    c sits in slices 3c and 3c + 1, its corner (x, y, z) is inside iff bit x + 2y + 4z of c is set, the eight magnitudes of a cell differ;
+    slice 3c + 2 is invalid (weight 0, NaN or 0.5 by turns) and holds tsdf values that must not be read."""
+    nx, ny, nz = CONFIG_DIMS
+    tsdf, weight = np.zeros((nz, ny, nx), np.float32), np.ones((nz, ny, nx), np.float32)
+    for c in range(256):
+        for z, y, x in itertools.product((0, 1), repeat=3):
+            bit = x + 2 * y + 4 * z
+            mag = (1 + (bit * 5 + c) % 8 + 8 * ((bit + c // 8) % 3)) / 32.0            # distinct within a cell: (bit * 5 + c) % 8 is a bijection
+            tsdf[3 * c + z, y, x] = -mag if (c >> bit) & 1 else mag
+        tsdf[3 * c + 2] = -tsdf[3 * c + 1] * 3
+        weight[3 * c + 2] = (0.0, np.nan, 0.5)[c % 3]
+    return tsdf, weight, np.random.RandomState(6).rand(3, nz, ny, nx).astype(np.float32)
+
+
+def stacked(blocks, order, gap):
+    """(tsdf, weight, color, k0): the lattices blocks[order[0]], blocks[order[1]], ... (each (tsdf, weight, color) with one nx and ny) one
+    behind the other along z with `gap` >= 1 invalid slices (weight 0; tsdf -1, never read) between two of them; k0[n] is the first slice
+    of the n-th.  No cell and no lattice edge with two valid ends crosses a gap, so the mesh is stacked_mesh()'s composition."""
+    assert gap >= 1
+    none = lambda like: (np.full((gap,) + like.shape[1:], -1, np.float32), np.zeros((gap,) + like.shape[1:], np.float32))
+    ts, ws, cs, k0, at = [], [], [], [], 0
+    for n, b in enumerate(order):
+        tsdf, weight, color = blocks[b]
+        if n:
+            gt, gw = none(tsdf)
+            ts.append(gt)
+            ws.append(gw)
+            cs.append(np.full((3,) + gt.shape, 0.5, np.float32))
+            at += gap
+        ts.append(tsdf)
+        ws.append(weight)
+        cs.append(color)
+        k0.append(at)
+        at += tsdf.shape[0]
+    return np.concatenate(ts), np.concatenate(ws), np.concatenate(cs, 1), np.array(k0)
+
+
+def stacked_mesh(blocks, order, k0, origin, voxel, min_weight=1.0):
+    """(verts, colors, faces, ends) of stacked()'s grid, composed from one extract() per distinct block: faces concatenated with each
+    block's vertex offset added, vertices (and the ends of their edges) shifted by float64(float32(voxel)) * k0 along z."""
+    own = {b: extract(*blocks[b], origin, voxel, min_weight, ends=True) for b in sorted(set(order))}
+    h = float(np.float32(voxel))
+    V, C, F, A, B, CA, CB, nV = [], [], [], [], [], [], [], 0
+    for b, k in zip(order, k0):
+        v, c, f, e = own[b]
+        shift = np.array([0.0, 0.0, h * float(k)])
+        V.append(v + shift)
+        A.append(e.a + shift)
+        B.append(e.b + shift)
+        C.append(c)
+        CA.append(e.ca)
+        CB.append(e.cb)
+        F.append(f.astype(np.int64) + nV)
+        nV += len(v)
+    cat = np.concatenate
+    return cat(V), cat(C), cat(F).astype(np.int32), Ends(cat(A), cat(B), cat(CA), cat(CB))
+
+
+COLUMN_NX, COLUMN_NY, COLUMN_SLICES, COLUMN_GAP, COLUMN_UNITS = 6, 5, 12, 2, 716
+COLUMN_ORIGIN, COLUMN_VOXEL = (0.3, -0.2, 0.1), 0.0004          # 10022 slices: a z extent of 4.0
+SPINE_ROUND = 1024 * 256                                         # nodes (or faces, or vertices) behind which the scan's second round begins
+
+
+def long_column(seed=7):
+    """(blocks, order, gap) for stacked(): a 6 x 5 column of 716 random lattices of 12 slices with 2-slice gaps, 300 660 nodes in 1175
+    blocks of 256, so that the one-block scan of the block sums runs a second round of 151 blocks.  Eight distinct lattices: five sparse
+    (p_invalid = 0.2, 150 to 390 faces each) in a seeded order up to the one that holds node 262 144, three dense (every node valid,
+    about 1640 faces each) in a seeded order from there on: the dense tail is what puts more than 40 % of all faces behind the first
+    round, while the sparse front still passes 2^16 faces and vertices near block 400."""
+    dims = (COLUMN_NX, COLUMN_NY, COLUMN_SLICES)
+    blocks = [random_lattice(dims, 40 + n, p, True) for n, p in enumerate((0.2, 0.2, 0.2, 0.2, 0.2, 0.0, 0.0, 0.0))]
+    straddles = SPINE_ROUND // (COLUMN_NX * COLUMN_NY) // (COLUMN_SLICES + COLUMN_GAP)
+    rs = np.random.RandomState(seed)
+    order = [int(rs.randint(0, 5)) if u < straddles else int(rs.randint(5, 8)) for u in range(COLUMN_UNITS)]
+    return blocks, order, COLUMN_GAP
+
+
+def _classes(tsdf, weight, min_weight):
+    tsdf, weight = np.asarray(tsdf, np.float32), np.asarray(weight, np.float32)
+    nz, ny, nx = tsdf.shape
+    with np.errstate(invalid="ignore"):
+        valid = weight >= np.float32(min_weight)
+        inside = tsdf < np.float32(0)
+    ok = np.ones((nz - 1, ny - 1, nx - 1), bool)
+    for dz, dy, dx in itertools.product((0, 1), repeat=3):
+        ok &= valid[dz:nz - 1 + dz, dy:ny - 1 + dy, dx:nx - 1 + dx]
+    return valid, inside, ok
+
+
+def coverage(tsdf, weight, min_weight=1.0):
+    """(pairs, configs) the valid cells of a grid reach: the set of (tetrahedron, inside mask over p0..p3), 96 at most, and the set of
+    corner configurations (bit x + 2y + 4z), 256 at most.  Only there to assert that an input reaches what it is meant to."""
+    valid, inside, ok = _classes(tsdf, weight, min_weight)
+    nz, ny, nx = inside.shape
+    corner = lambda x, y, z: inside[z:nz - 1 + z, y:ny - 1 + y, x:nx - 1 + x][ok].astype(np.int64)
+    config = sum(corner(x, y, z) << (x + 2 * y + 4 * z) for z, y, x in itertools.product((0, 1), repeat=3))
+    pairs = set()
+    for t in range(6):
+        mask = sum(corner(*p) << v for v, p in enumerate(tet_corners(t)))
+        pairs |= {(t, int(m)) for m in np.unique(mask)}
+    return pairs, {int(c) for c in np.unique(config)}
+
+
+def held_classes(tsdf, weight, min_weight=1.0):
+    """dict(none, some, all): the lattice edges whose two ends are valid and differ in `inside`, split by how many of the cells of the
+    grid that contain the edge are valid.  Only `none` carries no vertex."""
+    valid, inside, ok = _classes(tsdf, weight, min_weight)
+    nz, ny, nx = inside.shape
+    cells = np.zeros((nz + 1, ny + 1, nx + 1), np.int64)            # cell c at index c + 1, no cell beyond the borders
+    exists = np.zeros_like(cells)
+    cells[1:-1, 1:-1, 1:-1] = ok
+    exists[1:-1, 1:-1, 1:-1] = 1
+    out = dict(none=0, some=0, all=0)
+    for dx, dy, dz in DIRECTIONS:
+        lo = (slice(0, nz - dz), slice(0, ny - dy), slice(0, nx - dx))
+        hi = (slice(dz, nz), slice(dy, ny), slice(dx, nx))
+        held, around = np.zeros(inside[lo].shape, np.int64), np.zeros(inside[lo].shape, np.int64)
+        for oz, oy, ox in itertools.product(((1,) if dz else (0, 1)), ((1,) if dy else (0, 1)), ((1,) if dx else (0, 1))):
+            at = (slice(oz, oz + nz - dz), slice(oy, oy + ny - dy), slice(ox, ox + nx - dx))
+            held += cells[at]
+            around += exists[at]
+        cand = valid[lo] & valid[hi] & (inside[lo] != inside[hi])
+        out["none"] += int((cand & (held == 0)).sum())
+        out["all"] += int((cand & (held == around)).sum())
+        out["some"] += int((cand & (held > 0) & (held < around)).sum())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------- integration

@@ -4,6 +4,8 @@
         counts = (nV_out, nT_out, C, kept components, thr, ignored faces), the six the device writes
   labels_by_scipy(faces, nV)    the labels once more from scipy.sparse.csgraph.connected_components, where scipy is installed
   two_spheres() / chain() / singles() / scrambled()      the fixtures: (verts f32 [nV,3], faces i32 [nT,3], colors f32 [nV,3])
+  strips() / star() / sheet() / interleaved() / with_duplicates()      chains of given sizes, faces about one hub, a triangulated grid,
+                                two chains on the even and odd indices, repeated faces
 
 Everything is exact: labels, sizes and counts are integers, and the rows of vertices and colours are gathered, not computed.
 """
@@ -142,6 +144,69 @@ def chain(N, order, seed=5):
         assert order == "ascending"
     rs = np.random.RandomState(seed + 1)
     return rs.rand(N + 2, 3).astype(np.float32), np.ascontiguousarray(faces), rs.rand(N + 2, 3).astype(np.float32)
+
+
+def _rows(nV, seed):
+    rs = np.random.RandomState(seed)
+    return rs.rand(nV, 3).astype(np.float32), rs.rand(nV, 3).astype(np.float32)
+
+
+def strips(sizes, seed=13):
+    """Disjoint chains, one per entry of `sizes`: the n-th has sizes[n] faces (i, i+1, i+2) over sizes[n] + 2 vertices of its own, in
+    the order given: component n has exactly sizes[n] faces."""
+    faces, at = [], 0
+    for n in sizes:
+        i = np.arange(n, dtype=np.int64) + at
+        faces.append(np.stack([i, i + 1, i + 2], 1))
+        at += n + 2
+    verts, colors = _rows(at, seed)
+    return verts, np.concatenate(faces).astype(np.int32), colors
+
+
+def star(n, hub, seed=14):
+    """n faces (hub, a_i, b_i) over 2 n + 1 vertices that share the hub and nothing else: no two faces share an edge, all are one
+    component.  hub = "first": the hub is vertex 0 (the root every union arrives at); "last": vertex 2 n (the one every union hangs)."""
+    assert hub in ("first", "last")
+    i = np.arange(n, dtype=np.int64)
+    if hub == "first":
+        faces = np.stack([np.zeros(n, np.int64), 1 + 2 * i, 2 + 2 * i], 1)
+    else:
+        faces = np.stack([np.full(n, 2 * n, np.int64), 2 * i, 2 * i + 1], 1)
+    verts, colors = _rows(2 * n + 1, seed)
+    return verts, faces.astype(np.int32), colors
+
+
+def sheet(n, m, seed=15):
+    """A grid of n x m quads, each cut into two triangles: (n + 1)(m + 1) vertices, 2 n m faces, one component."""
+    j, i = np.meshgrid(np.arange(n, dtype=np.int64), np.arange(m, dtype=np.int64), indexing="ij")
+    v = (j * (m + 1) + i).reshape(-1)
+    faces = np.stack([np.stack([v, v + 1, v + m + 2], 1), np.stack([v, v + m + 2, v + m + 1], 1)], 1).reshape(-1, 3)
+    verts, colors = _rows((n + 1) * (m + 1), seed)
+    return verts, faces.astype(np.int32), colors
+
+
+def interleaved(n, drop=0, seed=16):
+    """Two chains of n faces each, one over the even vertex indices (2i, 2i+2, 2i+4) and one over the odd (2i+1, 2i+3, 2i+5), their
+    faces by turns: neighbouring indices lie in different components throughout.  drop: faces left off the END of the odd chain (its
+    last vertices are then in no face)."""
+    i = np.arange(n, dtype=np.int64)
+    faces = np.stack([np.stack([2 * i, 2 * i + 2, 2 * i + 4], 1), np.stack([2 * i + 1, 2 * i + 3, 2 * i + 5], 1)], 1).reshape(-1, 3)
+    keep = np.ones(2 * n, bool)
+    if drop:
+        keep[2 * (n - drop) + 1::2] = False
+    verts, colors = _rows(2 * n + 4, seed)
+    return verts, faces[keep].astype(np.int32), colors
+
+
+def with_duplicates(verts, faces, colors, every=3, seed=17):
+    """The mesh with every `every`-th face said once more, as the same triple or rotated, spliced in at seeded places: a repeat is a
+    counted face like any other (a component's size counts it)."""
+    rs = np.random.RandomState(seed)
+    again = faces[::every].copy()
+    turn = rs.randint(0, 3, len(again))
+    again = again[np.arange(len(again))[:, None], (np.arange(3)[None, :] + turn[:, None]) % 3]
+    at = np.sort(rs.randint(0, len(faces) + 1, len(again)))
+    return verts, np.insert(faces, at, again, axis=0).astype(np.int32), colors
 
 
 def singles(n=70000, fan=60, seed=9):

@@ -1,7 +1,9 @@
 """gsr_mesh.clean_mesh, cluster_connected_triangles and utils.mesh_utils.post_process_mesh on the GPU against the integer restatement
 (tests/meshclean_ref.py).  Every comparison is exact: the label and size of every face, the six counts, the faces, and the rows of vertices
 and colours bit for bit.  The shapes are the smallest that cross what can break: components that span several 256-blocks, the deepest
-tree the union can build, more than 2^16 components (more than 256 blocks of roots), and the empty and all-ignored edges."""
+tree the union can build, more than 2^16 components (more than 256 blocks of roots), and the empty and all-ignored edges; component
+sizes with a third byte and ties among them over more than 1024 blocks, 70 000 faces about one hub, a scrambled sheet, interleaved
+chains, repeated faces."""
 import numpy as np
 import pytest
 import torch
@@ -211,6 +213,98 @@ def test_on_a_side_stream_behind_a_producer(spheres):
     side.synchronize()
     assert_same(R.Cleaned(out.vertices.cpu().numpy(), out.faces.cpu().numpy(), out.colors.cpu().numpy(), tri_label.cpu().numpy(),
                           tri_size.cpu().numpy(), tuple(info)), ref)
+
+
+# ------------------------------------------------------------------------------------------------- sizes of more than two bytes
+STRIP_SIZES = (70000, 66000, 66000, 65536, 300, 256, 255, 1)          # 0x011170, 0x0101d0 twice, 0x010000: byte 2 is 1 in four of them
+STRIP_PARAMS = tuple((k, 0) for k in range(1, 9)) + ((8, 65537), (2, 10 ** 9))
+
+
+def _fixture(verts, faces, colors):
+    """(verts, faces, colors, vertex labels, the mesh on the device)."""
+    return verts, faces, colors, R.vertex_labels(faces, len(verts)), _mesh(verts, faces, colors)
+
+
+@pytest.fixture(scope="module")
+def strips():
+    return _fixture(*R.scrambled(*R.strips(STRIP_SIZES), 31))
+
+
+@pytest.mark.parametrize("cluster_to_keep, min_triangles", STRIP_PARAMS)
+def test_sizes_with_a_third_byte(strips, cluster_to_keep, min_triangles):
+    """Eight chains, four of them above 2^16 faces, scrambled: the select has to choose digit 1 in byte 2, then tell 0x11, 0x01, 0x01 and
+    0x00 apart in byte 1 among the sizes that match, with a tie at 66 000 that k = 2 and k = 3 both land in.  268 348 faces and 268 364
+    vertices are 1049 blocks of either, so the compaction's scan runs a second round too."""
+    verts, faces, colors, labels, mesh = strips
+    assert min(len(verts), len(faces)) > 1024 * 256
+    ref = R.clean(verts, faces, colors, cluster_to_keep, min_triangles, labels)
+    assert ref.counts[2] == 8 and ref.counts[4] == max(sorted(STRIP_SIZES, reverse=True)[cluster_to_keep - 1], min_triangles)
+    assert_same(clean_raw(mesh, cluster_to_keep, min_triangles), ref)
+    if (cluster_to_keep, min_triangles) == (3, 0):
+        assert_same(via_python(mesh, cluster_to_keep, min_triangles), ref)
+        assert ref.counts == R.clean(verts, faces, colors, 2, 0, labels).counts == (202006, 202000, 8, 3, 66000, 0)
+    if cluster_to_keep == 4:
+        assert ref.counts[1] == 70000 + 66000 + 66000 + 65536          # more than 2^18 kept faces: rows behind block 1023 move
+
+
+# ------------------------------------------------------------------------------------------------- contention and shapes of the union
+@pytest.fixture(scope="module")
+def stars():
+    out = {}
+    for hub in ("first", "last"):
+        plain = R.star(70000, hub)
+        out[hub, "plain"] = _fixture(*plain)
+        out[hub, "scrambled"] = _fixture(*R.scrambled(*plain, 33))
+    return out
+
+
+@pytest.mark.parametrize("order", ["plain", "scrambled"])
+@pytest.mark.parametrize("hub", ["first", "last"])
+def test_star_about_one_hub(stars, hub, order):
+    """70 000 faces (hub, a_i, b_i) that share the hub only: every union names one address, as the root all arrive at (hub first) or as
+    the vertex every thread tries to hang (hub last).  No two faces share an edge — connected by a vertex is connected here — and the one
+    component has a third size byte."""
+    verts, faces, colors, labels, mesh = stars[hub, order]
+    ref = R.clean(verts, faces, colors, 1, 50, labels)
+    assert ref.counts == (140001, 70000, 1, 1, 70000, 0) and len(set(ref.tri_label.tolist())) == 1
+    assert_same(clean_raw(mesh, 1, 50), ref)
+    assert_same(via_python(mesh, 1, 50), ref)
+    assert_same(clean_raw(mesh, 2, 70001), R.clean(verts, faces, colors, 2, 70001, labels))          # nothing reaches the minimum
+
+
+def test_scrambled_sheet():
+    """A 300 x 300 grid of quads, 180 000 faces (0x02bf20) in one component, faces and vertex rows in random order: unions arrive from
+    everywhere in a 2-D neighbourhood structure, not along a path."""
+    verts, faces, colors, labels, mesh = _fixture(*R.scrambled(*R.sheet(300, 300), 32))
+    ref = R.clean(verts, faces, colors, 1, 50, labels)
+    assert ref.counts == (90601, 180000, 1, 1, 180000, 0)
+    assert_same(clean_raw(mesh, 1, 50), ref)
+    assert_same(via_python(mesh, 1, 50), ref)
+
+
+@pytest.mark.parametrize("drop", [0, 1])
+def test_interleaved_chains_stay_apart(drop):
+    """Two chains of 40 000 faces on the even and the odd vertex indices: neighbouring indices never share a component, so a link to the
+    wrong neighbour shows.  Equal sizes: k = 1 keeps both (the tie); one face fewer in the odd chain: k = 1 keeps the even one alone."""
+    verts, faces, colors, labels, mesh = _fixture(*R.interleaved(40000, drop=drop))
+    ref = R.clean(verts, faces, colors, 1, 0, labels)
+    assert ref.counts == ((80004, 80000, 2, 2, 40000, 0) if drop == 0 else (40002, 40000, 2, 1, 40000, 0))
+    assert sorted(set(ref.tri_label.tolist())) == [0, 1]
+    assert_same(clean_raw(mesh, 1, 0), ref)
+    assert_same(via_python(mesh, 1, 0), ref)
+    assert_same(clean_raw(mesh, 2, 0), R.clean(verts, faces, colors, 2, 0, labels))
+
+
+def test_repeated_faces_count_every_time():
+    """Every third face said once more (as it is or rotated), scrambled: a repeat is a counted face, a component's size counts it, and
+    the kept repeats are emitted."""
+    verts, faces, colors, labels, mesh = _fixture(*R.scrambled(*R.with_duplicates(*R.strips((5000, 3000, 700, 2))), 34))
+    assert len(faces) == 8702 + 2901
+    for k, m in ((1, 0), (2, 0), (3, 1000), (4, 0)):
+        ref = R.clean(verts, faces, colors, k, m, labels)
+        assert_same(clean_raw(mesh, k, m), ref)
+    assert ref.counts[1] == len(faces) and sorted(set(ref.tri_size.tolist())) == [3, 933, 4000, 6667]
+    assert_same(via_python(mesh, 2, 0), R.clean(verts, faces, colors, 2, 0, labels))
 
 
 # ------------------------------------------------------------------------------------------------- end to end

@@ -150,3 +150,89 @@ def test_extractor_refuses_a_box_beyond_the_dense_limit(hip_lib_built):
         ex.extract_mesh_bounded(voxel_size=0.004, bounds=((-5, -5, -5), (5, 5, 5)))
     with pytest.raises(ValueError, match="reconstruction"):
         GaussianExtractor.camera_bounds(ex)
+
+
+# ------------------------------------------------------------------------------------------------- random lattices, the inputs of the exact GPU tests
+def test_random_lattice_with_exact_zeros_gives_a_closed_oriented_surface():
+    """Every node valid, the border outside: whatever the signs inside, and with 3 % of the nodes at 0.0 and 2 % at -0.0 (outside both),
+    every edge lies in exactly two faces and every directed edge appears once."""
+    for seed in (1, 2):
+        tsdf, weight, color = M.with_outside_border(M.random_lattice(M.GRID, seed, 0.0, True))
+        zeros = tsdf == 0
+        assert zeros.sum() > 50 and np.signbit(tsdf[zeros]).any() and not np.signbit(tsdf[zeros]).all()
+        assert (np.abs(tsdf[~zeros]) >= np.float32(0.05)).all() and np.abs(tsdf).max() <= 1
+        V, _, F = M.extract(tsdf, weight, None, M.GRID_ORIGIN, M.GRID_VOXEL)
+        t = M.topology(F, len(V))
+        print(f"seed {seed}: {len(V)} vertices, {len(F)} faces, {t}")
+        assert len(F) > 10000
+        assert (t["boundary"], t["nonmanifold"], t["repeated_directed"], t["unreferenced"]) == (0, 0, 0, 0)
+
+
+def test_random_lattices_reach_every_case_of_the_table():
+    for seed in (1, 2):
+        tsdf, weight, _ = M.random_lattice(M.GRID, seed, 0.0, True)
+        pairs, configs = M.coverage(tsdf, weight)
+        print(f"seed {seed}: {len(pairs)} (tetrahedron, mask) pairs, {len(configs)} corner configurations")
+        assert len(pairs) == 96 and len(configs) >= 250
+    # what the analytic grids reach, for comparison (the reason for the lattices)
+    assert len(M.coverage(*M.sphere_grid()[:2])[1]) < 100
+
+
+def test_config_lattice_holds_each_configuration_once():
+    tsdf, weight, color = M.config_lattice()
+    assert tsdf.shape == M.CONFIG_DIMS[::-1]
+    pairs, configs = M.coverage(tsdf, weight)
+    assert configs == set(range(256)) and len(pairs) == 96
+    _, _, ok = M._classes(tsdf, weight, 1.0)
+    assert ok.sum() == 256 and ok.reshape(-1)[::3].all()
+    mags = np.abs(tsdf).reshape(256, 3, 4)[:, :2].reshape(256, 8)
+    assert all(len(set(row)) == 8 for row in mags.tolist())
+    V, C, F = M.extract(tsdf, weight, color, (0.0, 0.0, 0.0), 0.5)
+    assert (len(V), len(F)) == (2432, 1920)
+    assert M.topology(F, len(V))["unreferenced"] == 0
+
+
+def test_scattered_invalid_nodes_leave_edges_held_by_none_some_and_all_of_their_cells():
+    for seed in (3, 4):
+        tsdf, weight, color = M.random_lattice(M.GRID, seed, 0.08, True)
+        assert np.isnan(weight).sum() > 20 and (weight == 0.5).sum() > 20 and (weight == 0).sum() > 20 and (weight == 1).sum() > 500
+        held = M.held_classes(tsdf, weight)
+        V, _, F = M.extract(tsdf, weight, None, M.GRID_ORIGIN, M.GRID_VOXEL)
+        print(f"seed {seed}: {held}, {len(V)} vertices, {len(F)} faces")
+        assert min(held.values()) >= 500
+        assert len(V) == held["some"] + held["all"]                # `none` is exactly what carries no vertex
+        assert M.topology(F, len(V))["unreferenced"] == 0
+    # the analytic grid with its one invalid column has no such mixture to speak of
+    assert M.held_classes(*M.sphere_grid()[:2])["none"] == 0
+
+
+def test_stacked_composition_is_the_direct_extraction():
+    blocks = [M.random_lattice((6, 5, 4), 1, 0.0, True), M.random_lattice((6, 5, 4), 2, 0.1, True)]
+    order, origin, voxel = [0, 1, 1, 0], (0.3, -0.2, 0.1), 0.07
+    tsdf, weight, color, k0 = M.stacked(blocks, order, 3)
+    assert list(k0) == [0, 7, 14, 21] and tsdf.shape == (25, 5, 6) and not (weight[4:7] >= 1).any()
+    V, C, F, E = M.stacked_mesh(blocks, order, k0, origin, voxel)
+    V2, C2, F2, E2 = M.extract(tsdf, weight, color, origin, voxel, ends=True)
+    assert len(F) > 500 and F.shape == F2.shape and (F == F2).all()
+    assert np.abs(V - V2).max() < 1e-15 and (C == C2).all()
+    assert np.abs(E.a - E2.a).max() < 1e-15 and np.abs(E.b - E2.b).max() < 1e-15 and (E.ca == E2.ca).all() and (E.cb == E2.cb).all()
+    pos, col = M.extract_bounds(E, voxel)
+    assert pos.shape == V.shape and col.shape == C.shape and pos.min() >= 4 * M.U32 * float(np.float32(voxel))
+
+
+def test_long_column_puts_two_fifths_of_its_faces_behind_the_first_round_of_the_scan():
+    blocks, order, gap = M.long_column()
+    tsdf, weight, color, k0 = M.stacked(blocks, order, gap)
+    per_slice = M.COLUMN_NX * M.COLUMN_NY
+    assert tsdf.shape[0] >= 8800 and tsdf.size > M.SPINE_ROUND + 256
+    faces = np.array([len(M.extract(*b, M.COLUMN_ORIGIN, M.COLUMN_VOXEL)[2]) for b in blocks])[order]
+    verts = np.array([len(M.extract(*b, M.COLUMN_ORIGIN, M.COLUMN_VOXEL)[0]) for b in blocks])[order]
+    first_node = k0 * per_slice
+    at = int(np.searchsorted(first_node, M.SPINE_ROUND, side="right")) - 1
+    assert first_node[at] < M.SPINE_ROUND < first_node[at] + M.COLUMN_SLICES * per_slice          # one lattice straddles node 262 144
+    behind = faces[at + 1:].sum() / faces.sum()                                                      # (the straddling one not counted)
+    blocks_16 = [int(first_node[np.searchsorted(np.cumsum(c), 2 ** 16)]) // 256 for c in (verts, faces)]
+    print(f"{tsdf.size} nodes in {-(-tsdf.size // 256)} blocks, {verts.sum()} vertices, {faces.sum()} faces, {behind:.3f} of them behind node 262144; "
+          f"2^16 vertices by block {blocks_16[0]}, faces by block {blocks_16[1]}")
+    assert behind > 0.4 and max(blocks_16) < 512
+    assert tsdf.shape[0] * M.COLUMN_VOXEL < 5

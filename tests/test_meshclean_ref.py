@@ -103,3 +103,63 @@ def test_many_singles_select_clamp_and_tie():
     assert R.clean(verts, faces, None, 2, 0).counts == (len(verts), n + fan, n + 1, n + 1, 1, 0)          # s_2 = 1: a 70 000-way tie
     assert R.clean(verts, faces, None, 2, 50).counts == (fan + 2, fan, n + 1, 1, 50, 0)
     assert R.clean(verts, faces, None, 10 ** 9, 0).counts == (len(verts), n + fan, n + 1, n + 1, 1, 0)   # the clamp
+
+
+# ------------------------------------------------------------------------------------------------- the builders of the multi-byte and contention tests
+def _labels(faces, nV):
+    """vertex_labels(), held to scipy's where scipy is installed."""
+    labels = R.vertex_labels(faces, nV)
+    by_scipy = R.labels_by_scipy(faces, nV)
+    assert by_scipy is None or (labels == by_scipy).all()
+    return labels
+
+
+def test_strips_have_the_sizes_asked_for():
+    sizes = (700, 660, 660, 300, 256, 255, 1)
+    verts, faces, colors = R.scrambled(*R.strips(sizes), 31)
+    assert len(faces) == sum(sizes) and len(verts) == sum(sizes) + 2 * len(sizes)
+    labels = _labels(faces, len(verts))
+    assert sorted(np.bincount(labels[faces[:, 0]])[np.unique(labels)].tolist(), reverse=True) == sorted(sizes, reverse=True)
+    thr = [R.clean(verts, faces, colors, k, 0, labels).counts[4] for k in range(1, len(sizes) + 1)]
+    assert thr == [700, 660, 660, 300, 256, 255, 1]
+    two, three = R.clean(verts, faces, colors, 2, 0, labels), R.clean(verts, faces, colors, 3, 0, labels)
+    assert two.counts == three.counts == (700 + 660 + 660 + 6, 700 + 660 + 660, 7, 3, 660, 0) and (two.faces == three.faces).all()
+
+
+def test_star_is_one_component_although_no_two_faces_share_an_edge():
+    for hub in ("first", "last"):
+        verts, faces, colors = R.star(500, hub)
+        assert len(verts) == 1001 and (faces[:, 0] == (0 if hub == "first" else 1000)).all()
+        assert M.topology(faces, len(verts))["boundary"] == 1500            # every edge lies in one face
+        assert (_labels(faces, len(verts)) == 0).all()
+        assert R.clean(verts, faces, colors, 1, 0).counts == (1001, 500, 1, 1, 500, 0)
+
+
+def test_sheet_is_one_manifold_component():
+    verts, faces, colors = R.sheet(30, 20)
+    t = M.topology(faces, len(verts))
+    assert (len(verts), len(faces)) == (31 * 21, 1200) and t["boundary"] == 100 and t["nonmanifold"] == 0 and t["euler"] == 1
+    assert t["repeated_directed"] == 0 and t["unreferenced"] == 0
+    v, f, _ = R.scrambled(verts, faces, colors, 32)
+    assert (_labels(f, len(v)) == 0).all()
+
+
+def test_interleaved_chains_stay_apart():
+    verts, faces, colors = R.interleaved(400)
+    labels = _labels(faces, len(verts))
+    assert (labels == np.arange(len(verts)) % 2).all()
+    assert R.clean(verts, faces, colors, 1, 0, labels).counts == (804, 800, 2, 2, 400, 0)          # the tie: k = 1 keeps both
+    verts, faces, colors = R.interleaved(400, drop=1)
+    out = R.clean(verts, faces, colors, 1, 0)
+    assert out.counts == (402, 400, 2, 1, 400, 0) and (out.tri_size[1::2] == 399).all() and len(faces) == 799
+    assert (out.verts == verts[::2]).all()
+
+
+def test_repeated_faces_count_every_time():
+    verts, faces, colors = R.strips((500, 300, 70, 2))
+    v, f, c = R.with_duplicates(verts, faces, colors, every=3)
+    assert len(f) == len(faces) + len(faces[::3])
+    assert len(np.unique(np.sort(f, 1), axis=0)) == len(faces)                                     # nothing new, only repeats
+    out = R.clean(v, f, c, 2, 0, _labels(f, len(v)))
+    assert sorted(set(out.tri_size.tolist())) == [3, 93, 400, 667]                                  # 2 + 1, 70 + 23 (faces 800, 803, ...), 300 + 100, 500 + 167
+    assert out.counts == (804, 1067, 4, 2, 400, 0)
