@@ -73,6 +73,16 @@ unsigned long long* dev_pair_counter() {
 	}
 	return words[dev];
 }
+// compute units of the current device, asked once per device (0: not known)
+int cu_count() {
+	static std::mutex mu;
+	static int cus[64];
+	int dev = 0;
+	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+	std::lock_guard<std::mutex> lk(mu);
+	if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); cus[dev] = 0; }
+	return cus[dev];
+}
 static int g_opt_emit_items = 0;   // 0: by the Gaussian count (EMIT_ITEMS2_FROM); 1 / 2: forced (tests)
 static int g_opt_mailbox = 1;
 static int option_mailbox() { return g_opt_mailbox; }
@@ -816,7 +826,7 @@ extern "C" int gsr_debug_fetch(int variant, const char* name, int P, int R, int 
 	{
 		// which workspace each array lives in (0 geometry, 1 binning, 2 image, -1 none), and whether this call copies anything out of it
 		static const struct { const char* name; int buf; } arrays[] = {
-			{"pairs", -1}, {"depths", 0}, {"means2D", 0}, {"tiles_touched", 0}, {"cull", 0}, {"point_offsets", 0}, {"clamped", 0}, {"rgb", 0}, {"geom4", 0},
+			{"pairs", -1}, {"pergauss_grid", -1}, {"depths", 0}, {"means2D", 0}, {"tiles_touched", 0}, {"cull", 0}, {"point_offsets", 0}, {"clamped", 0}, {"rgb", 0}, {"geom4", 0},
 			{"transMat", 0}, {"cov3D", 0}, {"point_list", 1}, {"blend_mask", 1}, {"keys", 1}, {"ranges", 2}, {"final_T", 2}, {"n_contrib", 2}};
 		int buf = -2;
 		for (const auto& a : arrays) if (strcmp(a.name, name) == 0) buf = a.buf;
@@ -849,6 +859,14 @@ extern "C" int gsr_debug_fetch(int variant, const char* name, int P, int R, int 
 		const unsigned long long* word = dev_pair_counter();
 		if (!word) { set_error("gsr_debug_fetch: no pair counter"); return GSR_E_HIP; }
 		return d2d(word, sizeof(unsigned long long));
+	}
+	if (n == "pergauss_grid") {   // launch shape of the per-Gaussian passes on the current device (no buffer is read)
+		// variant S's backward pass and both passes of variant G are one-shot kernels: one workgroup per batch, no resident-slot count
+		const int fwd = variant == 0 ? S_PRE_FWD_WGS : 0, bwd = 0;
+		const uint32_t grids[4] = {(uint32_t)pergauss_grid(P, fwd), (uint32_t)pergauss_grid(P, bwd), (uint32_t)(cu_count() * fwd), (uint32_t)(cu_count() * bwd)};
+		GSR_HIP_CHECK(hipMemcpyAsync(dst, grids, sizeof(grids), hipMemcpyHostToDevice, stream));
+		GSR_HIP_CHECK(hipStreamSynchronize(stream));   // (`grids` is on this frame)
+		return 0;
 	}
 	if (n == "depths") return d2d(g.depths, (size_t)P * 4);
 	if (n == "means2D") return gather(0, 2);     // the first two floats of the render record of both variants (not kept as an array of its own since round 4)

@@ -201,6 +201,23 @@ int option_dev();    // development bits (0 in production): 1 = skip the gradien
                      // the (wave, entry) pairs they evaluate to the current device's word (dev_pair_counter; gsr_debug_fetch("pairs") reads it); 4 = with 2, the vote
                      // tests against the whole 8x8 block, not against its live pixels (the count the live box is compared with)
 unsigned long long* dev_pair_counter();   // device address of that word: allocated and zeroed at its first use, never reset; NULL on failure
+// Launch shape of the persistent per-Gaussian passes (pergauss_batches below): `wgs_per_cu` resident workgroups of PG_BLOCK threads on
+// every compute unit of the current device, never more workgroups than batches.  The CU count is asked once per device.
+#define PG_BLOCK 256
+// Resident workgroups per CU (= waves per SIMD: a workgroup is four waves) of variant S's forward pass; the kernel is compiled for that
+// occupancy (amdgpu_waves_per_eu).  Measured at 1 / 2 / 3 / 4: profiles/pergauss_batches_occupancy.txt.
+#ifndef S_PRE_FWD_WGS
+#define S_PRE_FWD_WGS 1
+#endif
+int cu_count();   // of the current device; 0 when it cannot be read (the passes then launch one workgroup per batch)
+// With more batches than resident workgroups every workgroup makes the same number of trips (the last one may be short): the smallest grid that
+// needs no more trips than the full one, so that no workgroup idles through a last round (3907 batches on 256 slots: 245 workgroups x 16 trips).
+static inline int pergauss_grid(int P, int wgs_per_cu) {
+	const long long nb = ((long long)P + PG_BLOCK - 1) / PG_BLOCK, cap = (long long)cu_count() * wgs_per_cu;
+	if (cap <= 0 || cap >= nb) return (int)nb;
+	const long long trips = (nb + cap - 1) / cap;
+	return (int)((nb + trips - 1) / trips);
+}
 size_t sort_temp_bytes(size_t R, int end_bit);
 int run_tile_order(const ImageState& img, size_t tiles, hipStream_t stream);
 uint32_t higher_msb(uint32_t n);
@@ -362,6 +379,71 @@ template <bool ACC> __device__ __forceinline__ void put4(float4* p, float a, flo
 		*p = make_float4(a, b, c, d);
 	}
 }
+// ---- persistent, software-pipelined per-Gaussian pass.  The per-Gaussian kernels are streaming kernels with ~1000 VALU instructions
+// between their loads and their stores; launched one Gaussian per lane and one shot per wave, a wave has loads in flight only at the start
+// of its life and the memory system idles while it computes.  Here a grid of pergauss_grid() workgroups walks the batches of PG_BLOCK
+// Gaussians grid-stride, and every lane keeps the inputs of its NEXT Gaussian in registers (`In`, a register double buffer) while it
+// computes the current one:
+//   load(in, row)          issues the unconditional loads of Gaussian `row` into `in` and must not use what it loads;
+//   late(in, row)          issues the loads of the part of `in` that has ONE buffer (the forward's SH row, 48 registers); it is called through
+//                          `mid`, which the body invokes once it has finished with that part of the current Gaussian: it may use what load()
+//                          fetched (and then waits for it);
+//   body(in, idx, mid)     one Gaussian: idx = batch * PG_BLOCK + thread, which may lie past P in the last batch (the body tests it, as the
+//                          one-shot kernels did); the body takes its lane and wave from idx.  A `return` inside it ends this Gaussian, not the walk.
+// The two buffers alternate by unrolling the walk twice, so no register copies are made.  The prefetch is issued on EVERY trip, the last one
+// included, and never reads past the arrays: its row is clamped to the last batch and to P - 1, so a lane past the end re-reads row P - 1 and the
+// prefetch behind the last batch re-reads that batch (out of L2) for nothing.  Unconditional on purpose: s_waitcnt vmcnt counts in order, the
+// wait for the current buffer may leave exactly as many loads outstanding as every path to it has issued since, and a path without the
+// prefetch would bring that number down to a handful.  No workgroup barrier, no communication between workgroups.
+//
+// A load in the middle of the body whose result is needed at once waits for EVERYTHING older (vmcnt counts in order), the prefetch included: the
+// body must not load.  What every Gaussian reads of the camera is therefore fetched once, in front of the walk, and kept in scalar registers
+// (the values are wave-uniform; readfirstlane says so to the compiler, which cannot prove that the kernel's own stores leave them alone).
+__device__ __forceinline__ float wave_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+struct CamRegs {
+	float view[16], proj[16], campos[3];
+	__device__ __forceinline__ explicit CamRegs(const RasterCam& c) {
+#pragma unroll
+		for (int i = 0; i < 16; i++) { view[i] = wave_uniform(c.view[i]); proj[i] = wave_uniform(c.proj[i]); }
+#pragma unroll
+		for (int i = 0; i < 3; i++) campos[i] = wave_uniform(c.campos[i]);
+	}
+	// `c` with its three pointers on this copy
+	__device__ __forceinline__ RasterCam cam(RasterCam c) const { c.view = view; c.proj = proj; c.campos = campos; return c; }
+};
+// A buffer that load() or late() fills only under a condition must be given up where it is not filled: otherwise the values it held two trips
+// ago stay alive on that path, and with them a second set of its registers (measured: the forward with load_sh's conditional walk, 203 VGPRs
+// against 150).  forget() defines every element anew without an instruction.
+template <int N> __device__ __forceinline__ void forget(float (&v)[N]) {
+#pragma unroll
+	for (int k = 0; k < N; k++) asm("" : "=v"(v[k]));
+}
+template <class In, class Load, class Late, class Body>
+__device__ __forceinline__ void pergauss_batches(int P, Load load, Late late, Body body) {
+	const int nb = (int)(((unsigned)P + PG_BLOCK - 1u) / PG_BLOCK), step = (int)gridDim.x, tid = (int)threadIdx.x;
+	int b = (int)blockIdx.x;
+	if (b >= nb) return;
+	auto row = [&](int batch) { return min(min(batch, nb - 1) * PG_BLOCK + tid, P - 1); };
+	In in0, in1;
+	load(in0, row(b));
+	late(in0, row(b));
+	// The body gets its thread number through an empty asm, once per trip: what it derives from its lane alone (the row and column numbers of the
+	// wave-cooperative stores, three registers per stored plane) is then computed where it is used, as in a one-shot kernel, and not kept across the walk.
+	auto thread = [&] { int t = tid; asm volatile("" : "+v"(t)); return t; };
+	for (;;) {
+		int n = b + step;
+		load(in1, row(n));
+		body(in0, b * PG_BLOCK + thread(), [&] { late(in1, row(n)); });
+		if (n >= nb) return;
+		b = n;
+		n = b + step;
+		load(in0, row(n));
+		body(in1, b * PG_BLOCK + thread(), [&] { late(in0, row(n)); });
+		if (n >= nb) return;
+		b = n;
+	}
+}
+
 // v_ffbl_b32: index of the lowest set bit, 0xFFFFFFFF for 0 (which __builtin_ctz leaves undefined)
 __device__ __forceinline__ uint32_t ffbl_raw(uint32_t x) {
 	uint32_t r;

@@ -131,27 +131,81 @@ __device__ __forceinline__ void surfel_cull_record(const M3& T, float cx, float 
 	c1.x = fc;
 }
 
+// The inputs of one surfel that the forward reads whatever becomes of it: fetched one batch ahead (pergauss_batches, gsr_internal.hpp).
+// The SH row is the larger part of them (48 of 60 registers) and has ONE buffer: the pass
+// evaluates the colour FIRST (surfel_sh_colour: the row and the mean are all it needs) and requests the next surfel's row into the registers
+// that frees, in front of everything else it computes.
+struct SurfelIn {
+	float mean[3], scale[2], rot[4], opacity, refl;
+	uint32_t mask;      // env-scope mask byte (without a mask: a byte nobody reads, see surfel_in_load)
+	ShRow sh;           // (late)
+};
+// PLAIN: the reference's training call — scales and rotations (no precomputed transform), SH rows of 16 coefficients at degree 3 (no precomputed
+// colours).  Its prefetch is straight-line code, 12 + 6 loads with no test between them, so every path to the wait for the current buffer has
+// issued the same number of loads (see pergauss_batches on why that matters).  Otherwise the pointers are tested and load_sh walks the row.
+template <bool PLAIN>
+__device__ __forceinline__ void surfel_in_load_sh(SurfelIn& in, int row, int D, int M, const float* __restrict__ shs) {
+	if constexpr (PLAIN) {
+		const float4* r4 = reinterpret_cast<const float4*>(shs) + (size_t)row * 12;
+#pragma unroll
+		for (int q = 0; q < 12; q++) {
+			const float4 t = r4[q];
+			in.sh.v[4 * q + 0] = t.x; in.sh.v[4 * q + 1] = t.y; in.sh.v[4 * q + 2] = t.z; in.sh.v[4 * q + 3] = t.w;
+		}
+	} else {
+		forget(in.sh.v);
+		if (shs != nullptr) load_sh(shs, row, M, (D + 1) * (D + 1), in.sh);
+	}
+}
+// mask_bytes: env_scope_mask, or without a mask any array of at least P bytes (the byte is fetched and not used: a test of the pointer here
+// would be a second path through the prefetch, and the compiler moves the byte's conversion up into it, with a wait for every load in flight).
+template <bool PLAIN>
+__device__ __forceinline__ void surfel_in_load(SurfelIn& in, int row, const float* __restrict__ means, const float* __restrict__ scales,
+                                               const float* __restrict__ rotations, const float* __restrict__ opacities,
+                                               const float* __restrict__ refl, const uint8_t* __restrict__ mask_bytes) {
+	in.mean[0] = means[3 * row]; in.mean[1] = means[3 * row + 1]; in.mean[2] = means[3 * row + 2];
+	if (PLAIN || scales != nullptr) {      // (NULL with transMat_precomp)
+		in.scale[0] = scales[2 * row]; in.scale[1] = scales[2 * row + 1];
+#pragma unroll
+		for (int k = 0; k < 4; k++) in.rot[k] = rotations[4 * row + k];
+	}
+	in.opacity = opacities[row];
+	in.refl = refl[row];
+	in.mask = mask_bytes[row];
+}
+// computeColorFromSH of the forward (DSR forward.cu:20-71, called at forward.cu:237): the unclamped colour + 0.5.  Evaluated for every lane, in
+// front of the culling tests (a culled surfel's colour is not used).  The empty asm keeps the evaluation HERE: without it the compiler moves the
+// arithmetic down to its only use, and the row's registers stay occupied until then.
+__device__ __forceinline__ F3 surfel_sh_colour(const SurfelIn& in, int D, const RasterCam& cam) {
+#pragma clang fp contract(off)
+	const float mx = in.mean[0], my = in.mean[1], mz = in.mean[2];
+	const float dx = mx - cam.campos[0], dy = my - cam.campos[1], dz = mz - cam.campos[2];
+	const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+	F3 c = sh_eval(D, in.sh, dx / len, dy / len, dz / len);
+	asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z));
+	return c;
+}
+
 // preprocessCUDA forward (DSR forward.cu:149-253); FMA contraction off (integer outputs bit-exact vs oracle).
-// (Occupancy: 88 VGPRs = 5 waves per SIMD.  Forcing 6 / 8 with amdgpu_waves_per_eu was measured on the backward twin of this
-// kernel: 0.175 -> 0.249 / 0.321 ms at C3, the registers it gives up cost more than the waves it gains.)
-// One Gaussian of the pass; returns false where the reference's kernel returns early.  The render record (5 float4) and the
-// cull record (2 float4) are handed back in `o` instead of being stored: the wave stores them together (see the kernel).
+// (Occupancy of the one-shot form of this kernel: 88 VGPRs = 5 waves per SIMD.  Forcing 6 / 8 with amdgpu_waves_per_eu was measured on its
+// backward twin: 0.175 -> 0.249 / 0.321 ms at C3, the registers it gives up cost more than the waves it gains.)
+// One Gaussian of the pass, from its prefetched inputs `in` and its SH colour `c`; returns false where the reference's kernel returns early.
+// The render record (5 float4) and the cull record (2 float4) are handed back in `o` instead of being stored: the wave stores them together
+// (see the kernel).
 // TRAIN = false (inference forward, gsr_surfel_forward_eval): what only the backward reads — the zero-fill of gaussian_weights and
 // the SH clamp flags — is not written; the records come out the same.
 template <bool TRAIN>
 __device__ __forceinline__ bool
-surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
-                      const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
-                      const float* __restrict__ transMat_precomp, const float* __restrict__ colors_precomp, const float* __restrict__ refl,
-                      const uint8_t* __restrict__ env_scope_mask, const RasterCam& cam, int* __restrict__ radii, const GeomState& g, int gx, int gy,
-                      int prefiltered, float* __restrict__ gaussian_weights, float4* o) {
+surfel_preprocess_one(const SurfelIn& in, const F3 c, int idx, float scale_modifier, const float* __restrict__ transMat_precomp,
+                      const float* __restrict__ colors_precomp, const uint8_t* __restrict__ env_scope_mask, const RasterCam& cam,
+                      int* __restrict__ radii, const GeomState& g, int gx, int gy, int prefiltered, float* __restrict__ gaussian_weights, float4* o) {
 #pragma clang fp contract(off)
 	radii[idx] = 0;
 	if constexpr (TRAIN) gaussian_weights[idx] = 0.f;   // the tile kernel merges per-wave maxima into it with atomicMax
 	g.tiles_touched[idx] = 0;
 	reinterpret_cast<uint2*>(g.rect)[idx] = make_uint2(0u, 0u);   // empty tile rectangle: emit_tiles_kernel takes the instance count from its area
 	g.depths[idx] = __int_as_float(0x7f7fffff);   // culled: sorts behind every visible Gaussian in the depth pre-sort
-	const float mx = means[3 * idx], my = means[3 * idx + 1], mz = means[3 * idx + 2];
+	const float mx = in.mean[0], my = in.mean[1], mz = in.mean[2];
 	const float* vm = cam.view;
 	const float pvx = vm[0] * mx + vm[4] * my + vm[8] * mz + vm[12];
 	const float pvy = vm[1] * mx + vm[5] * my + vm[9] * mz + vm[13];
@@ -163,7 +217,7 @@ surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, co
 	M3 T;
 	F3 normal;
 	if (transMat_precomp == nullptr) {
-		compute_transmat(mx, my, mz, scales + 2 * idx, scale_modifier, rotations + 4 * idx, cam, T, normal);
+		compute_transmat(mx, my, mz, in.scale, scale_modifier, in.rot, cam, T, normal);
 	} else {
 #pragma unroll
 		for (int c = 0; c < 3; c++)
@@ -195,11 +249,6 @@ surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, co
 
 	float cr, cg, cb;
 	if (colors_precomp == nullptr) {
-		const float dx = mx - cam.campos[0], dy = my - cam.campos[1], dz = mz - cam.campos[2];
-		const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-		ShRow s;
-		load_sh(shs, idx, M, (D + 1) * (D + 1), s);
-		const F3 c = sh_eval(D, s, dx / len, dy / len, dz / len);
 		if constexpr (TRAIN) g.clamped[idx] = (uint8_t)((c.x < 0 ? 1 : 0) | (c.y < 0 ? 2 : 0) | (c.z < 0 ? 4 : 0));
 		cr = fmaxf(c.x, 0.0f); cg = fmaxf(c.y, 0.0f); cb = fmaxf(c.z, 0.0f);
 	} else {
@@ -209,16 +258,16 @@ surfel_preprocess_one(int idx, int D, int M, const float* __restrict__ means, co
 	radii[idx] = f2i(radius);
 	g.rect[2 * idx] = x0 | (y0 << 16);
 	g.rect[2 * idx + 1] = x1 | (y1 << 16);
-	const float maskv = (env_scope_mask != nullptr && env_scope_mask[idx]) ? 1.0f : 0.0f;
-	surfel_cull_record(T, pxi, pyi, opacities[idx], o[5], o[6]);
+	const float maskv = (env_scope_mask != nullptr && in.mask) ? 1.0f : 0.0f;
+	surfel_cull_record(T, pxi, pyi, in.opacity, o[5], o[6]);
 	float4* rec = o;
 	// Render record, laid out in even-aligned PAIRS so that the tile kernels can feed them to packed fp32 instructions
 	// (v_pk_mul/add/fma_f32 take a 64-bit aligned SGPR pair) straight from the s_load destination:
 	//   {x, y | Tu.x, Tv.x} {Tu.y, Tv.y | Tu.z, Tv.z} {Tw.x, Tw.y | Tw.z, opacity} {n.x, n.y | n.z, refl} {r, g | b, mask}
 	rec[0] = make_float4(pxi, pyi, T.m[0][0], T.m[1][0]);
 	rec[1] = make_float4(T.m[0][1], T.m[1][1], T.m[0][2], T.m[1][2]);
-	rec[2] = make_float4(T.m[2][0], T.m[2][1], T.m[2][2], opacities[idx]);
-	rec[3] = make_float4(normal.x, normal.y, normal.z, refl[idx]);
+	rec[2] = make_float4(T.m[2][0], T.m[2][1], T.m[2][2], in.opacity);
+	rec[3] = make_float4(normal.x, normal.y, normal.z, in.refl);
 	rec[4] = make_float4(cr, cg, cb, maskv);
 	g.tiles_touched[idx] = (y1 - y0) * (x1 - x0);
 	return true;
@@ -237,38 +286,55 @@ struct CubemapInterleave {
 	float4* rgba;
 	uint32_t ntex, LL;
 };
-template <bool TRAIN>
-__global__ void __launch_bounds__(256)
+// Persistent: pergauss_grid(P, S_PRE_FWD_WGS) workgroups walk the batches of 256 surfels, each lane holding its next surfel's inputs while it
+// computes the current one (pergauss_batches).  The wave-private LDS tile is reused every trip (wave_store_rows4 ends with a wave sync).
+// At C3: 94 -> 73-80 us (profiles/pergauss_batches_kernel_trace.txt); the same form of the backward pass gained nothing and was not kept
+// ("Per-Gaussian passes").
+template <bool TRAIN, bool PLAIN>
+__global__ void __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(S_PRE_FWD_WGS, S_PRE_FWD_WGS)))
 surfel_preprocess_kernel(int P, int D, int M, const float* __restrict__ means, const float* __restrict__ scales, float scale_modifier,
                          const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
                          const float* __restrict__ transMat_precomp, const float* __restrict__ colors_precomp,
                          const float* __restrict__ refl, const uint8_t* __restrict__ env_scope_mask, RasterCam cam, int* __restrict__ radii,
                          GeomState g, int gx, int gy, int prefiltered, float* __restrict__ gaussian_weights, CubemapInterleave ci) {
-	const int idx = blockIdx.x * 256 + threadIdx.x;
-	for (uint32_t t = (uint32_t)idx; t < ci.ntex; t += gridDim.x * 256u) {
+	const CamRegs cam_regs(cam);
+	cam = cam_regs.cam(cam);
+	const int tid0 = blockIdx.x * PG_BLOCK + threadIdx.x;     // thread of the grid: the whole-grid stride loops below
+	const uint32_t nthreads = gridDim.x * (uint32_t)PG_BLOCK;
+	for (uint32_t t = (uint32_t)tid0; t < ci.ntex; t += nthreads) {
 		const uint32_t f = t / ci.LL, r = t - f * ci.LL;
 		const float* c = ci.cubemap + (size_t)f * 3 * ci.LL + r;
 		ci.rgba[t] = make_float4(c[0], c[ci.LL], c[2 * (size_t)ci.LL], 0.f);
 	}
 	// look-back state of the depth sort that follows (gsr_sort.hpp): cleared here instead of by a dispatch of its own
-	sort_clear_region(g.depth_sort_temp, g.depth_sort_clear, (size_t)idx, (size_t)gridDim.x * 256u);
-	sort_clear_region(g.emit_state, g.emit_state_bytes, (size_t)idx, (size_t)gridDim.x * 256u);   // look-back state of emit_tiles_kernel's scan
-	if (idx == 0) { g.flags[1] = 0; g.flags[2] = 0; g.flags[3] = 0; }   // [1] workgroup tickets, [2,3] num_rendered (64 bits) of gaussian_stats_kernel
+	sort_clear_region(g.depth_sort_temp, g.depth_sort_clear, (size_t)tid0, (size_t)nthreads);
+	sort_clear_region(g.emit_state, g.emit_state_bytes, (size_t)tid0, (size_t)nthreads);   // look-back state of emit_tiles_kernel's scan
+	if (tid0 == 0) { g.flags[1] = 0; g.flags[2] = 0; g.flags[3] = 0; }   // [1] workgroup tickets, [2,3] num_rendered (64 bits) of gaussian_stats_kernel
 	__shared__ float4 s_out[4][S_REC_F4 * 65];
-	const int lane = threadIdx.x & 63;
-	float4* so = s_out[threadIdx.x >> 6];
-	float4 o[S_OUT_F4];
+	const float* sh_in = colors_precomp == nullptr ? shs : nullptr;   // (precomputed colours: the SH rows are not read)
+	const uint8_t* mask_bytes = env_scope_mask != nullptr ? env_scope_mask : reinterpret_cast<const uint8_t*>(opacities);
+	pergauss_batches<SurfelIn>(
+		P, [&](SurfelIn& in, int row) { surfel_in_load<PLAIN>(in, row, means, scales, rotations, opacities, refl, mask_bytes); },
+		[&](SurfelIn& in, int row) { surfel_in_load_sh<PLAIN>(in, row, D, M, sh_in); },
+		[&](const SurfelIn& in, int idx, auto mid) {
+			const int lane = idx & 63;
+			float4* so = s_out[(idx >> 6) & 3];
+			F3 c = f3(0.f, 0.f, 0.f);
+			if (PLAIN || sh_in != nullptr) c = surfel_sh_colour(in, D, cam);
+			mid();      // the next surfel's SH row, into the registers this one's has left
+			float4 o[S_OUT_F4];
 #pragma unroll
-	for (int k = 0; k < S_OUT_F4; k++) o[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-	bool live = false;
-	if (idx < P)
-		live = surfel_preprocess_one<TRAIN>(idx, D, M, means, scales, scale_modifier, rotations, opacities, shs, transMat_precomp, colors_precomp, refl,
-		                             env_scope_mask, cam, radii, g, gx, gy, prefiltered, gaussian_weights, o);
-	if (__ballot(live) == 0ull) return;      // (wave-uniform) nothing of this wave is ever read
-	const int g0 = idx - lane;               // first Gaussian of the wave
-	const int ng = min(64, P - g0);
-	wave_store_rows4<S_REC_F4, false>(so, o, g.rec + (size_t)g0 * S_REC_F4, S_REC_F4, 0, ng, lane);
-	wave_store_rows4<2, false>(so, o + S_REC_F4, g.bbox + (size_t)g0 * 2, 2, 0, ng, lane);
+			for (int k = 0; k < S_OUT_F4; k++) o[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+			bool live = false;
+			if (idx < P)
+				live = surfel_preprocess_one<TRAIN>(in, c, idx, scale_modifier, PLAIN ? nullptr : transMat_precomp, PLAIN ? nullptr : colors_precomp,
+				                                    env_scope_mask, cam, radii, g, gx, gy, prefiltered, gaussian_weights, o);
+			if (__ballot(live) == 0ull) return;      // (wave-uniform) nothing of this wave is ever read
+			const int g0 = idx - lane;               // first Gaussian of the wave
+			const int ng = min(64, P - g0);
+			wave_store_rows4<S_REC_F4, false>(so, o, g.rec + (size_t)g0 * S_REC_F4, S_REC_F4, 0, ng, lane);
+			wave_store_rows4<2, false>(so, o + S_REC_F4, g.bbox + (size_t)g0 * 2, 2, 0, ng, lane);
+		});
 }
 
 // Pairs of floats for packed fp32 math (v_pk_*_f32): the k- and l-side (or x- and y-side) of the reference's arithmetic in one register pair.
@@ -1286,9 +1352,13 @@ static int surfel_forward(gsr_alloc_fn alloc, void* alloc_user, int P, int D, in
 			rf = SurfelReflFwd{refl->cam, refl->cubemap, reinterpret_cast<const float4*>(refl->cubemap_rgba), refl->fail_value, (int)refl->L, 6u * refl->L * refl->L,
 			                   refl->out_final, refl->out_refl_color, refl->out_normal_world, refl->sort_keys};
 		}
-	{ StageTimer st_(GSR_STAGE_PREPROCESS, stream); 	surfel_preprocess_kernel<TRAIN><<<(P + 255) / 256, 256, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
-		                                                                     transMat_precomp, colors_precomp, refl_strengths, env_scope_mask, cam, radii, geom,
-		                                                                     tiles_x, tiles_y, prefiltered, gaussian_weights, ci); }
+	{ StageTimer st_(GSR_STAGE_PREPROCESS, stream);
+		const bool plain = shs != nullptr && colors_precomp == nullptr && M == 16 && D == 3 && scales != nullptr && rotations != nullptr &&
+		                   transMat_precomp == nullptr;
+		auto kern = plain ? surfel_preprocess_kernel<TRAIN, true> : surfel_preprocess_kernel<TRAIN, false>;
+		kern<<<pergauss_grid(P, S_PRE_FWD_WGS), PG_BLOCK, 0, stream>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, transMat_precomp,
+		                                                              colors_precomp, refl_strengths, env_scope_mask, cam, radii, geom, tiles_x, tiles_y,
+		                                                              prefiltered, gaussian_weights, ci); }
 		GSR_LAUNCH_CHECK(debug, stream);
 
 		BinningState bin;

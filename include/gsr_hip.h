@@ -264,6 +264,9 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
  * t is batch index ranges[t][0] / 64 + t + b).
  * "pairs" u64[1] reads no workspace (the buffers may be NULL): the running number of (wave, list entry) pairs the forward tile kernels have
  * evaluated on the current device while the "dev" option had bit 2 set (gsr_set_option); it is never reset, so take differences.
+ * "pergauss_grid" u32[4] reads no workspace either: the workgroups (of 256 Gaussians a trip) that the per-Gaussian forward and backward
+ * pass of `variant` launch for P Gaussians on the current device, then the resident workgroup slots each of them is sized for (0: the
+ * pass launches one workgroup per batch).  With more batches than slots a workgroup walks several batches.
  * GSR_E_INVALID: a variant other than 0 / 1, a NULL or unknown name, P < 0, R < 0, width or height <= 0, and a NULL dst or a NULL buffer
  * of the workspace the named array lives in ("keys": binning and geometry) whenever the call copies something out of it (a per-Gaussian
  * array with P == 0 and a per-instance array with R == 0 copy nothing). */
