@@ -184,6 +184,11 @@ ABI = [
         ("gsr_mesh_clean_count", I, [P, U64, U64, U64, U64, P, P, P, c_size_t, P, P]),
         ("gsr_mesh_clean_scratch_bytes", c_size_t, [U64, U64]),
         ("gsr_mesh_clean_emit", I, [P, P, P, U64, U64, P, P, P, P, U64, U64, P])]),
+    # TSDF fusion on a lattice in contracted space, per-vertex colours, un-contraction: gsr_mesh.ContractedTSDFVolume, color_vertices
+    ("gsr_hip_unbounded.h", "csrc/gsr_unbounded.hip", True, [
+        ("gsr_tsdf_integrate_contracted", I, [P, P, I, F, F, F, F, F, F, F, P, I, I, P, P, P]),
+        ("gsr_points_fuse_view", I, [P, U64, P, P, P, P, I, I, P, P, F, P]),
+        ("gsr_uncontract_points", I, [P, P, U64, F, F, F, F, F, P])]),
 ]
 
 ENTRIES_BY_HEADER = {}          # {header file name: [entry names]}, what tests/test_cabi.py holds each header to

@@ -6,6 +6,9 @@ voxel grid, `TSDFVolume.extract` pulls the iso-surface out as an indexed triangl
 it.  Everything stays on the device; the one read-back is the 16 bytes that hold the vertex and triangle counts.  The reference took
 this from open3d (ScalableTSDFVolume) on the host; utils/mesh_utils.py has its GaussianExtractor on top of this module.
 
+`ContractedTSDFVolume` is the same for scenes that do not end at a box (include/gsr_hip_unbounded.h, csrc/gsr_unbounded.hip): the lattice
+lies in contracted space, `extract` maps the vertices back to the world, and `color_vertices` colours them from the views afterwards.
+
 `clean_mesh` is the step upstream runs on that mesh before writing it: the connected triangle clusters are labelled, the largest kept,
 the small ones and the vertices nobody references any more dropped; `cluster_connected_triangles` gives the labels alone.  Its one
 read-back is the 48 bytes of its six counts.
@@ -23,6 +26,43 @@ _gsr.require_entry(lib, "gsr_tsdf_integrate")
 Mesh = collections.namedtuple("Mesh", "vertices faces colors")     # float32 [nV, 3], int32 [nT, 3], float32 [nV, 3] or None: device tensors
 MAX_NODES = 2 ** 31 - 1
 CleanInfo = collections.namedtuple("CleanInfo", "vertices faces components kept_components threshold ignored_faces")     # the six counts of gsr_mesh_clean_count
+
+
+def _view_inputs(who, owner, camera, device, **maps):
+    """(W, H, view, proj, {name: map}) of one view for the entries that sample it: every map that is given float32 and contiguous,
+    [channels, H, W] (or [H, W] for one channel), on `device` like the two matrices.  maps: name=(tensor or None, channels); `owner` is
+    what lives on `device`, for the message."""
+    H, W = int(camera.image_height), int(camera.image_width)
+    out = {}
+    for name, (t, channels) in maps.items():
+        if t is not None:
+            t = f32c(t, name)
+            if not (tuple(t.shape) == (channels, H, W) or (channels == 1 and tuple(t.shape) == (H, W))):
+                raise ValueError(f"{who}: {name} must be [{channels}, {H}, {W}] (got {tuple(t.shape)})")
+        out[name] = t
+    view, proj = f32c(camera.world_view_transform, "world_view_transform"), f32c(camera.full_proj_transform, "full_proj_transform")
+    for name, t in list(out.items()) + [("world_view_transform", view), ("full_proj_transform", proj)]:
+        if t is not None and t.device != device:
+            raise ValueError(f"{who}: {name} is on {t.device}, {owner} on {device}")
+    return W, H, view, proj, out
+
+
+def _iso_surface(tsdf, weight, color, dims, origin, voxel, min_weight, dev):
+    """gsr_mesh_count and gsr_mesh_emit over the planes of a volume, on the current stream of `dev`: Mesh(vertices, faces, colors | None).
+    Waits once, for the two counts."""
+    nx, ny, nz = dims
+    scratch = torch.empty(int(lib.gsr_mesh_scratch_bytes(nx, ny, nz)), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.gsr_mesh_count(ptr(tsdf), ptr(weight), nx, ny, nz, float(min_weight), ptr(scratch), scratch.numel(), ptr(counts), stream_ptr(dev)),
+              "gsr_mesh_count")
+        nV, nT = (int(c) for c in counts.tolist())
+        verts = torch.empty((nV, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nT, 3), dtype=torch.int32, device=dev)
+        colors = None if color is None else torch.empty((nV, 3), dtype=torch.float32, device=dev)
+        check(lib.gsr_mesh_emit(ptr(tsdf), ptr(weight), ptr(color), nx, ny, nz, *origin, voxel, float(min_weight), ptr(scratch), ptr(verts), ptr(colors),
+                                ptr(faces), nV, nT, stream_ptr(dev)), "gsr_mesh_emit")
+    return Mesh(verts, faces, colors)
 
 
 class TSDFVolume:
@@ -58,24 +98,11 @@ class TSDFVolume:
         if depth_trunc is None:
             raise ValueError("TSDFVolume.integrate: depth_trunc is required")
         sdf_trunc = 5.0 * self.voxel_size if sdf_trunc is None else float(sdf_trunc)
-        H, W = int(camera.image_height), int(camera.image_width)
-
-        def plane(t, name, channels):
-            t = f32c(t, name)
-            if tuple(t.shape) == (H, W) and channels == 1:
-                return t
-            if tuple(t.shape) != (channels, H, W):
-                raise ValueError(f"TSDFVolume.integrate: {name} must be [{channels}, {H}, {W}] (got {tuple(t.shape)})")
-            return t
-        depth = plane(depth, "depth", 1)
         if (rgb is None) != (self.color is None):
             raise ValueError("TSDFVolume.integrate: rgb is given exactly when the volume holds colour")
-        rgb = None if rgb is None else plane(rgb, "rgb", 3)
-        alpha = None if alpha is None else plane(alpha, "alpha", 1)
-        view, proj = f32c(camera.world_view_transform, "world_view_transform"), f32c(camera.full_proj_transform, "full_proj_transform")
-        for t, name in ((depth, "depth"), (rgb, "rgb"), (alpha, "alpha"), (view, "world_view_transform"), (proj, "full_proj_transform")):
-            if t is not None and t.device != self.tsdf.device:
-                raise ValueError(f"TSDFVolume.integrate: {name} is on {t.device}, the volume on {self.tsdf.device}")
+        W, H, view, proj, maps = _view_inputs("TSDFVolume.integrate", "the volume", camera, self.tsdf.device, depth=(depth, 1), rgb=(rgb, 3),
+                                              alpha=(alpha, 1))
+        depth, rgb, alpha = maps["depth"], maps["rgb"], maps["alpha"]
         nx, ny, nz = self.dims
         with torch.cuda.device(self.device):
             check(lib.gsr_tsdf_integrate(ptr(self.tsdf), ptr(self.weight), ptr(self.color), nx, ny, nz, *self.origin, self.voxel_size, ptr(depth),
@@ -85,20 +112,78 @@ class TSDFVolume:
     def extract(self, min_weight=1.0):
         """The iso-surface tsdf = 0 over the cells whose eight nodes have weight >= min_weight, as Mesh(vertices, faces, colors) on the
         device; an empty surface gives empty tensors.  Waits once, for the two counts."""
-        nx, ny, nz = self.dims
-        dev = self.device
-        scratch = torch.empty(int(lib.gsr_mesh_scratch_bytes(nx, ny, nz)), dtype=torch.uint8, device=dev)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        return _iso_surface(self.tsdf, self.weight, self.color, self.dims, self.origin, self.voxel_size, min_weight, self.device)
+
+
+class ContractedTSDFVolume:
+    """A cubic lattice of resolution^3 nodes in CONTRACTED space (include/gsr_hip_unbounded.h) about the world sphere (center, radius): node
+    (i, j, k) sits at the contracted coordinate -extent + step * (i, j, k), step = 2 extent / (resolution - 1); the unit ball is the
+    sphere itself and the shell 1 <= |y| < 2 holds everything beyond it.  Planes tsdf and weight, float32 [n, n, n] on `device`, both 1
+    when fresh: an unseen node is free space.  The truncation is five voxels of 2 radius / resolution inside the ball and grows with
+    the distance beyond it.  There are no colour planes: color_vertices colours the extracted vertices."""
+
+    def __init__(self, center, radius, resolution, extent, device):
+        self.center = tuple(float(c) for c in center)
+        self.radius, self.resolution, self.extent = float(radius), int(resolution), float(extent)
+        if len(self.center) != 3 or not all(np.isfinite(c) for c in self.center):
+            raise ValueError(f"ContractedTSDFVolume: center has three finite components (got {center})")
+        if not (np.isfinite(self.radius) and self.radius > 0):
+            raise ValueError(f"ContractedTSDFVolume: radius must be positive and finite (got {radius})")
+        if not 0 < self.extent <= 1.9:
+            raise ValueError(f"ContractedTSDFVolume: extent must lie in (0, 1.9] (got {extent})")
+        n = self.resolution
+        if n < 2 or n ** 3 > MAX_NODES:
+            raise ValueError(f"ContractedTSDFVolume: resolution must be at least 2 and resolution^3 below 2^31 (got {resolution})")
+        self.lo, self.step, self.voxel_size = -self.extent, 2.0 * self.extent / (n - 1), 2.0 * self.radius / n
+        self.device = torch.device(device)
+        self.tsdf = torch.ones((n, n, n), dtype=torch.float32, device=self.device)
+        self.weight = torch.ones((n, n, n), dtype=torch.float32, device=self.device)
+
+    def reset(self):
+        self.tsdf.fill_(1.0)
+        self.weight.fill_(1.0)
+
+    def integrate(self, depth, camera):
+        """Fuses one view (gsr_tsdf_integrate_contracted): depth [H, W] or [1, H, W] (render()'s surf_depth), `camera` any object render()
+        accepts.  Runs on the current stream; nothing is read back."""
+        _gsr.require_entry(lib, "gsr_tsdf_integrate_contracted")
+        W, H, view, proj, maps = _view_inputs("ContractedTSDFVolume.integrate", "the volume", camera, self.tsdf.device, depth=(depth, 1))
+        with torch.cuda.device(self.device):
+            check(lib.gsr_tsdf_integrate_contracted(ptr(self.tsdf), ptr(self.weight), self.resolution, self.lo, self.step, *self.center, self.radius,
+                                                    self.voxel_size, ptr(maps["depth"]), W, H, ptr(view), ptr(proj), stream_ptr(self.device)),
+                  "gsr_tsdf_integrate_contracted")
+
+    def extract(self, max_range=32.0):
+        """The iso-surface tsdf = 0 of the lattice (gsr_mesh_count and gsr_mesh_emit with min_weight = 1: every cell), its vertices mapped
+        back to the world and clamped to [-max_range, max_range] per coordinate (gsr_uncontract_points, in place): Mesh(vertices, faces,
+        None) on the device.  Waits once, for the two counts."""
+        _gsr.require_entry(lib, "gsr_uncontract_points")
+        n, dev = self.resolution, self.device
+        mesh = _iso_surface(self.tsdf, self.weight, None, (n, n, n), (self.lo,) * 3, self.step, 1.0, dev)
         with torch.cuda.device(dev):
-            check(lib.gsr_mesh_count(ptr(self.tsdf), ptr(self.weight), nx, ny, nz, float(min_weight), ptr(scratch), scratch.numel(), ptr(counts),
-                                     stream_ptr(dev)), "gsr_mesh_count")
-            nV, nT = (int(c) for c in counts.tolist())
-            verts = torch.empty((nV, 3), dtype=torch.float32, device=dev)
-            faces = torch.empty((nT, 3), dtype=torch.int32, device=dev)
-            colors = None if self.color is None else torch.empty((nV, 3), dtype=torch.float32, device=dev)
-            check(lib.gsr_mesh_emit(ptr(self.tsdf), ptr(self.weight), ptr(self.color), nx, ny, nz, *self.origin, self.voxel_size, float(min_weight),
-                                    ptr(scratch), ptr(verts), ptr(colors), ptr(faces), nV, nT, stream_ptr(dev)), "gsr_mesh_emit")
-        return Mesh(verts, faces, colors)
+            check(lib.gsr_uncontract_points(ptr(mesh.vertices), ptr(mesh.vertices), mesh.vertices.shape[0], *self.center, self.radius, float(max_range),
+                                            stream_ptr(dev)), "gsr_uncontract_points")
+        return mesh
+
+
+def color_vertices(vertices, views, sdf_trunc):
+    """Per-vertex colours of WORLD points [nV, 3] (gsr_points_fuse_view, one launch per view): `views` iterates (camera, depth [H, W] or
+    [1, H, W], rgb [3, H, W]); a vertex gets the mean of the bilinear samples of the views that see it within sdf_trunc of their
+    surface, and stays black where none does.  float32 [nV, 3] on the vertices' device; runs on the current stream, nothing is read
+    back."""
+    _gsr.require_entry(lib, "gsr_points_fuse_view")
+    vertices = f32c(vertices, "vertices")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"color_vertices: vertices must be [nV, 3] (got {tuple(vertices.shape)})")
+    dev, nV = vertices.device, int(vertices.shape[0])
+    color = torch.zeros((nV, 3), dtype=torch.float32, device=dev)
+    weight = torch.zeros(nV, dtype=torch.float32, device=dev)
+    for camera, depth, rgb in views:
+        W, H, view, proj, maps = _view_inputs("color_vertices", "the vertices", camera, dev, depth=(depth, 1), rgb=(rgb, 3))
+        with torch.cuda.device(dev):
+            check(lib.gsr_points_fuse_view(ptr(vertices), nV, ptr(color), ptr(weight), ptr(maps["depth"]), ptr(maps["rgb"]), W, H, ptr(view), ptr(proj),
+                                           float(sdf_trunc), stream_ptr(dev)), "gsr_points_fuse_view")
+    return color
 
 
 def _clean_count(mesh, cluster_to_keep, min_triangles, want_labels):

@@ -2,7 +2,8 @@
 
 The reference kept the constructor, clean() and reconstruction() and dropped the extraction together with its open3d and trimesh
 imports; here the extraction is gsr_mesh.TSDFVolume (csrc/gsr_mesh.hip): the rendered maps stay on the device, the fusion and the
-iso-surface run there, and the mesh comes back as device tensors (gsr_mesh.save_mesh_ply writes it).  post_process_mesh is upstream
+iso-surface run there, and the mesh comes back as device tensors (gsr_mesh.save_mesh_ply writes it).  extract_mesh_unbounded is upstream
+2DGS's method of that name on gsr_mesh.ContractedTSDFVolume and gsr_mesh.color_vertices (csrc/gsr_unbounded.hip).  post_process_mesh is upstream
 2DGS's clean-up of that mesh, on gsr_mesh.clean_mesh (csrc/gsr_meshclean.hip).  export_image is not provided: it needs the reference's
 utils/render_utils.
 """
@@ -99,3 +100,34 @@ class GaussianExtractor:
             volume.integrate(depth, cam, rgb=rgb, alpha=alpha if mask_backgrond else None, alpha_min=0.5, sdf_trunc=sdf_trunc,
                              depth_trunc=depth_trunc)
         return volume.extract()
+
+    def contracted_extent(self, centre, radius):
+        """Half the side of the lattice extract_mesh_unbounded lays out, in contracted units: the 0.95 quantile (linear interpolation
+        between order statistics) of the model's contracted norms about (centre, radius), a norm m counting as m below 1 and as
+        2 - 1 / m beyond, plus 0.01 and at most 1.9.  Torch ops and one host read."""
+        xyz = self.gaussians.get_xyz.detach().to(torch.float32)
+        m = ((xyz - torch.as_tensor([float(c) for c in centre], dtype=torch.float32, device=xyz.device)) / float(radius)).norm(dim=1)
+        if m.numel() == 0:
+            raise ValueError("GaussianExtractor: the model has no Gaussians")
+        g = torch.where(m < 1, m, 2 - 1 / m).sort().values               # (torch.quantile stops at 2^24 elements)
+        at = 0.95 * (g.numel() - 1)
+        below = int(math.floor(at))
+        a, b = g[[below, min(below + 1, g.numel() - 1)]].tolist()
+        return min(a + (b - a) * (at - below) + 0.01, 1.9)
+
+    @torch.no_grad()
+    def extract_mesh_unbounded(self, resolution=1024):
+        """The unbounded TSDF extraction upstream 2DGS calls by this name: every kept view is fused into a lattice of resolution^3 nodes in
+        contracted space (gsr_mesh.ContractedTSDFVolume: the sphere of camera_bounds() is the unit ball, everything beyond it is folded
+        into the shell up to 2), the iso-surface is extracted and mapped back to the world, and the vertices are coloured from the views
+        with the truncation of five voxels.  The lattice reaches as far as contracted_extent() says.  Returns gsr_mesh.Mesh(vertices,
+        faces, colors) on the device.  include/gsr_hip_unbounded.h states where this differs from upstream."""
+        if not self.depthmaps:
+            raise ValueError("GaussianExtractor.extract_mesh_unbounded: call reconstruction() first")
+        centre, radius = self.camera_bounds()
+        volume = gsr_mesh.ContractedTSDFVolume(centre, radius, resolution, self.contracted_extent(centre, radius), self.depthmaps[0].device)
+        for cam, depth in zip(self.viewpoint_stack, self.depthmaps):
+            volume.integrate(depth, cam)
+        mesh = volume.extract()
+        colors = gsr_mesh.color_vertices(mesh.vertices, zip(self.viewpoint_stack, self.depthmaps, self.rgbmaps), 5.0 * volume.voxel_size)
+        return gsr_mesh.Mesh(mesh.vertices, mesh.faces, colors)
