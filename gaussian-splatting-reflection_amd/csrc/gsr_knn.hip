@@ -16,6 +16,7 @@
 // any pair of points the boxes contain.  So a box is pruned (strict >) only if none of its points can beat a current b2; ties do
 // not change the multiset of the three smallest distances.  The result is (b0 + b1 + b2) / 3 of that multiset, summed in ascending
 // order, and so does not depend on the input order bit for bit.  Missing neighbours (P < 4) stay at FLT_MAX.
+// Host side: the caller's scratch is KnnLayout, typed pointers carved by knn_carve on Carver (a NULL base answers gsr_knn_scratch_bytes).
 #include "gsr_internal.hpp"
 #include <algorithm>
 #include <cfloat>
@@ -252,28 +253,31 @@ __global__ void __launch_bounds__(256) knn_search_kernel(KnnTree t, float* __res
 
 // ------------------------------------------------------------------ scratch layout (one caller-provided buffer)
 struct KnnLayout {
-	size_t keys, keys_sorted, order, sorted, partial, lo[KNN_LEVELS], hi[KNN_LEVELS], sort_temp, sort_bytes, total;
-	int n[KNN_LEVELS];
+	uint32_t *keys, *keys_sorted, *order;     // P each   Morton keys, the same sorted, the original index at each sorted position
+	float4* sorted;                           // P        the points in Morton order, w = original index
+	float4* partial;                          // 2 * KNN_BOUNDS_BLOCKS   partial AABBs: lo, hi
+	float4 *lo[KNN_LEVELS], *hi[KNN_LEVELS];  // n[k]     boxes of level k
+	char* sort_temp;                          // sort_bytes
+	size_t sort_bytes, bytes;
+	int n[KNN_LEVELS];                  // boxes per level
 };
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-static KnnLayout knn_layout(size_t P) {
+static KnnLayout knn_carve(void* base, size_t P) {
+	Carver c(base);
 	KnnLayout l;
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
 	l.n[0] = (int)((P + KNN_LEAF - 1) / KNN_LEAF);
 	for (int k = 1; k < KNN_LEVELS; k++) l.n[k] = (l.n[k - 1] + 63) / 64;
-	l.keys = take(P * 4);
-	l.keys_sorted = take(P * 4);
-	l.order = take(P * 4);
-	l.sorted = take(P * 16);
-	l.partial = take(2 * KNN_BOUNDS_BLOCKS * 16);
+	l.keys = c.take<uint32_t>(P);
+	l.keys_sorted = c.take<uint32_t>(P);
+	l.order = c.take<uint32_t>(P);
+	l.sorted = c.take<float4>(P);
+	l.partial = c.take<float4>(2 * KNN_BOUNDS_BLOCKS);
 	for (int k = 0; k < KNN_LEVELS; k++) {
-		l.lo[k] = take((size_t)l.n[k] * 16);
-		l.hi[k] = take((size_t)l.n[k] * 16);
+		l.lo[k] = c.take<float4>(l.n[k]);
+		l.hi[k] = c.take<float4>(l.n[k]);
 	}
 	l.sort_bytes = KnnSort::temp_bytes((const uint32_t*)nullptr, rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr, P, KNN_MORTON_BITS);
-	l.sort_temp = take(l.sort_bytes);
-	l.total = o;
+	l.sort_temp = c.take<char>(l.sort_bytes);
+	l.bytes = c.size();
 	return l;
 }
 
@@ -283,7 +287,7 @@ using namespace gsr;
 
 extern "C" size_t gsr_knn_scratch_bytes(int P) {
 	if (P <= 0 || (size_t)P >= KNN_MAX_POINTS) return 0;
-	return knn_layout((size_t)P).total;
+	return knn_carve(nullptr, (size_t)P).bytes;
 }
 
 extern "C" int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, void* scratch, size_t scratch_bytes, void* stream_) {
@@ -291,39 +295,31 @@ extern "C" int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, v
 	if (P < 0 || (size_t)P >= KNN_MAX_POINTS) { set_error("gsr_knn_mean_dist: P = %d outside [0, 2^30)", P); return GSR_E_INVALID; }
 	if (P == 0) return 0;
 	if (!points || !mean_dist || !scratch) { set_error("gsr_knn_mean_dist: NULL buffer"); return GSR_E_INVALID; }
-	const KnnLayout l = knn_layout((size_t)P);
-	if (scratch_bytes < l.total) {
-		set_error("gsr_knn_mean_dist: scratch of %zu bytes, %zu needed (gsr_knn_scratch_bytes)", scratch_bytes, l.total);
+	const KnnLayout l = knn_carve(scratch, (size_t)P);
+	if (scratch_bytes < l.bytes) {
+		set_error("gsr_knn_mean_dist: scratch of %zu bytes, %zu needed (gsr_knn_scratch_bytes)", scratch_bytes, l.bytes);
 		return GSR_E_INVALID;
 	}
 	GSR_REQUIRE_ALIGNED16_IN("gsr_knn_mean_dist", scratch, "scratch");   // (it is carved into float4 arrays)
-	char* base = static_cast<char*>(scratch);
-	uint32_t* keys = reinterpret_cast<uint32_t*>(base + l.keys);
-	uint32_t* keys_sorted = reinterpret_cast<uint32_t*>(base + l.keys_sorted);
-	uint32_t* order = reinterpret_cast<uint32_t*>(base + l.order);
-	float4* sorted = reinterpret_cast<float4*>(base + l.sorted);
-	float4* partial = reinterpret_cast<float4*>(base + l.partial);
 	KnnTree t;
-	t.pts = sorted;
+	t.pts = l.sorted;
 	t.P = P;
 	for (int k = 0; k < KNN_LEVELS; k++) {
-		t.lo[k] = reinterpret_cast<const float4*>(base + l.lo[k]);
-		t.hi[k] = reinterpret_cast<const float4*>(base + l.hi[k]);
+		t.lo[k] = l.lo[k];
+		t.hi[k] = l.hi[k];
 		t.n[k] = l.n[k];
 	}
 	const int n_partial = (int)std::min<size_t>(KNN_BOUNDS_BLOCKS, ((size_t)P + 256 * 16 - 1) / (256 * 16));
-	knn_bounds_kernel<<<n_partial, 256, 0, stream>>>(P, points, partial);
+	knn_bounds_kernel<<<n_partial, 256, 0, stream>>>(P, points, l.partial);
 	GSR_LAUNCH_CHECK(0, stream);
 	const unsigned blocks = (unsigned)(((size_t)P + 255) / 256);
-	knn_morton_kernel<<<blocks, 256, 0, stream>>>(P, n_partial, points, partial, keys);
+	knn_morton_kernel<<<blocks, 256, 0, stream>>>(P, n_partial, points, l.partial, l.keys);
 	GSR_LAUNCH_CHECK(0, stream);
-	GSR_HIP_CHECK(KnnSort::pairs(base + l.sort_temp, l.sort_bytes, keys, keys_sorted, rocprim::counting_iterator<uint32_t>(0), order, (size_t)P, KNN_MORTON_BITS, stream));
-	knn_gather_leaves_kernel<<<blocks, 256, 0, stream>>>(P, points, order, sorted, reinterpret_cast<float4*>(base + l.lo[0]),
-	                                                     reinterpret_cast<float4*>(base + l.hi[0]));
+	GSR_HIP_CHECK(KnnSort::pairs(l.sort_temp, l.sort_bytes, l.keys, l.keys_sorted, rocprim::counting_iterator<uint32_t>(0), l.order, (size_t)P, KNN_MORTON_BITS, stream));
+	knn_gather_leaves_kernel<<<blocks, 256, 0, stream>>>(P, points, l.order, l.sorted, l.lo[0], l.hi[0]);
 	GSR_LAUNCH_CHECK(0, stream);
 	for (int k = 1; k < KNN_LEVELS; k++) {
-		knn_parent_boxes_kernel<<<(unsigned)(((size_t)l.n[k - 1] + 255) / 256), 256, 0, stream>>>(
-		    l.n[k - 1], t.lo[k - 1], t.hi[k - 1], reinterpret_cast<float4*>(base + l.lo[k]), reinterpret_cast<float4*>(base + l.hi[k]));
+		knn_parent_boxes_kernel<<<(unsigned)(((size_t)l.n[k - 1] + 255) / 256), 256, 0, stream>>>(l.n[k - 1], l.lo[k - 1], l.hi[k - 1], l.lo[k], l.hi[k]);
 		GSR_LAUNCH_CHECK(0, stream);
 	}
 	knn_search_kernel<<<(unsigned)((l.n[0] + 3) / 4), 256, 0, stream>>>(t, mean_dist);

@@ -16,10 +16,11 @@
 //   offsets     node -> exclusive vertex and triangle offsets (block scan + the block's base)
 //   emit        node -> its vertices, and its cell's triangles with the vertex indices looked up at the cell's corners
 // Offsets are 32-bit: they are exact whenever the totals are below 2^31, and gsr_mesh_emit refuses larger ones.
-#include <cmath>
-#include <initializer_list>
-#include "gsr_internal.hpp"
+// Host side: the checks that are not specific to an entry are gsr_host.hpp's; the scratch is MeshScratch, typed pointers carved by
+// mesh_carve (a NULL base answers gsr_mesh_scratch_bytes).  The view's matrix rows and dot products are gsr_view.hpp's.
+#include "gsr_host.hpp"
 #include "gsr_scan.hpp"
+#include "gsr_view.hpp"
 #include "../../include/gsr_hip_mesh.h"
 
 namespace gsr {
@@ -39,14 +40,7 @@ struct TsdfArgs {
 
 __global__ void __launch_bounds__(64 * TSDF_ROWS)
 tsdf_integrate_kernel(const TsdfArgs a) {
-	float V[4], P[12];            // the rows of the two matrices the kernel needs: view z; projection x, y, w
-#pragma unroll
-	for (int c = 0; c < 4; c++) {
-		V[c] = a.view[4 * c + 2];
-		P[c] = a.proj[4 * c];
-		P[4 + c] = a.proj[4 * c + 1];
-		P[8 + c] = a.proj[4 * c + 3];
-	}
+	const ViewRows r(a.view, a.proj);
 	const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
 	const size_t plane = (size_t)a.nx * a.ny, vol = plane * a.nz;
 	for (uint32_t b = blockIdx.x; b < a.nblocks; b += gridDim.x) {
@@ -58,19 +52,15 @@ tsdf_integrate_kernel(const TsdfArgs a) {
 		const int k1 = min(k0 + TSDF_KZ, a.nz);
 		if (i >= a.nx) continue;
 		const float X = fmaf(a.voxel, (float)i, a.ox), Y = fmaf(a.voxel, (float)j, a.oy);
-		// the part of the four dot products that does not change along z
-		const float zxy = fmaf(V[0], X, fmaf(V[1], Y, V[3]));
-		const float xxy = fmaf(P[0], X, fmaf(P[1], Y, P[3]));
-		const float yxy = fmaf(P[4], X, fmaf(P[5], Y, P[7]));
-		const float wxy = fmaf(P[8], X, fmaf(P[9], Y, P[11]));
+		const ViewDots xy = r.xy(X, Y);                                // the part of the four dot products that does not change along z
 		size_t node = (size_t)k0 * plane + (size_t)j * a.nx + i;       // < 2^31
 #pragma unroll 2
 		for (int k = k0; k < k1; k++, node += plane) {
 			const float Z = fmaf(a.voxel, (float)k, a.oz);
-			const float z = fmaf(V[2], Z, zxy), pw = fmaf(P[10], Z, wxy);
+			const float z = r.z(xy, Z), pw = r.w(xy, Z);
 			if (!(z > 0.f && pw > 0.f)) continue;
-			const float fx = ((fmaf(P[2], Z, xxy) / pw + 1.f) * (float)a.W - 1.f) * 0.5f;
-			const float fy = ((fmaf(P[6], Z, yxy) / pw + 1.f) * (float)a.H - 1.f) * 0.5f;
+			const float fx = ((r.x(xy, Z) / pw + 1.f) * (float)a.W - 1.f) * 0.5f;
+			const float fy = ((r.y(xy, Z) / pw + 1.f) * (float)a.H - 1.f) * 0.5f;
 			const float ru = rintf(fx), rv = rintf(fy);
 			if (!(ru >= 0.f && ru < (float)a.W && rv >= 0.f && rv < (float)a.H)) continue;      // (NaN: skipped)
 			const size_t pix = (size_t)(int)rv * a.W + (int)ru;
@@ -98,25 +88,32 @@ tsdf_integrate_kernel(const TsdfArgs a) {
 #define NODE_INSIDE 2u
 #define CELL_VALID 0x80u          // bit 7 of a node's vertex mask: the cell whose low corner it is is valid
 
-// scratch of gsr_mesh_count, shared with gsr_mesh_emit: offsets in bytes, each a multiple of 256
+// scratch of gsr_mesh_count, shared with gsr_mesh_emit (which only reads it): N nodes in `nblocks` blocks
 struct MeshScratch {
-	size_t cls, vmask, tcnt, vert_off, tri_off, part, vbase, tbase, bytes;
+	uint8_t* cls;          // N        node class
+	uint8_t* vmask;        // N        vertex mask | CELL_VALID
+	uint8_t* tcnt;         // N        triangles of the node's cell (0..12)
+	uint32_t* vert_off;    // N        exclusive vertex offset of the node
+	uint32_t* tri_off;     // N        exclusive triangle offset of the node's cell
+	uint32_t* part;        // nblocks  block sums: vertices | triangles << 16
+	uint32_t* vbase;       // nblocks  vertices in front of the block
+	uint32_t* tbase;       // nblocks  triangles in front of the block
+	size_t bytes;
 	uint32_t nblocks;
 };
-static MeshScratch mesh_scratch(uint64_t N) {
+static MeshScratch mesh_carve(void* base, uint64_t N) {
+	Carver c(base);
 	MeshScratch s;
 	s.nblocks = (uint32_t)((N + MESH_BLOCK - 1) / MESH_BLOCK);
-	size_t off = 0;
-	auto take = [&](size_t bytes) { size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
-	s.cls = take(N);                       // uint8  node class
-	s.vmask = take(N);                     // uint8  vertex mask | CELL_VALID
-	s.tcnt = take(N);                      // uint8  triangles of the node's cell (0..12)
-	s.vert_off = take(4 * N);              // uint32 exclusive vertex offset of the node
-	s.tri_off = take(4 * N);               // uint32 exclusive triangle offset of the node's cell
-	s.part = take(4 * (size_t)s.nblocks);  // uint32 block sums: vertices | triangles << 16
-	s.vbase = take(4 * (size_t)s.nblocks); // uint32 vertices in front of the block
-	s.tbase = take(4 * (size_t)s.nblocks); // uint32 triangles in front of the block
-	s.bytes = off;
+	s.cls = c.take<uint8_t>(N);
+	s.vmask = c.take<uint8_t>(N);
+	s.tcnt = c.take<uint8_t>(N);
+	s.vert_off = c.take<uint32_t>(N);
+	s.tri_off = c.take<uint32_t>(N);
+	s.part = c.take<uint32_t>(s.nblocks);
+	s.vbase = c.take<uint32_t>(s.nblocks);
+	s.tbase = c.take<uint32_t>(s.nblocks);
+	s.bytes = c.size();
 	return s;
 }
 
@@ -331,29 +328,19 @@ mesh_emit_kernel(const EmitArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-static inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-static inline bool positive_finite(float v) { return std::isfinite(v) && v > 0.f; }
-
-// The volume's size limits.  Returns 0 and the node count, or GSR_E_INVALID with the message set.
-static int volume_check(const char* entry, int nx, int ny, int nz, uint64_t* N) {
-	if (nx < 2 || ny < 2 || nz < 2) {
-		set_error("%s: every dimension of the volume must be at least 2 (got %d x %d x %d)", entry, nx, ny, nz);
-		return GSR_E_INVALID;
-	}
-	const uint64_t limit = (uint64_t)1 << 31;
+// The volume's size limits: the node count of a volume the entries take (every dimension at least 2, nx * ny * nz below 2^31), else 0.
+static uint64_t volume_nodes(int nx, int ny, int nz) {
+	if (nx < 2 || ny < 2 || nz < 2) return 0;
 	const uint64_t xy = (uint64_t)nx * (uint64_t)ny;               // < 2^62
-	if (xy >= limit || xy * (uint64_t)nz >= limit) {
-		set_error("%s: nx * ny * nz must be below 2^31 (got %d x %d x %d)", entry, nx, ny, nz);
-		return GSR_E_INVALID;
-	}
-	*N = xy * (uint64_t)nz;
-	return 0;
+	return xy < LIMIT_2_31 && xy * (uint64_t)nz < LIMIT_2_31 ? xy * (uint64_t)nz : 0;
 }
-
-static int grid_check(const char* entry, float ox, float oy, float oz, float voxel) {
-	if (!positive_finite(voxel)) { set_error("%s: voxel must be positive and finite (got %g)", entry, (double)voxel); return GSR_E_INVALID; }
-	if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz)) { set_error("%s: the origin is not finite", entry); return GSR_E_INVALID; }
-	return 0;
+// Returns 0 and the node count, or GSR_E_INVALID with the message set.
+static int volume_check(const char* entry, int nx, int ny, int nz, uint64_t* N) {
+	*N = volume_nodes(nx, ny, nz);
+	if (*N) return 0;
+	if (nx < 2 || ny < 2 || nz < 2) set_error("%s: every dimension of the volume must be at least 2 (got %d x %d x %d)", entry, nx, ny, nz);
+	else set_error("%s: nx * ny * nz must be below 2^31 (got %d x %d x %d)", entry, nx, ny, nz);
+	return GSR_E_INVALID;
 }
 
 }  // namespace gsr
@@ -367,16 +354,11 @@ extern "C" int gsr_tsdf_integrate(float* tsdf, float* weight, float* color, int 
 	hipStream_t stream = (hipStream_t)stream_;
 	if (!tsdf || !weight || !depth || !viewmatrix || !projmatrix) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
 	if ((color != nullptr) != (rgb != nullptr)) { set_error("%s: color and rgb must both be given or both be NULL", entry); return GSR_E_INVALID; }
-	for (const void* p : {(const void*)tsdf, (const void*)weight, (const void*)color, (const void*)depth, (const void*)rgb, (const void*)alpha,
-	                      (const void*)viewmatrix, (const void*)projmatrix})
-		if (misaligned(p, 4)) { set_error("%s: pointers must be 4-byte aligned (got %p)", entry, p); return GSR_E_INVALID; }
+	if (int rc = pointers_check(entry, {tsdf, weight, color, depth, rgb, alpha, viewmatrix, projmatrix})) return rc;
 	uint64_t N;
 	if (int rc = volume_check(entry, nx, ny, nz, &N)) return rc;
-	if (int rc = grid_check(entry, ox, oy, oz, voxel)) return rc;
-	if (W < 1 || H < 1 || (uint64_t)W * (uint64_t)H >= ((uint64_t)1 << 31)) {
-		set_error("%s: invalid image size %d x %d", entry, W, H);
-		return GSR_E_INVALID;
-	}
+	if (int rc = placement_check(entry, "voxel", voxel, "origin", ox, oy, oz)) return rc;
+	if (int rc = image_check(entry, W, H)) return rc;
 	if (!positive_finite(sdf_trunc) || !positive_finite(depth_trunc)) {
 		set_error("%s: sdf_trunc and depth_trunc must be positive and finite (got %g, %g)", entry, (double)sdf_trunc, (double)depth_trunc);
 		return GSR_E_INVALID;
@@ -399,10 +381,8 @@ extern "C" int gsr_tsdf_integrate(float* tsdf, float* weight, float* color, int 
 }
 
 extern "C" size_t gsr_mesh_scratch_bytes(int nx, int ny, int nz) {
-	if (nx < 2 || ny < 2 || nz < 2) return 0;
-	const uint64_t limit = (uint64_t)1 << 31, xy = (uint64_t)nx * (uint64_t)ny;
-	if (xy >= limit || xy * (uint64_t)nz >= limit) return 0;
-	return mesh_scratch(xy * (uint64_t)nz).bytes;
+	const uint64_t N = volume_nodes(nx, ny, nz);
+	return N ? mesh_carve(nullptr, N).bytes : 0;
 }
 
 extern "C" int gsr_mesh_count(const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, void* scratch, size_t scratch_bytes,
@@ -410,32 +390,25 @@ extern "C" int gsr_mesh_count(const float* tsdf, const float* weight, int nx, in
 	const char* entry = "gsr_mesh_count";
 	hipStream_t stream = (hipStream_t)stream_;
 	if (!tsdf || !weight || !scratch || !counts) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
-	if (misaligned(tsdf, 4) || misaligned(weight, 4)) { set_error("%s: tsdf and weight must be 4-byte aligned", entry); return GSR_E_INVALID; }
-	if (misaligned(scratch, 16)) { set_error("%s: scratch must be 16-byte aligned (got %p)", entry, scratch); return GSR_E_INVALID; }
-	if (misaligned(counts, 8)) { set_error("%s: counts must be 8-byte aligned (got %p)", entry, (void*)counts); return GSR_E_INVALID; }
+	if (int rc = pointers_check(entry, {tsdf, weight})) return rc;
+	if (int rc = aligned_check(entry, "scratch", scratch, 16)) return rc;
+	if (int rc = aligned_check(entry, "counts", counts, 8)) return rc;
 	uint64_t N64;
 	if (int rc = volume_check(entry, nx, ny, nz, &N64)) return rc;
 	if (std::isnan(min_weight)) { set_error("%s: min_weight is NaN", entry); return GSR_E_INVALID; }
-	const MeshScratch s = mesh_scratch(N64);
+	const MeshScratch s = mesh_carve(scratch, N64);
 	if (scratch_bytes < s.bytes) {
 		set_error("%s: scratch of %zu bytes, gsr_mesh_scratch_bytes(%d, %d, %d) = %zu", entry, scratch_bytes, nx, ny, nz, s.bytes);
 		return GSR_E_INVALID;
 	}
-	char* base = (char*)scratch;
 	const uint32_t N = (uint32_t)N64;
-	uint8_t* cls = (uint8_t*)(base + s.cls);
-	uint8_t* vmask = (uint8_t*)(base + s.vmask);
-	uint8_t* tcnt = (uint8_t*)(base + s.tcnt);
-	uint32_t* part = (uint32_t*)(base + s.part);
-	uint32_t* vbase = (uint32_t*)(base + s.vbase);
-	uint32_t* tbase = (uint32_t*)(base + s.tbase);
-	mesh_classify_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(tsdf, weight, N, min_weight, cls);
+	mesh_classify_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(tsdf, weight, N, min_weight, s.cls);
 	GSR_LAUNCH_CHECK(0, stream);
-	mesh_count_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(cls, N, nx, ny, nz, vmask, tcnt, part);
+	mesh_count_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(s.cls, N, nx, ny, nz, s.vmask, s.tcnt, s.part);
 	GSR_LAUNCH_CHECK(0, stream);
-	scan_spine_kernel<<<1, 1024, 0, stream>>>(part, s.nblocks, vbase, tbase, (unsigned long long*)counts);
+	scan_spine_kernel<<<1, 1024, 0, stream>>>(s.part, s.nblocks, s.vbase, s.tbase, (unsigned long long*)counts);
 	GSR_LAUNCH_CHECK(0, stream);
-	mesh_offsets_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(vmask, tcnt, N, vbase, tbase, (uint32_t*)(base + s.vert_off), (uint32_t*)(base + s.tri_off));
+	mesh_offsets_kernel<<<s.nblocks, MESH_BLOCK, 0, stream>>>(s.vmask, s.tcnt, N, s.vbase, s.tbase, s.vert_off, s.tri_off);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
@@ -447,28 +420,22 @@ extern "C" int gsr_mesh_emit(const float* tsdf, const float* weight, const float
 	hipStream_t stream = (hipStream_t)stream_;
 	(void)min_weight;             // the classification is the one gsr_mesh_count left in the scratch
 	if (!tsdf || !weight || !scratch) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
-	for (const void* p : {(const void*)tsdf, (const void*)weight, (const void*)color, (const void*)verts, (const void*)vcolor, (const void*)faces})
-		if (misaligned(p, 4)) { set_error("%s: pointers must be 4-byte aligned (got %p)", entry, p); return GSR_E_INVALID; }
-	if (misaligned(scratch, 16)) { set_error("%s: scratch must be 16-byte aligned (got %p)", entry, scratch); return GSR_E_INVALID; }
+	if (int rc = pointers_check(entry, {tsdf, weight, color, verts, vcolor, faces})) return rc;
+	if (int rc = aligned_check(entry, "scratch", scratch, 16)) return rc;
 	uint64_t N64;
 	if (int rc = volume_check(entry, nx, ny, nz, &N64)) return rc;
-	if (int rc = grid_check(entry, ox, oy, oz, voxel)) return rc;
-	const uint64_t limit = (uint64_t)1 << 31;
-	if (nV >= limit || nT >= limit || 3 * nT >= limit) {
+	if (int rc = placement_check(entry, "voxel", voxel, "origin", ox, oy, oz)) return rc;
+	if (nV >= LIMIT_2_31 || nT >= LIMIT_2_31 || 3 * nT >= LIMIT_2_31) {
 		set_error("%s: nV and 3 * nT must be below 2^31 (got %llu vertices, %llu triangles)", entry, (unsigned long long)nV, (unsigned long long)nT);
 		return GSR_E_INVALID;
 	}
 	if (nV == 0) return 0;
 	if (!verts || (nT > 0 && !faces)) { set_error("%s: invalid argument (NULL verts or faces)", entry); return GSR_E_INVALID; }
 	if ((color != nullptr) != (vcolor != nullptr)) { set_error("%s: color and vcolor must both be given or both be NULL", entry); return GSR_E_INVALID; }
-	const MeshScratch s = mesh_scratch(N64);
-	const char* base = (const char*)scratch;
+	const MeshScratch s = mesh_carve(const_cast<void*>(scratch), N64);      // (read only: EmitArgs takes the arrays as pointers to const)
 	EmitArgs a;
 	a.tsdf = tsdf; a.color = color;
-	a.cls = (const uint8_t*)(base + s.cls);
-	a.vmask = (const uint8_t*)(base + s.vmask);
-	a.vert_off = (const uint32_t*)(base + s.vert_off);
-	a.tri_off = (const uint32_t*)(base + s.tri_off);
+	a.cls = s.cls; a.vmask = s.vmask; a.vert_off = s.vert_off; a.tri_off = s.tri_off;
 	a.verts = verts; a.vcolor = vcolor; a.faces = faces;
 	a.N = (uint32_t)N64; a.nV = (uint32_t)nV; a.nT = (uint32_t)nT;
 	a.nx = nx; a.ny = ny; a.nz = nz;

@@ -21,8 +21,9 @@
 // EVERY LOOP ENDS WHATEVER ANOTHER WORKGROUP DOES.  All stores to parent[] are the initial parent[v] = v and atomic minima, so every
 // value parent[v] ever holds is <= v, and a load — however stale — returns one of them.  Each loop below names the integer that strictly
 // decreases in it.  There is no compare-and-swap retry and no spin on a value another workgroup writes.
-#include <initializer_list>
-#include "gsr_internal.hpp"
+// Host side: the checks that are not specific to an entry are gsr_host.hpp's; the scratch is CleanScratch, typed pointers carved by
+// clean_carve (a NULL base answers gsr_mesh_clean_scratch_bytes).
+#include "gsr_host.hpp"
 #include "gsr_scan.hpp"
 #include "../../include/gsr_hip_meshclean.h"
 
@@ -32,29 +33,39 @@ namespace gsr {
 #define CLEAN_PASSES 4            // bytes of a size, most significant first
 #define CLEAN_AGG_ROUNDS 4        // labels a wave adds up before its remaining lanes add for themselves
 
-// scratch of gsr_mesh_clean_count, shared with gsr_mesh_clean_emit: offsets in bytes, each a multiple of 256
+// scratch of gsr_mesh_clean_count, shared with gsr_mesh_clean_emit (which only reads it): nV vertices in `vblocks` blocks, nT faces in
+// `tblocks`; nblocks is the larger of the two
 struct CleanScratch {
-	size_t parent, size, vert_off, tri_off, used, keep, hist, part, vbase, tbase, bytes;
+	uint32_t* parent;      // nV       union-find parent; behind `flatten` the label
+	uint32_t* size;        // nV       counted faces of the component, at its root
+	uint32_t* vert_off;    // nV       new row of the vertex
+	uint32_t* tri_off;     // nT       new row of the face
+	uint8_t* used;         // nV       a kept face names the vertex
+	uint8_t* keep;         // nT       the face is kept
+	uint32_t* hist;        // 256 * CLEAN_PASSES  digit counts of the radix select, 256 per pass
+	uint32_t* part;        // nblocks  block sums: used vertices | kept faces << 16; block b has vertices AND faces 256 b ...
+	uint32_t* vbase;       // nblocks  used vertices in front of the block
+	uint32_t* tbase;       // nblocks  kept faces in front of the block
+	size_t bytes;
 	uint32_t vblocks, tblocks, nblocks;
 };
-static CleanScratch clean_scratch(uint64_t nV, uint64_t nT) {
+static CleanScratch clean_carve(void* base, uint64_t nV, uint64_t nT) {
+	Carver c(base);
 	CleanScratch s;
 	s.vblocks = (uint32_t)((nV + CLEAN_BLOCK - 1) / CLEAN_BLOCK);
 	s.tblocks = (uint32_t)((nT + CLEAN_BLOCK - 1) / CLEAN_BLOCK);
 	s.nblocks = s.vblocks > s.tblocks ? s.vblocks : s.tblocks;
-	size_t off = 0;
-	auto take = [&](size_t bytes) { size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
-	s.parent = take(4 * nV);                  // uint32 union-find parent; behind `flatten` the label
-	s.size = take(4 * nV);                    // uint32 counted faces of the component, at its root
-	s.vert_off = take(4 * nV);                // uint32 new row of the vertex
-	s.tri_off = take(4 * nT);                 // uint32 new row of the face
-	s.used = take(nV);                        // uint8  a kept face names the vertex
-	s.keep = take(nT);                        // uint8  the face is kept
-	s.hist = take(4 * 256 * CLEAN_PASSES);    // uint32 digit counts of the radix select, 256 per pass
-	s.part = take(4 * (size_t)s.nblocks);     // uint32 block sums: used vertices | kept faces << 16; block b has vertices AND faces 256 b ...
-	s.vbase = take(4 * (size_t)s.nblocks);    // uint32 used vertices in front of the block
-	s.tbase = take(4 * (size_t)s.nblocks);    // uint32 kept faces in front of the block
-	s.bytes = off;
+	s.parent = c.take<uint32_t>(nV);
+	s.size = c.take<uint32_t>(nV);
+	s.vert_off = c.take<uint32_t>(nV);
+	s.tri_off = c.take<uint32_t>(nT);
+	s.used = c.take<uint8_t>(nV);
+	s.keep = c.take<uint8_t>(nT);
+	s.hist = c.take<uint32_t>(256 * CLEAN_PASSES);
+	s.part = c.take<uint32_t>(s.nblocks);
+	s.vbase = c.take<uint32_t>(s.nblocks);
+	s.tbase = c.take<uint32_t>(s.nblocks);
+	s.bytes = c.size();
 	return s;
 }
 
@@ -340,13 +351,8 @@ clean_emit_kernel(const CleanEmitArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-static inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-
 // nV < 2^31 and 3 nT < 2^31
-static bool clean_sizes_fit(uint64_t nV, uint64_t nT) {
-	const uint64_t limit = (uint64_t)1 << 31;
-	return nV < limit && nT < limit && 3 * nT < limit;
-}
+static bool clean_sizes_fit(uint64_t nV, uint64_t nT) { return nV < LIMIT_2_31 && nT < LIMIT_2_31 && 3 * nT < LIMIT_2_31; }
 static int clean_size_check(const char* entry, uint64_t nV, uint64_t nT) {
 	if (!clean_sizes_fit(nV, nT)) {
 		set_error("%s: nV and 3 * nT must be below 2^31 (got %llu vertices, %llu faces)", entry, (unsigned long long)nV, (unsigned long long)nT);
@@ -361,7 +367,7 @@ using namespace gsr;
 
 extern "C" size_t gsr_mesh_clean_scratch_bytes(uint64_t nV, uint64_t nT) {
 	if (!clean_sizes_fit(nV, nT)) return 0;
-	return clean_scratch(nV, nT).bytes;
+	return clean_carve(nullptr, nV, nT).bytes;
 }
 
 extern "C" int gsr_mesh_clean_count(const int* faces, uint64_t nV64, uint64_t nT64, uint64_t cluster_to_keep, uint64_t min_triangles, int* tri_label,
@@ -370,13 +376,12 @@ extern "C" int gsr_mesh_clean_count(const int* faces, uint64_t nV64, uint64_t nT
 	hipStream_t stream = (hipStream_t)stream_;
 	const bool empty = nV64 == 0 || nT64 == 0;
 	if (!counts_ || (!empty && (!faces || !scratch))) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
-	for (const void* p : {(const void*)faces, (const void*)tri_label, (const void*)tri_size})
-		if (misaligned(p, 4)) { set_error("%s: pointers must be 4-byte aligned (got %p)", entry, p); return GSR_E_INVALID; }
-	if (misaligned(scratch, 16)) { set_error("%s: scratch must be 16-byte aligned (got %p)", entry, scratch); return GSR_E_INVALID; }
-	if (misaligned(counts_, 8)) { set_error("%s: counts must be 8-byte aligned (got %p)", entry, (void*)counts_); return GSR_E_INVALID; }
+	if (int rc = pointers_check(entry, {faces, tri_label, tri_size})) return rc;
+	if (int rc = aligned_check(entry, "scratch", scratch, 16)) return rc;
+	if (int rc = aligned_check(entry, "counts", counts_, 8)) return rc;
 	if (int rc = clean_size_check(entry, nV64, nT64)) return rc;
 	if (cluster_to_keep == 0) { set_error("%s: cluster_to_keep must be at least 1", entry); return GSR_E_INVALID; }
-	const CleanScratch s = clean_scratch(nV64, nT64);
+	const CleanScratch s = clean_carve(scratch, nV64, nT64);
 	if (!empty && scratch_bytes < s.bytes) {
 		set_error("%s: scratch of %zu bytes, gsr_mesh_clean_scratch_bytes(%llu, %llu) = %zu", entry, scratch_bytes, (unsigned long long)nV64,
 		          (unsigned long long)nT64, s.bytes);
@@ -389,36 +394,27 @@ extern "C" int gsr_mesh_clean_count(const int* faces, uint64_t nV64, uint64_t nT
 		GSR_LAUNCH_CHECK(0, stream);
 		return 0;
 	}
-	char* base = (char*)scratch;
-	uint32_t* parent = (uint32_t*)(base + s.parent);
-	uint32_t* size = (uint32_t*)(base + s.size);
-	uint8_t* used = (uint8_t*)(base + s.used);
-	uint8_t* keep = (uint8_t*)(base + s.keep);
-	uint32_t* hist = (uint32_t*)(base + s.hist);
-	uint32_t* part = (uint32_t*)(base + s.part);
-	uint32_t* vbase = (uint32_t*)(base + s.vbase);
-	uint32_t* tbase = (uint32_t*)(base + s.tbase);
-	clean_init_kernel<<<s.vblocks, CLEAN_BLOCK, 0, stream>>>(nV, parent, size, used, hist, counts);
+	clean_init_kernel<<<s.vblocks, CLEAN_BLOCK, 0, stream>>>(nV, s.parent, s.size, s.used, s.hist, counts);
 	GSR_LAUNCH_CHECK(0, stream);
-	clean_union_kernel<<<s.tblocks, CLEAN_BLOCK, 0, stream>>>(faces, nV, nT, parent);
+	clean_union_kernel<<<s.tblocks, CLEAN_BLOCK, 0, stream>>>(faces, nV, nT, s.parent);
 	GSR_LAUNCH_CHECK(0, stream);
-	clean_flatten_kernel<<<s.vblocks, CLEAN_BLOCK, 0, stream>>>(nV, parent);
+	clean_flatten_kernel<<<s.vblocks, CLEAN_BLOCK, 0, stream>>>(nV, s.parent);
 	GSR_LAUNCH_CHECK(0, stream);
-	clean_sizes_kernel<<<s.tblocks, CLEAN_BLOCK, 0, stream>>>(faces, nV, nT, parent, size, tri_label, counts);
+	clean_sizes_kernel<<<s.tblocks, CLEAN_BLOCK, 0, stream>>>(faces, nV, nT, s.parent, s.size, tri_label, counts);
 	GSR_LAUNCH_CHECK(0, stream);
 	for (int pass = 0; pass < CLEAN_PASSES; pass++) {
-		clean_digits_kernel<<<s.vblocks, CLEAN_BLOCK, 0, stream>>>(nV, parent, size, hist, pass, cluster_to_keep);
+		clean_digits_kernel<<<s.vblocks, CLEAN_BLOCK, 0, stream>>>(nV, s.parent, s.size, s.hist, pass, cluster_to_keep);
 		GSR_LAUNCH_CHECK(0, stream);
 	}
-	clean_threshold_kernel<<<1, CLEAN_BLOCK, 0, stream>>>(hist, cluster_to_keep, min_triangles, counts);
+	clean_threshold_kernel<<<1, CLEAN_BLOCK, 0, stream>>>(s.hist, cluster_to_keep, min_triangles, counts);
 	GSR_LAUNCH_CHECK(0, stream);
-	clean_flag_kernel<<<s.tblocks, CLEAN_BLOCK, 0, stream>>>(faces, nV, nT, parent, size, counts, tri_size, keep, used);
+	clean_flag_kernel<<<s.tblocks, CLEAN_BLOCK, 0, stream>>>(faces, nV, nT, s.parent, s.size, counts, tri_size, s.keep, s.used);
 	GSR_LAUNCH_CHECK(0, stream);
-	clean_count_kernel<<<s.nblocks, CLEAN_BLOCK, 0, stream>>>(nV, nT, parent, size, used, keep, part, counts);
+	clean_count_kernel<<<s.nblocks, CLEAN_BLOCK, 0, stream>>>(nV, nT, s.parent, s.size, s.used, s.keep, s.part, counts);
 	GSR_LAUNCH_CHECK(0, stream);
-	scan_spine_kernel<<<1, 1024, 0, stream>>>(part, s.nblocks, vbase, tbase, counts);
+	scan_spine_kernel<<<1, 1024, 0, stream>>>(s.part, s.nblocks, s.vbase, s.tbase, counts);
 	GSR_LAUNCH_CHECK(0, stream);
-	clean_offsets_kernel<<<s.nblocks, CLEAN_BLOCK, 0, stream>>>(nV, nT, used, keep, vbase, tbase, (uint32_t*)(base + s.vert_off), (uint32_t*)(base + s.tri_off));
+	clean_offsets_kernel<<<s.nblocks, CLEAN_BLOCK, 0, stream>>>(nV, nT, s.used, s.keep, s.vbase, s.tbase, s.vert_off, s.tri_off);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
@@ -427,9 +423,8 @@ extern "C" int gsr_mesh_clean_emit(const float* verts, const float* vcolor, cons
                                    float* verts_out, float* vcolor_out, int* faces_out, uint64_t nV_out, uint64_t nT_out, void* stream_) {
 	const char* entry = "gsr_mesh_clean_emit";
 	hipStream_t stream = (hipStream_t)stream_;
-	for (const void* p : {(const void*)verts, (const void*)vcolor, (const void*)faces, (const void*)verts_out, (const void*)vcolor_out, (const void*)faces_out})
-		if (misaligned(p, 4)) { set_error("%s: pointers must be 4-byte aligned (got %p)", entry, p); return GSR_E_INVALID; }
-	if (misaligned(scratch, 16)) { set_error("%s: scratch must be 16-byte aligned (got %p)", entry, scratch); return GSR_E_INVALID; }
+	if (int rc = pointers_check(entry, {verts, vcolor, faces, verts_out, vcolor_out, faces_out})) return rc;
+	if (int rc = aligned_check(entry, "scratch", scratch, 16)) return rc;
 	if (int rc = clean_size_check(entry, nV, nT)) return rc;
 	if (nV_out > nV || nT_out > nT) {
 		set_error("%s: nV_out and nT_out cannot exceed nV and nT (got %llu of %llu vertices, %llu of %llu faces)", entry, (unsigned long long)nV_out,
@@ -439,14 +434,10 @@ extern "C" int gsr_mesh_clean_emit(const float* verts, const float* vcolor, cons
 	if (nT_out == 0) return 0;
 	if (!verts || !faces || !scratch || !verts_out || !faces_out) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
 	if ((vcolor != nullptr) != (vcolor_out != nullptr)) { set_error("%s: vcolor and vcolor_out must both be given or both be NULL", entry); return GSR_E_INVALID; }
-	const CleanScratch s = clean_scratch(nV, nT);
-	const char* base = (const char*)scratch;
+	const CleanScratch s = clean_carve(const_cast<void*>(scratch), nV, nT);      // (read only: CleanEmitArgs takes the arrays as pointers to const)
 	CleanEmitArgs a;
 	a.verts = verts; a.vcolor = vcolor; a.faces = faces;
-	a.used = (const uint8_t*)(base + s.used);
-	a.keep = (const uint8_t*)(base + s.keep);
-	a.vert_off = (const uint32_t*)(base + s.vert_off);
-	a.tri_off = (const uint32_t*)(base + s.tri_off);
+	a.used = s.used; a.keep = s.keep; a.vert_off = s.vert_off; a.tri_off = s.tri_off;
 	a.verts_out = verts_out; a.vcolor_out = vcolor_out; a.faces_out = faces_out;
 	a.nV = (uint32_t)nV; a.nT = (uint32_t)nT; a.nV_out = (uint32_t)nV_out; a.nT_out = (uint32_t)nT_out;
 	clean_emit_kernel<<<s.nblocks, CLEAN_BLOCK, 0, stream>>>(a);

@@ -7,9 +7,9 @@
 // registers and the gathered depth before a plane is touched, so a node beyond the shell or outside the view costs no plane traffic.
 // The matrices and the scalars sit in the kernel arguments and in SGPRs.  Unlike gsr_tsdf_integrate the kernel hoists nothing along z:
 // the contraction makes the world position a non-linear function of all three lattice coordinates.
-#include <cmath>
-#include <initializer_list>
-#include "gsr_internal.hpp"
+// The view's matrix rows and dot products are gsr_view.hpp's (shared with gsr_mesh.hip); the entries' common checks are gsr_host.hpp's.
+#include "gsr_host.hpp"
+#include "gsr_view.hpp"
 #include "../../include/gsr_hip_unbounded.h"
 
 namespace gsr {
@@ -19,20 +19,6 @@ namespace gsr {
 struct ViewArgs {             // what steps 2-4 need of a view
 	const float* depth; const float* view; const float* proj;
 	int W, H;
-};
-
-// The rows of the two matrices the kernels need: view z; projection x, y, w (wave-uniform: scalar loads).
-struct ViewRows {
-	float V[4], P[12];
-	__device__ __forceinline__ explicit ViewRows(const ViewArgs& a) {
-#pragma unroll
-		for (int c = 0; c < 4; c++) {
-			V[c] = a.view[4 * c + 2];
-			P[c] = a.proj[4 * c];
-			P[4 + c] = a.proj[4 * c + 1];
-			P[8 + c] = a.proj[4 * c + 3];
-		}
-	}
 };
 
 struct Taps {                 // the four pixels of a bilinear sample and their weights
@@ -45,11 +31,10 @@ struct Taps {                 // the four pixels of a bilinear sample and their 
 
 // Steps 2-4 of the header for the world point (X, Y, Z): false when the point is skipped, else the taps and t.
 __device__ __forceinline__ bool observe(const ViewArgs& a, const ViewRows& r, float X, float Y, float Z, float trunc, Taps& s, float& t) {
-	const float z = fmaf(r.V[2], Z, fmaf(r.V[0], X, fmaf(r.V[1], Y, r.V[3])));
-	const float pw = fmaf(r.P[10], Z, fmaf(r.P[8], X, fmaf(r.P[9], Y, r.P[11])));
+	const ViewDots xy = r.xy(X, Y);
+	const float z = r.z(xy, Z), pw = r.w(xy, Z);
 	if (!(z > 0.f && pw > 0.f)) return false;
-	const float qx = fmaf(r.P[2], Z, fmaf(r.P[0], X, fmaf(r.P[1], Y, r.P[3]))) / pw;
-	const float qy = fmaf(r.P[6], Z, fmaf(r.P[4], X, fmaf(r.P[5], Y, r.P[7]))) / pw;
+	const float qx = r.x(xy, Z) / pw, qy = r.y(xy, Z) / pw;
 	if (!(qx > -1.f && qx < 1.f && qy > -1.f && qy < 1.f)) return false;                  // (NaN: skipped)
 	const float px = fminf(fmaxf(((qx + 1.f) * (float)a.W - 1.f) * 0.5f, 0.f), (float)(a.W - 1));
 	const float py = fminf(fmaxf(((qy + 1.f) * (float)a.H - 1.f) * 0.5f, 0.f), (float)(a.H - 1));
@@ -94,7 +79,7 @@ tsdf_integrate_contracted_kernel(const ContractedArgs a) {
 	if (!(m < 2.f)) return;
 	const float s = uncontract_scale(m) * a.radius;
 	const float trunc = m <= 1.f ? 5.f * a.voxel : 5.f * a.voxel / (2.f - fminf(m, 1.9f));
-	const ViewRows r(a.v);
+	const ViewRows r(a.v.view, a.v.proj);
 	Taps taps;
 	float t;
 	if (!observe(a.v, r, fmaf(s, yx, a.cx), fmaf(s, yy, a.cy), fmaf(s, yz, a.cz), trunc, taps, t)) return;
@@ -115,7 +100,7 @@ points_fuse_view_kernel(const PointsArgs a) {
 	const uint32_t p = blockIdx.x * UNB_BLOCK + threadIdx.x;
 	if (p >= a.n_points) return;
 	const size_t at = (size_t)p * 3;
-	const ViewRows r(a.v);
+	const ViewRows r(a.v.view, a.v.proj);
 	Taps taps;
 	float t;
 	if (!observe(a.v, r, a.points[at], a.points[at + 1], a.points[at + 2], a.sdf_trunc, taps, t)) return;
@@ -140,38 +125,9 @@ uncontract_points_kernel(const float* src, float* dst, uint32_t n_points, float 
 	dst[at + 2] = fminf(fmaxf(fmaf(s, yz, cz), -max_range), max_range);
 }
 
-// ------------------------------------------------------------------------------------------------------------ host side
-static inline bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-static inline bool positive_finite(float v) { return std::isfinite(v) && v > 0.f; }
-static const uint64_t LIMIT = (uint64_t)1 << 31;
-
-static int pointers_check(const char* entry, std::initializer_list<const void*> ptrs) {
-	for (const void* p : ptrs)
-		if (misaligned(p, 4)) { set_error("%s: pointers must be 4-byte aligned (got %p)", entry, p); return GSR_E_INVALID; }
-	return 0;
-}
-
-static int image_check(const char* entry, int W, int H) {
-	if (W < 1 || H < 1 || (uint64_t)W * (uint64_t)H >= LIMIT) {
-		set_error("%s: invalid image size %d x %d", entry, W, H);
-		return GSR_E_INVALID;
-	}
-	return 0;
-}
-
-static int points_check(const char* entry, uint64_t n_points) {
-	if (n_points >= LIMIT) { set_error("%s: n_points must be below 2^31 (got %llu)", entry, (unsigned long long)n_points); return GSR_E_INVALID; }
-	return 0;
-}
-
-static int centre_check(const char* entry, float cx, float cy, float cz, float radius) {
-	if (!positive_finite(radius)) { set_error("%s: radius must be positive and finite (got %g)", entry, (double)radius); return GSR_E_INVALID; }
-	if (!std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(cz)) { set_error("%s: the centre is not finite", entry); return GSR_E_INVALID; }
-	return 0;
-}
-
 }  // namespace gsr
 
+// ------------------------------------------------------------------------------------------------------------ host side
 using namespace gsr;
 
 extern "C" int gsr_tsdf_integrate_contracted(float* tsdf, float* weight, int n, float lo, float step, float cx, float cy, float cz, float radius,
@@ -181,7 +137,7 @@ extern "C" int gsr_tsdf_integrate_contracted(float* tsdf, float* weight, int n, 
 	hipStream_t stream = (hipStream_t)stream_;
 	if (!tsdf || !weight || !depth || !viewmatrix || !projmatrix) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
 	if (int rc = pointers_check(entry, {tsdf, weight, depth, viewmatrix, projmatrix})) return rc;
-	if (n < 2 || n > 2048 || (uint64_t)n * (uint64_t)n * (uint64_t)n >= LIMIT) {          // (the product of three factors up to 2^11 cannot wrap)
+	if (n < 2 || n > 2048 || (uint64_t)n * (uint64_t)n * (uint64_t)n >= LIMIT_2_31) {     // (the product of three factors up to 2^11 cannot wrap)
 		set_error("%s: n must be at least 2 and n^3 below 2^31 (got %d)", entry, n);
 		return GSR_E_INVALID;
 	}
@@ -190,7 +146,7 @@ extern "C" int gsr_tsdf_integrate_contracted(float* tsdf, float* weight, int n, 
 		return GSR_E_INVALID;
 	}
 	if (!std::isfinite(lo)) { set_error("%s: lo is not finite", entry); return GSR_E_INVALID; }
-	if (int rc = centre_check(entry, cx, cy, cz, radius)) return rc;
+	if (int rc = placement_check(entry, "radius", radius, "centre", cx, cy, cz)) return rc;
 	if (int rc = image_check(entry, W, H)) return rc;
 	ContractedArgs a;
 	a.tsdf = tsdf; a.weight = weight;
@@ -231,7 +187,7 @@ extern "C" int gsr_uncontract_points(const float* src, float* dst, uint64_t n_po
 	if (n_points > 0 && (!src || !dst)) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
 	if (int rc = pointers_check(entry, {src, dst})) return rc;
 	if (int rc = points_check(entry, n_points)) return rc;
-	if (int rc = centre_check(entry, cx, cy, cz, radius)) return rc;
+	if (int rc = placement_check(entry, "radius", radius, "centre", cx, cy, cz)) return rc;
 	if (!positive_finite(max_range)) { set_error("%s: max_range must be positive and finite (got %g)", entry, (double)max_range); return GSR_E_INVALID; }
 	if (n_points == 0) return 0;
 	uncontract_points_kernel<<<((uint32_t)n_points + UNB_BLOCK - 1) / UNB_BLOCK, UNB_BLOCK, 0, stream>>>(src, dst, (uint32_t)n_points, cx, cy, cz,

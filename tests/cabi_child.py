@@ -1,6 +1,6 @@
 """The child process in which the C-ABI tests call entries with fake pointers, and the parent's side of it.
 
-A test file keeps its well-formed call and its case tables as data, and ends in
+A test file keeps its well-formed call and its case tables as data (`cases` lists them, `changes` looks one up), and ends in
     if __name__ == "__main__":
         sys.exit(cabi_child.serve(<[(entry, case)]>, <call(gsr, entry, case) -> rc>))
 so that `python <that file>` is the child; its `outcomes` fixture is `cabi_child.run(__file__)` and its test_refusal calls `check`.  The
@@ -17,6 +17,20 @@ from cabi_args import GSR_E_INVALID, HIDE_GPUS, _visible_devices
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STILL_VISIBLE = "a GPU is still visible to the child process although the visible-devices variables hide them: nothing is called"
+
+
+def cases(entries, tables):
+    """[(entry, case, expect)] of a file's case tables, ((expect, {entry: {case: changes}}), ...): entry by entry, and inside an entry
+    table by table in the order given.  This is the order of the test ids and of the child's calls."""
+    return [(entry, k, expect) for entry in entries for expect, table in tables for k in table.get(entry, {})]
+
+
+def changes(tables, entry, case):
+    """What `case` changes in the entry's well-formed call."""
+    for _, table in tables:
+        if case in table.get(entry, {}):
+            return table[entry][case]
+    raise KeyError(case)
 
 
 def serve(cases, call, argv=None):

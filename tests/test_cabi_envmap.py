@@ -79,24 +79,12 @@ ACCEPTED = {
         "largest": dict(planes=2, L=32767), "dst-right-behind-src": dict(dst=FAKE + SRC_BYTES), "wide-clamp": dict(lo=1e-6, hi=1 - 1e-6),
     },
 }
-
-
-def cases():
-    out = []
-    for entry in ENTRIES:
-        out += [(entry, k, "accepted") for k in ACCEPTED[entry]] + [(entry, k, "refused") for k in REFUSED[entry]]
-    return out
-
-
-def _changes(entry, case):
-    for table in (ACCEPTED, REFUSED):
-        if case in table[entry]:
-            return table[entry][case]
-    raise KeyError(case)
+TABLES = (("accepted", ACCEPTED), ("refused", REFUSED))
+CASES = cabi_child.cases(ENTRIES, TABLES)
 
 
 def _call(gsr, entry, case):
-    args = dict(BASE[entry], **_changes(entry, case))
+    args = dict(BASE[entry], **cabi_child.changes(TABLES, entry, case))
     names = RESIZE_ARGS if entry == "gsr_envmap_resize" else SHARPEN_ARGS
     return getattr(gsr.lib, entry)(*[args[k] for k in names])
 
@@ -106,10 +94,10 @@ def outcomes(hip_lib_built):
     return cabi_child.run(__file__)
 
 
-@pytest.mark.parametrize("entry, case, expect", cases(), ids=lambda v: v)
+@pytest.mark.parametrize("entry, case, expect", CASES, ids=lambda v: v)
 def test_refusal(outcomes, entry, case, expect):
     cabi_child.check(outcomes, entry, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(cabi_child.serve([c[:2] for c in cases()], _call))
+    sys.exit(cabi_child.serve([c[:2] for c in CASES], _call))

@@ -45,6 +45,22 @@ def test_scratch_bytes_is_host_arithmetic(hip_lib_built):
     assert q(2047, 1024, 1024) > 0
 
 
+def test_scratch_sizes_are_the_recorded_ones(hip_lib_built):
+    """The three size queries whose layouts are carved by one function each (mesh_carve, clean_carve, knn_carve): the values below were
+    read from the library as it was before the layouts moved onto Carver, at one node, block and leaf on either side of a boundary, at
+    empty arrays and at the largest sizes.  A caller's buffer sized by an older library must still fit: none of them may change."""
+    import _gsr
+    mesh = {(2, 2, 2): 2048, (23, 19, 17): 83712, (64, 4, 8): 23296, (65, 5, 9): 33536, (2047, 1024, 1024): 23711399936,
+            (1, 19, 17): 0, (23, 0, 17): 0, (23, 19, -4): 0, (2048, 1024, 1024): 0, (65536, 65536, 2): 0}
+    clean = {(1, 1): 6400, (255, 257): 9984, (256, 256): 9472, (70000, 0): 918272, (0, 0): 4096, (0, 1504): 12544,
+             (2 ** 31 - 1, (2 ** 31 - 1) // 3): 31597094400, (2 ** 31, 1504): 0, (754, (2 ** 31 + 2) // 3): 0}
+    knn = {(1,): 20736, (255,): 28416, (256,): 28416, (257,): 29952, (100000,): 3768320, (2 ** 30 - 1,): 40273851648,
+           (0,): 0, (-1,): 0, (2 ** 30,): 0}
+    for name, table in (("gsr_mesh_scratch_bytes", mesh), ("gsr_mesh_clean_scratch_bytes", clean), ("gsr_knn_scratch_bytes", knn)):
+        for sizes, expected in table.items():
+            assert int(getattr(_gsr.lib, name)(*sizes)) == expected, (name, sizes)
+
+
 # ------------------------------------------------------------------------------------------------- the refusals
 ARGS = {
     "gsr_tsdf_integrate": ("tsdf", "weight", "color", "nx", "ny", "nz", "ox", "oy", "oz", "voxel", "depth", "rgb", "alpha", "alpha_min", "W", "H",
@@ -114,19 +130,11 @@ NOOP = {"gsr_mesh_emit": {"nV=0": dict(nV=0, nT=0), "nV=0-null-outputs": dict(nV
 TABLES = (("accepted", ACCEPTED), ("refused", REFUSED), ("noop", NOOP))
 
 
-def cases():
-    return [(entry, k, expect) for entry in ENTRIES for expect, table in TABLES for k in table.get(entry, {})]
-
-
-def _changes(entry, case):
-    for _, table in TABLES:
-        if case in table.get(entry, {}):
-            return table[entry][case]
-    raise KeyError(case)
+CASES = cabi_child.cases(ENTRIES, TABLES)
 
 
 def _call(gsr, entry, case):
-    args = dict(BASE[entry], **_changes(entry, case))
+    args = dict(BASE[entry], **cabi_child.changes(TABLES, entry, case))
     if isinstance(args.get("scratch_bytes"), tuple):
         args["scratch_bytes"] = int(gsr.lib.gsr_mesh_scratch_bytes(NX, NY, NZ)) + args["scratch_bytes"][1]
     return getattr(gsr.lib, entry)(*[args[k] for k in ARGS[entry]])
@@ -137,10 +145,10 @@ def outcomes(hip_lib_built):
     return cabi_child.run(__file__)
 
 
-@pytest.mark.parametrize("entry, case, expect", cases(), ids=lambda v: v)
+@pytest.mark.parametrize("entry, case, expect", CASES, ids=lambda v: v)
 def test_refusal(outcomes, entry, case, expect):
     cabi_child.check(outcomes, entry, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(cabi_child.serve([c[:2] for c in cases()], _call))
+    sys.exit(cabi_child.serve([c[:2] for c in CASES], _call))

@@ -101,19 +101,11 @@ NOOP = {"gsr_mesh_clean_emit": {"nT_out=0": dict(nV_out=0, nT_out=0),
 TABLES = (("accepted", ACCEPTED), ("refused", REFUSED), ("noop", NOOP))
 
 
-def cases():
-    return [(entry, k, expect) for entry in ENTRIES for expect, table in TABLES for k in table.get(entry, {})]
-
-
-def _changes(entry, case):
-    for _, table in TABLES:
-        if case in table.get(entry, {}):
-            return table[entry][case]
-    raise KeyError(case)
+CASES = cabi_child.cases(ENTRIES, TABLES)
 
 
 def _call(gsr, entry, case):
-    args = dict(BASE[entry], **_changes(entry, case))
+    args = dict(BASE[entry], **cabi_child.changes(TABLES, entry, case))
     if isinstance(args.get("scratch_bytes"), tuple):
         args["scratch_bytes"] = int(gsr.lib.gsr_mesh_clean_scratch_bytes(args["nV"], args["nT"])) + args["scratch_bytes"][1]
     return getattr(gsr.lib, entry)(*[args[k] for k in ARGS[entry]])
@@ -124,10 +116,10 @@ def outcomes(hip_lib_built):
     return cabi_child.run(__file__)
 
 
-@pytest.mark.parametrize("entry, case, expect", cases(), ids=lambda v: v)
+@pytest.mark.parametrize("entry, case, expect", CASES, ids=lambda v: v)
 def test_refusal(outcomes, entry, case, expect):
     cabi_child.check(outcomes, entry, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(cabi_child.serve([c[:2] for c in cases()], _call))
+    sys.exit(cabi_child.serve([c[:2] for c in CASES], _call))

@@ -65,25 +65,12 @@ NOOP = {
     "gsr_env_scope_forward": {"P=0-masks-only": dict(MASKS_ONLY, P=0, means3D=None, inside=None, outside=None)},
     "gsr_env_scope_backward": {"P=0": dict(P=0)},
 }
-
-
-def cases():
-    out = []
-    for entry in ENTRIES[1:]:
-        out += [(entry, k, "accepted") for k in ACCEPTED[entry]] + [(entry, k, "noop") for k in NOOP[entry]]
-        out += [(entry, k, "refused") for k in REFUSED[entry]]
-    return out
-
-
-def _changes(entry, case):
-    for table in (ACCEPTED, NOOP, REFUSED):
-        if case in table[entry]:
-            return table[entry][case]
-    raise KeyError(case)
+TABLES = (("accepted", ACCEPTED), ("noop", NOOP), ("refused", REFUSED))
+CASES = cabi_child.cases(ENTRIES[1:], TABLES)         # (the first entry is a size query: it refuses nothing)
 
 
 def _call(gsr, entry, case):
-    args = dict(BASE[entry], **_changes(entry, case))
+    args = dict(BASE[entry], **cabi_child.changes(TABLES, entry, case))
     names = FORWARD_ARGS if entry == "gsr_env_scope_forward" else BACKWARD_ARGS
     return getattr(gsr.lib, entry)(*[args[k] for k in names])
 
@@ -99,10 +86,10 @@ def test_scratch_query_is_positive(hip_lib_built):
     assert floats > 0 and floats % 2 == 0       # whole pairs
 
 
-@pytest.mark.parametrize("entry, case, expect", cases(), ids=lambda v: v)
+@pytest.mark.parametrize("entry, case, expect", CASES, ids=lambda v: v)
 def test_refusal(outcomes, entry, case, expect):
     cabi_child.check(outcomes, entry, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(cabi_child.serve([c[:2] for c in cases()], _call))
+    sys.exit(cabi_child.serve([c[:2] for c in CASES], _call))

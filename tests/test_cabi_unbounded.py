@@ -127,19 +127,11 @@ NOOP = {
 TABLES = (("accepted", ACCEPTED), ("refused", REFUSED), ("noop", NOOP))
 
 
-def cases():
-    return [(entry, k, expect) for entry in ENTRIES for expect, table in TABLES for k in table.get(entry, {})]
-
-
-def _changes(entry, case):
-    for _, table in TABLES:
-        if case in table.get(entry, {}):
-            return table[entry][case]
-    raise KeyError(case)
+CASES = cabi_child.cases(ENTRIES, TABLES)
 
 
 def _call(gsr, entry, case):
-    args = dict(BASE[entry], **_changes(entry, case))
+    args = dict(BASE[entry], **cabi_child.changes(TABLES, entry, case))
     return getattr(gsr.lib, entry)(*[args[k] for k in ARGS[entry]])
 
 
@@ -148,10 +140,10 @@ def outcomes(hip_lib_built):
     return cabi_child.run(__file__)
 
 
-@pytest.mark.parametrize("entry, case, expect", cases(), ids=lambda v: v)
+@pytest.mark.parametrize("entry, case, expect", CASES, ids=lambda v: v)
 def test_refusal(outcomes, entry, case, expect):
     cabi_child.check(outcomes, entry, case, expect)
 
 
 if __name__ == "__main__":
-    sys.exit(cabi_child.serve([c[:2] for c in cases()], _call))
+    sys.exit(cabi_child.serve([c[:2] for c in CASES], _call))
