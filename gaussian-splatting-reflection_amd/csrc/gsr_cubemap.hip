@@ -5,7 +5,7 @@
 // (<= 4.7 MB at L = 256) lives in L2 / Infinity Cache, the streaming traffic is the per-pixel planes.
 #include <algorithm>
 #include <cstring>
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include <mutex>
 #include <memory>
 #include "gsr_sort.hpp"
@@ -544,7 +544,7 @@ extern "C" int gsr_deferred_reflection_forward_keys(const float* normal_view, co
                                                   uint32_t* sort_keys, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
 	if (width <= 0 || height <= 0 || !normal_view || !base_color || !refl_strength || !cam || !cubemap || !fail_value || !out_final ||
-	    !out_refl_color || !out_normal_world || L == 0 || ((uintptr_t)cubemap_rgba & 15) != 0) {
+	    !out_refl_color || !out_normal_world || L == 0 || misaligned(cubemap_rgba, 16)) {
 		set_error("gsr_deferred_reflection_forward: invalid argument");
 		return GSR_E_INVALID;
 	}
@@ -552,10 +552,10 @@ extern "C" int gsr_deferred_reflection_forward_keys(const float* normal_view, co
 	if ((size_t)6 * L * L >= 0xFFFFFFFFull) { set_error("gsr_deferred_reflection_forward: cubemap too large"); return GSR_E_INVALID; }
 	const size_t HW = (size_t)width * height;
 	StageTimer st_(GSR_STAGE_REFL_FWD, stream);
-	const unsigned grid = (unsigned)((HW + 255) / 256);
+	const unsigned grid = blocks_of(HW);
 	if (cubemap_rgba) {
 		float4* rgba = reinterpret_cast<float4*>(cubemap_rgba);
-		cubemap_interleave_kernel<<<(unsigned)((6 * (size_t)L * L + 255) / 256), 256, 0, stream>>>(cubemap, rgba, (int)L);
+		cubemap_interleave_kernel<<<blocks_of(6 * (size_t)L * L), 256, 0, stream>>>(cubemap, rgba, (int)L);
 		deferred_refl_fwd_kernel<true><<<grid, 256, 0, stream>>>(normal_view, base_color, refl_strength, cam, cubemap, rgba, fail_value, (int)L, width, height,
 		                                                        out_final, out_refl_color, out_normal_world, sort_keys, (uint32_t)(6 * (size_t)L * L));
 	} else {
@@ -689,7 +689,7 @@ struct ReflTail {
 	bool carve(float* scratch, size_t scratch_floats) {
 		staging = scratch;
 		fail_acc = scratch + rs.ntex * 4;
-		if (scratch_floats < rs.total_floats || rs.n >= ((size_t)1 << 30) || rs.ntex >= 0xFFFFFFFFull || ((uintptr_t)scratch & 31) != 0) return false;
+		if (scratch_floats < rs.total_floats || rs.n >= ((size_t)1 << 30) || rs.ntex >= 0xFFFFFFFFull || misaligned(scratch, 32)) return false;
 		footprints = reinterpret_cast<ReflFootprint*>(scratch + (rs.ntex + 1) * 4 + 4);   // 32-byte aligned as long as scratch is
 		keys_in = reinterpret_cast<uint32_t*>(footprints + rs.n);
 		keys_out = keys_in + rs.n;
@@ -801,8 +801,8 @@ extern "C" int gsr_deferred_reflection_backward_keys(const float* normal_view, c
 	}
 	if ((size_t)6 * L * L >= 0xFFFFFFFFull) { set_error("gsr_deferred_reflection_backward: cubemap too large"); return GSR_E_INVALID; }
 	// the texel staging at the head of the scratch and the interleaved cubemap are float4 arrays on every path
-	GSR_REQUIRE_ALIGNED16_IN("gsr_deferred_reflection_backward", scratch, "scratch");
-	GSR_REQUIRE_ALIGNED16_IN("gsr_deferred_reflection_backward", cubemap_rgba, "cubemap_rgba");
+	if (int rc = aligned_check("gsr_deferred_reflection_backward", "scratch", scratch, 16)) return rc;
+	if (int rc = aligned_check("gsr_deferred_reflection_backward", "cubemap_rgba", cubemap_rgba, 16)) return rc;
 	const size_t HW = (size_t)width * height;
 	ReflTail t(L, width, height, stream);
 	const size_t ntex = t.rs.ntex;
@@ -816,11 +816,11 @@ extern "C" int gsr_deferred_reflection_backward_keys(const float* normal_view, c
 		// texel gradients by float atomics straight from the pixel kernel (memory-side, ~2.5 requests per pixel)
 		{
 			StageTimer st_(GSR_STAGE_REFL_BWD, stream);
-			const unsigned grid = (unsigned)((HW * 4 + 255) / 256);
+			const unsigned grid = blocks_of(HW * 4);
 			deferred_refl_bwd_kernel<<<grid, 256, 0, stream>>>(normal_view, base_color, refl_strength, cam, cubemap, fail_value, (int)L, width, height, g_final,
 			                                                  g_refl_color, g_normal_world, g_normal_view, g_base, g_strength, t.staging, t.fail_acc);
 		}
-		unpack<<<(unsigned)((ntex + 255) / 256), 256, 0, stream>>>((const float4*)t.staging, g_cubemap, g_fail, (int)L);
+		unpack<<<blocks_of(ntex), 256, 0, stream>>>((const float4*)t.staging, g_cubemap, g_fail, (int)L);
 		GSR_LAUNCH_CHECK(0, stream);
 		return 0;
 	}
@@ -873,7 +873,7 @@ extern "C" int gsr_deferred_reflection_backward_keys(const float* normal_view, c
 		const unsigned cgrid = (unsigned)((t.rs.n + per_wg - 1) / per_wg);
 		if (!sort_keys) GSR_HIP_CHECK(t.sort(t.keys_in, small_sort, false));
 		refl_run_combine_kernel<<<cgrid, 256, 0, t.tail>>>(t.keys_out, t.pix_out, t.footprints, t.rs.n, L, (uint32_t)ntex, t.staging);
-		unpack<<<(unsigned)((ntex + 255) / 256), 256, 0, t.tail>>>((const float4*)t.staging, g_cubemap, g_fail, (int)L);
+		unpack<<<blocks_of(ntex), 256, 0, t.tail>>>((const float4*)t.staging, g_cubemap, g_fail, (int)L);
 	}
 	if (t.side) GSR_HIP_CHECK(t.mark_done());
 	GSR_HIP_CHECK(hipGetLastError());
@@ -944,7 +944,7 @@ __global__ void __launch_bounds__(256) normal_world_bwd_kernel(const float* __re
 extern "C" int gsr_normal_world_forward(const float* normal_view, const float* cam, int width, int height, float* out_normal_world, void* stream_) {
 	if (width <= 0 || height <= 0 || !normal_view || !cam || !out_normal_world) { set_error("gsr_normal_world_forward: invalid argument"); return GSR_E_INVALID; }
 	const size_t HW = (size_t)width * height;
-	normal_world_fwd_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, (hipStream_t)stream_>>>(normal_view, cam, HW, out_normal_world);
+	normal_world_fwd_kernel<<<blocks_of(HW), 256, 0, (hipStream_t)stream_>>>(normal_view, cam, HW, out_normal_world);
 	GSR_LAUNCH_CHECK(0, (hipStream_t)stream_);
 	return 0;
 }
@@ -952,7 +952,7 @@ extern "C" int gsr_normal_world_backward(const float* normal_view, const float* 
                                          float* g_normal_view, void* stream_) {
 	if (width <= 0 || height <= 0 || !normal_view || !cam || !g_normal_world || !g_normal_view) { set_error("gsr_normal_world_backward: invalid argument"); return GSR_E_INVALID; }
 	const size_t HW = (size_t)width * height;
-	normal_world_bwd_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, (hipStream_t)stream_>>>(normal_view, cam, HW, g_normal_world, g_normal_view);
+	normal_world_bwd_kernel<<<blocks_of(HW), 256, 0, (hipStream_t)stream_>>>(normal_view, cam, HW, g_normal_world, g_normal_view);
 	GSR_LAUNCH_CHECK(0, (hipStream_t)stream_);
 	return 0;
 }

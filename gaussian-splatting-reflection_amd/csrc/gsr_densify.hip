@@ -5,7 +5,7 @@
 // plan="torch": a few P-sized boolean vectors) or on the device by the plan entries at the end of this file
 // (include/gsr_hip_densify.h: classify + rank per workgroup, a one-workgroup scan of the workgroup counts, emit); the only arithmetic
 // besides the plan's tests is the per-view statistics update and the sampling of split children.
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include "../../include/gsr_hip_densify.h"
 
 namespace gsr {
@@ -337,6 +337,11 @@ static PlanScratch plan_carve(void* base, size_t P, size_t N) {
 	s.bytes = c.size();
 	return s;
 }
+// (these entries refuse a misaligned scratch before one that is too small, so the alignment is asked first)
+static int plan_scratch_check(const char* entry, const void* scratch, size_t scratch_bytes, size_t P, size_t N) {
+	if (int rc = aligned_check(entry, "scratch", scratch, 16)) return rc;
+	return scratch_check(entry, scratch, scratch_bytes, plan_carve(nullptr, P, N).bytes, "bytes", "gsr_densify_plan_scratch_bytes(P, N)", 16);
+}
 static inline bool plan_sizes_ok(int P, int N) { return P >= 0 && N >= 1 && (long long)P * ((long long)N + 1) < (1ll << 31); }
 
 // What select and rows refuse alike.  0 to go on (P == 0 included: the caller writes its zero counts), GSR_E_INVALID otherwise.
@@ -350,10 +355,7 @@ static int plan_check(const char* entry, int P, const gsr_densify_plan* plan, co
 	if (!counts) { set_error("%s: NULL counts", entry); return GSR_E_INVALID; }
 	if (P == 0) return 0;
 	if (!scratch) { set_error("%s: NULL scratch", entry); return GSR_E_INVALID; }
-	if (misaligned16(scratch)) { set_error("%s: scratch must be 16-byte aligned; got %p", entry, scratch); return GSR_E_INVALID; }
-	const size_t need = plan_carve(nullptr, (size_t)P, (size_t)plan->N).bytes;
-	if (scratch_bytes < need) { set_error("%s: scratch of %zu bytes, gsr_densify_plan_scratch_bytes(%d, %d) = %zu", entry, scratch_bytes, P, plan->N, need); return GSR_E_INVALID; }
-	return 0;
+	return plan_scratch_check(entry, scratch, scratch_bytes, (size_t)P, (size_t)plan->N);
 }
 
 static int fill_gather_groups(const char* entry, uint64_t n_rows, const gsr_gather_group* groups, int num_groups, GatherGroups* g) {
@@ -408,15 +410,9 @@ extern "C" int gsr_gather_rows(const float* src, float* dst, const int* row_map,
 	if (n_rows == 0 || num_groups == 0) return 0;
 	if (!src || !dst || !row_map || !groups) { set_error("gsr_gather_rows: NULL argument"); return GSR_E_INVALID; }
 	GatherGroups g;
-	g.n = num_groups;
-	g.first[0] = 0;
-	for (int k = 0; k < num_groups; k++) {
-		if (groups[k].width == 0) { set_error("gsr_gather_rows: zero-width group"); return GSR_E_INVALID; }
-		g.src_off[k] = groups[k].src_offset; g.dst_off[k] = groups[k].dst_offset; g.width[k] = groups[k].width;
-		g.first[k + 1] = g.first[k] + n_rows * (unsigned long long)groups[k].width;
-	}
+	if (int rc = fill_gather_groups("gsr_gather_rows", n_rows, groups, num_groups, &g)) return rc;
 	const unsigned long long total = g.first[num_groups];
-	gather_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, stream>>>(src, dst, row_map, g);
+	gather_rows_kernel<<<blocks_of(total), 256, 0, stream>>>(src, dst, row_map, g);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
@@ -442,7 +438,7 @@ extern "C" int gsr_scatter_rows(const float* src, float* dst, const int* slot, u
 	GatherGroups g;
 	if (int rc = fill_gather_groups("gsr_scatter_rows", n_rows, groups, num_groups, &g)) return rc;
 	const unsigned long long total = g.first[num_groups];
-	scatter_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, stream>>>(src, dst, slot, g);
+	scatter_rows_kernel<<<blocks_of(total), 256, 0, stream>>>(src, dst, slot, g);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
@@ -508,9 +504,8 @@ extern "C" int gsr_prune_rows(int P, const uint8_t* remove, void* scratch, size_
 		return 0;
 	}
 	if (!remove || !scratch || !row_map) { set_error("gsr_prune_rows: NULL buffer"); return GSR_E_INVALID; }
-	if (misaligned16(scratch)) { set_error("gsr_prune_rows: scratch must be 16-byte aligned; got %p", scratch); return GSR_E_INVALID; }
+	if (int rc = plan_scratch_check("gsr_prune_rows", scratch, scratch_bytes, (size_t)P, 1)) return rc;
 	const PlanScratch s = plan_carve(scratch, (size_t)P, 1);
-	if (scratch_bytes < s.bytes) { set_error("gsr_prune_rows: scratch of %zu bytes, gsr_densify_plan_scratch_bytes(%d, 1) = %zu", scratch_bytes, P, s.bytes); return GSR_E_INVALID; }
 	const int nb = (int)plan_blocks((size_t)P);
 	prune_rows_kernel<<<nb, PLAN_B, 0, stream>>>(P, remove, s.words, s.blocks);
 	GSR_LAUNCH_CHECK(0, stream);

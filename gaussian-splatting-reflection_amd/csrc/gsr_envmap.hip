@@ -4,7 +4,7 @@
 // no tuning.  Every index is formed in 64 bits from values the entries have bounded (planes * L * L < 2^31 for both resolutions).
 #include <cmath>
 #include <initializer_list>
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include "../../include/gsr_hip_envmap.h"
 
 namespace gsr {
@@ -90,17 +90,13 @@ envmap_sharpen_kernel(const float* __restrict__ src, float* __restrict__ dst, ui
 // What both entries check alike.  Returns 0 to go on.
 static int envmap_check(const char* entry, const float* src, float* dst, int planes, int L_src, int L_dst) {
 	if (!src || !dst) { set_error("%s: invalid argument (NULL pointer)", entry); return GSR_E_INVALID; }
-	if ((reinterpret_cast<uintptr_t>(src) & 3u) || (reinterpret_cast<uintptr_t>(dst) & 3u)) {
-		set_error("%s: src and dst must be 4-byte aligned (got %p, %p)", entry, (const void*)src, (const void*)dst);
-		return GSR_E_INVALID;
-	}
+	if (int rc = pointers_check(entry, {src, dst}, 4, "src and dst")) return rc;
 	if (planes < 1 || L_src < 1 || L_dst < 1) {
 		set_error("%s: invalid size (planes = %d, resolutions %d and %d)", entry, planes, L_src, L_dst);
 		return GSR_E_INVALID;
 	}
-	const uint64_t limit = ((uint64_t)1 << 31) - 1;      // planes * L * L must stay below 2^31 (L * L fits 64 bits; the product is never formed)
-	for (int L : {L_src, L_dst})
-		if ((uint64_t)L * (uint64_t)L > limit / (uint64_t)planes) {
+	for (int L : {L_src, L_dst})      // (L * L fits 64 bits; the product with planes is never formed)
+		if ((uint64_t)L * (uint64_t)L > (LIMIT_2_31 - 1) / (uint64_t)planes) {
 			set_error("%s: planes * L * L must be below 2^31 (planes = %d, L = %d)", entry, planes, L);
 			return GSR_E_INVALID;
 		}
@@ -118,7 +114,7 @@ extern "C" int gsr_envmap_resize(const float* src, float* dst, int planes, int L
 	hipStream_t stream = (hipStream_t)stream_;
 	if (int rc = envmap_check("gsr_envmap_resize", src, dst, planes, L_src, L_dst)) return rc;
 	const uint32_t total = (uint32_t)planes * (uint32_t)L_dst * (uint32_t)L_dst;
-	envmap_resize_kernel<<<(total + 255u) / 256u, 256, 0, stream>>>(src, dst, total, (uint32_t)L_src, (uint32_t)L_dst);
+	envmap_resize_kernel<<<blocks_of(total), 256, 0, stream>>>(src, dst, total, (uint32_t)L_src, (uint32_t)L_dst);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
@@ -132,7 +128,7 @@ extern "C" int gsr_envmap_sharpen(const float* src, float* dst, int planes, int 
 		return GSR_E_INVALID;
 	}
 	const uint32_t total = (uint32_t)planes * (uint32_t)L * (uint32_t)L;
-	envmap_sharpen_kernel<<<(total + 255u) / 256u, 256, 0, stream>>>(src, dst, total, (uint32_t)L, factor, lo, hi);
+	envmap_sharpen_kernel<<<blocks_of(total), 256, 0, stream>>>(src, dst, total, (uint32_t)L, factor, lo, hi);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }

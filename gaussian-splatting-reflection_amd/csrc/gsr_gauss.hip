@@ -8,7 +8,7 @@
 // which the tile kernels gather with four lanes per record (64 contiguous bytes) into LDS.
 // A 16x16 tile is one 256-thread workgroup = 4 waves, each wave owning an 8x8 pixel quadrant so that
 // wave-uniform skips ("no lane of this wave touches Gaussian j") fire as often as possible.
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include "gsr_tile_walk.hpp"
 #include "gsr_sort.hpp"
 #include "gsr_math.hpp"

@@ -30,19 +30,6 @@ void set_error(const char* fmt, ...);
 		if (debug) GSR_HIP_CHECK(hipStreamSynchronize(stream));          \
 	} while (0)
 
-// 128-bit accesses: the per-Gaussian kernels read an SH row whose length is a multiple of 16 bytes as float4, and store dL_dsh rows
-// (M = 16) and dL_drot rows as float4.  torch allocations are 256-byte aligned; VIEWS into a packed buffer (gradient sinks) need not be.
-// Checked at the C ABI so that a misaligned caller gets GSR_E_INVALID instead of a faulting or sector-splitting kernel.
-static inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-#define GSR_REQUIRE_ALIGNED16_IN(func, ptr, what)                                                             \
-	do {                                                                                                      \
-		if ((ptr) && gsr::misaligned16(ptr)) {                                                                \
-			gsr::set_error("%s: %s must be 16-byte aligned (float4 accesses); got %p", func, what, (const void*)(ptr)); \
-			return GSR_E_INVALID;                                                                             \
-		}                                                                                                     \
-	} while (0)
-#define GSR_REQUIRE_ALIGNED16(ptr, what) GSR_REQUIRE_ALIGNED16_IN(__func__, ptr, what)
-
 // ------------------------------------------------------------------ per-stage timing (off by default)
 // RAII: records a start event at construction and a stop event at destruction on `stream` when profiling
 // is enabled (gsr_profile_enable); a no-op otherwise.
@@ -143,17 +130,6 @@ BinningState carve_binning(void* buf, size_t R, size_t tiles, size_t sort_temp_b
 int forward_workspace(gsr_alloc_fn alloc, void* alloc_user, const WorkspaceLayout& layout, size_t P, size_t HW, size_t tiles, GeomState* geom,
                       ImageState* img);
 
-// The check of the SH input every forward AND backward makes (through its variant's check_*_inputs): degree 0..3 with (D+1)^2 <= M
-// coefficients per row, and rows of a multiple of 16 bytes 16-byte aligned (their float4 loads).  `entry` names the caller in the message.
-static inline int check_sh_input(const char* entry, int D, int M, const float* shs) {
-	if (D < 0 || D > 3 || (shs && (D + 1) * (D + 1) > M)) { set_error("%s: SH degree %d not supported with M=%d", entry, D, M); return GSR_E_INVALID; }
-	if (shs && ((M * 3) & 3) == 0 && misaligned16(shs)) {
-		set_error("%s: shs (rows of a multiple of 16 bytes) must be 16-byte aligned (float4 accesses); got %p", entry, (const void*)shs);
-		return GSR_E_INVALID;
-	}
-	return 0;
-}
-
 // One camera for both variants' per-Gaussian kernels (reference rasterizer_impl.cu:228-229 for the focal lengths, the same in DGR and DSR).
 struct RasterCam {
 	const float* view;
@@ -169,31 +145,6 @@ static inline RasterCam make_cam(const float* view, const float* proj, const flo
 	c.focal_y = H / (2.0f * tan_fovy);
 	c.focal_x = W / (2.0f * tan_fovx);
 	return c;
-}
-
-// What both backward drivers do before their kernels, after the variant's check_*_inputs (the scene, camera and SH tests the forward makes
-// too): size check, P == 0 (returns 0: nothing to do), the test of the pointers only the backward has (`missing_pointer`: the caller
-// evaluates it, it only compares pointers), 16-byte alignment of what the per-Gaussian pass stores as float4 (`also_aligned`: one more
-// such pointer of the variant, or NULL), the forward's buffers carved again, the accumulator zeroed.
-// `entry` / `func` name the operation / the driver in the messages.  Returns 1 to go on, < 0 on error.
-struct BackwardWorkspace { GeomState geom; ImageState img; BinningState bin; int tiles_x, ntiles; };
-static inline int backward_prologue(const char* entry, const char* func, const WorkspaceLayout& layout, int P, int M, int R, int width, int height,
-                                    bool missing_pointer, const float* shs, const float* dL_dsh, const float* dL_drot, const float* also_aligned,
-                                    const char* also_what, void* geom_buffer, void* binning_buffer, void* image_buffer, hipStream_t stream,
-                                    BackwardWorkspace* w) {
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) { set_error("%s: invalid size", entry); return GSR_E_INVALID; }
-	if (P == 0) return 0;
-	if (missing_pointer) { set_error("%s: missing required pointer", entry); return GSR_E_INVALID; }
-	if (shs && ((M * 3) & 3) == 0) GSR_REQUIRE_ALIGNED16_IN(func, dL_dsh, "dL_dsh");   // (shs itself: check_sh_input)
-	GSR_REQUIRE_ALIGNED16_IN(func, dL_drot, "dL_drot");
-	GSR_REQUIRE_ALIGNED16_IN(func, also_aligned, also_what);
-	w->tiles_x = (width + 15) / 16;
-	w->ntiles = w->tiles_x * ((height + 15) / 16);
-	w->geom = carve_geom(geom_buffer, P, layout, nullptr);
-	w->img = carve_image(image_buffer, (size_t)width * height, w->ntiles, layout, nullptr);
-	w->bin = carve_binning(binning_buffer, R, w->ntiles, 0, nullptr);
-	GSR_HIP_CHECK(hipMemsetAsync(w->geom.acc, 0, (size_t)P * layout.acc_floats * sizeof(float), stream));
-	return 1;
 }
 
 int option_cull();   // 1 (default): per-wave bounding-box culling in the tile kernels; 0: evaluate every list entry

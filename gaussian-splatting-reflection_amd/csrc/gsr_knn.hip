@@ -17,7 +17,7 @@
 // not change the multiset of the three smallest distances.  The result is (b0 + b1 + b2) / 3 of that multiset, summed in ascending
 // order, and so does not depend on the input order bit for bit.  Missing neighbours (P < 4) stay at FLT_MAX.
 // Host side: the caller's scratch is KnnLayout, typed pointers carved by knn_carve on Carver (a NULL base answers gsr_knn_scratch_bytes).
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include <algorithm>
 #include <cfloat>
 #include "gsr_sort.hpp"
@@ -300,7 +300,7 @@ extern "C" int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, v
 		set_error("gsr_knn_mean_dist: scratch of %zu bytes, %zu needed (gsr_knn_scratch_bytes)", scratch_bytes, l.bytes);
 		return GSR_E_INVALID;
 	}
-	GSR_REQUIRE_ALIGNED16_IN("gsr_knn_mean_dist", scratch, "scratch");   // (it is carved into float4 arrays)
+	if (int rc = aligned_check("gsr_knn_mean_dist", "scratch", scratch, 16)) return rc;   // (it is carved into float4 arrays)
 	KnnTree t;
 	t.pts = l.sorted;
 	t.P = P;
@@ -312,14 +312,14 @@ extern "C" int gsr_knn_mean_dist(int P, const float* points, float* mean_dist, v
 	const int n_partial = (int)std::min<size_t>(KNN_BOUNDS_BLOCKS, ((size_t)P + 256 * 16 - 1) / (256 * 16));
 	knn_bounds_kernel<<<n_partial, 256, 0, stream>>>(P, points, l.partial);
 	GSR_LAUNCH_CHECK(0, stream);
-	const unsigned blocks = (unsigned)(((size_t)P + 255) / 256);
+	const unsigned blocks = blocks_of((size_t)P);
 	knn_morton_kernel<<<blocks, 256, 0, stream>>>(P, n_partial, points, l.partial, l.keys);
 	GSR_LAUNCH_CHECK(0, stream);
 	GSR_HIP_CHECK(KnnSort::pairs(l.sort_temp, l.sort_bytes, l.keys, l.keys_sorted, rocprim::counting_iterator<uint32_t>(0), l.order, (size_t)P, KNN_MORTON_BITS, stream));
 	knn_gather_leaves_kernel<<<blocks, 256, 0, stream>>>(P, points, l.order, l.sorted, l.lo[0], l.hi[0]);
 	GSR_LAUNCH_CHECK(0, stream);
 	for (int k = 1; k < KNN_LEVELS; k++) {
-		knn_parent_boxes_kernel<<<(unsigned)(((size_t)l.n[k - 1] + 255) / 256), 256, 0, stream>>>(l.n[k - 1], l.lo[k - 1], l.hi[k - 1], l.lo[k], l.hi[k]);
+		knn_parent_boxes_kernel<<<blocks_of((size_t)l.n[k - 1]), 256, 0, stream>>>(l.n[k - 1], l.lo[k - 1], l.hi[k - 1], l.lo[k], l.hi[k]);
 		GSR_LAUNCH_CHECK(0, stream);
 	}
 	knn_search_kernel<<<(unsigned)((l.n[0] + 3) / 4), 256, 0, stream>>>(t, mean_dist);

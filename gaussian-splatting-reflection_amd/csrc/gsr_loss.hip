@@ -15,17 +15,13 @@
 //   * photometric_bwd_kernel: the backward of the composites, dL/drgb = alpha dL/dv and dL/dalpha = sum_c (rgb[c] - background[c])
 //     dL/dv[c] in one pass over the channels.  Global traffic per pixel, C = 3: forward 2 C + 2 reads and 3 C writes of 4 B (the
 //     composed path adds ~10 plane passes of 3 x 4 B each way around the same kernels); backward 5 C + 2 reads, C + 1 writes.
-#include "gsr_internal.hpp"
+// Host side: the SSIM grid's limits, the compositing triple and the derivative planes are checked by gsr_ssim.hpp.
+#include "gsr_host.hpp"
 #include "gsr_reduce.hpp"
 #include "gsr_ssim.hpp"
 
 namespace gsr {
 
-struct Compositing {
-	const float* alpha;      // [H,W] or NULL: v = rgb * alpha + (1 - alpha) * background[c]
-	const float* gt_mask;    // [H,W] or NULL: g = gt * gt_mask + (1 - gt_mask) * background[c]
-	const float* background; // [C]
-};
 // t * a + (1 - a) * bg.  At a == 1 the result is t itself and at a == 0 it is bg, with or without a fused multiply-add.
 __device__ __forceinline__ float blend(float t, float a, float bg) { return t * a + (1.0f - a) * bg; }
 
@@ -236,7 +232,7 @@ extern "C" int gsr_ssim_l1_forward(const float* img1, const float* img2, int C, 
 	if (C < 0 || H < 0 || W < 0 || !sums) { set_error("gsr_ssim_l1_forward: invalid argument"); return GSR_E_INVALID; }
 	if (C == 0 || H == 0 || W == 0) { GSR_HIP_CHECK(hipMemsetAsync(sums, 0, 2 * sizeof(float), stream)); return 0; }
 	if (!scratch) { set_error("gsr_ssim_l1_forward: scratch of gsr_ssim_l1_scratch_floats(C,H,W) floats is required"); return GSR_E_INVALID; }
-	if (!img1 || !img2 || ((dm_dmu1 != nullptr) != (dm_dsigma1_sq != nullptr)) || ((dm_dmu1 != nullptr) != (dm_dsigma12 != nullptr))) {
+	if (!img1 || !img2 || !derivative_planes_ok(dm_dmu1, dm_dsigma1_sq, dm_dsigma12, false)) {
 		set_error("gsr_ssim_l1_forward: NULL image or partial set of derivative planes");
 		return GSR_E_INVALID;
 	}
@@ -251,7 +247,7 @@ extern "C" int gsr_ssim_l1_backward(const float* img1, const float* img2, int C,
 	hipStream_t stream = (hipStream_t)stream_;
 	if (C < 0 || H < 0 || W < 0) { set_error("gsr_ssim_l1_backward: invalid argument"); return GSR_E_INVALID; }
 	if (C == 0 || H == 0 || W == 0) return 0;
-	if (!img1 || !img2 || !weights || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1) {
+	if (!img1 || !img2 || !weights || !derivative_planes_ok(dm_dmu1, dm_dsigma1_sq, dm_dsigma12, true) || !dL_dimg1) {
 		set_error("gsr_ssim_l1_backward: NULL argument");
 		return GSR_E_INVALID;
 	}
@@ -264,15 +260,15 @@ extern "C" int gsr_photometric_forward(const float* rgb, const float* alpha, con
                                        int H, int W, float C1, float C2, float* sums, float* scratch, float* dm_dmu1, float* dm_dsigma1_sq,
                                        float* dm_dsigma12, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
-	if (C <= 0 || H <= 0 || W <= 0) { set_error("gsr_photometric_forward: invalid size C = %d, H = %d, W = %d", C, H, W); return GSR_E_INVALID; }
-	if (C > 65535 || ssim_tiles(H) > 65535) { set_error("gsr_photometric_forward: C and H / 32 are grid dimensions, at most 65535"); return GSR_E_INVALID; }
+	const Compositing cp = {alpha, gt_mask, background};
+	if (int rc = ssim_planes_check("gsr_photometric_forward", "C", C, H, W)) return rc;
 	if (!rgb || !gt || !sums || !scratch) { set_error("gsr_photometric_forward: NULL image, sums or scratch"); return GSR_E_INVALID; }
-	if ((alpha || gt_mask) && !background) { set_error("gsr_photometric_forward: alpha or gt_mask given without a background"); return GSR_E_INVALID; }
-	if (((dm_dmu1 != nullptr) != (dm_dsigma1_sq != nullptr)) || ((dm_dmu1 != nullptr) != (dm_dsigma12 != nullptr))) {
+	if (int rc = compositing_check("gsr_photometric_forward", cp)) return rc;
+	if (!derivative_planes_ok(dm_dmu1, dm_dsigma1_sq, dm_dsigma12, false)) {
 		set_error("gsr_photometric_forward: partial set of derivative planes (all three or none)");
 		return GSR_E_INVALID;
 	}
-	launch_loss_forward(rgb, gt, C, H, W, C1, C2, Compositing{alpha, gt_mask, background}, sums, scratch, nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, stream);
+	launch_loss_forward(rgb, gt, C, H, W, C1, C2, cp, sums, scratch, nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, stream);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }
@@ -281,16 +277,15 @@ extern "C" int gsr_photometric_backward(const float* rgb, const float* alpha, co
                                         int H, int W, const float* weights, const float* dm_dmu1, const float* dm_dsigma1_sq,
                                         const float* dm_dsigma12, float* dL_drgb, float* dL_dalpha, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
-	if (C <= 0 || H <= 0 || W <= 0) { set_error("gsr_photometric_backward: invalid size C = %d, H = %d, W = %d", C, H, W); return GSR_E_INVALID; }
-	if (ssim_tiles(H) > 65535) { set_error("gsr_photometric_backward: H / 32 is a grid dimension, at most 65535"); return GSR_E_INVALID; }
-	if (!rgb || !gt || !weights || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12) {
+	const Compositing cp = {alpha, gt_mask, background};
+	if (int rc = ssim_planes_check("gsr_photometric_backward", "C", C, H, W, false)) return rc;      // (the kernel loops over the channels)
+	if (!rgb || !gt || !weights || !derivative_planes_ok(dm_dmu1, dm_dsigma1_sq, dm_dsigma12, true)) {
 		set_error("gsr_photometric_backward: NULL image, weights or derivative plane");
 		return GSR_E_INVALID;
 	}
-	if ((alpha || gt_mask) && !background) { set_error("gsr_photometric_backward: alpha or gt_mask given without a background"); return GSR_E_INVALID; }
+	if (int rc = compositing_check("gsr_photometric_backward", cp)) return rc;
 	if (dL_dalpha && !alpha) { set_error("gsr_photometric_backward: dL_dalpha asked for without alpha"); return GSR_E_INVALID; }
 	if (!dL_drgb && !dL_dalpha) return 0;
-	const Compositing cp = {alpha, gt_mask, background};
 	dim3 grid(ssim_tiles(W), ssim_tiles(H), 1);
 	{
 		StageTimer st_(GSR_STAGE_LOSS_BWD, stream);
@@ -303,9 +298,8 @@ extern "C" int gsr_photometric_backward(const float* rgb, const float* alpha, co
 extern "C" int gsr_ssim_map_backward(const float* img1, const float* img2, int planes, int H, int W, const float* dL_dmap, const float* dm_dmu1,
                                      const float* dm_dsigma1_sq, const float* dm_dsigma12, float* dL_dimg1, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
-	if (planes <= 0 || H <= 0 || W <= 0) { set_error("gsr_ssim_map_backward: invalid size planes = %d, H = %d, W = %d", planes, H, W); return GSR_E_INVALID; }
-	if (planes > 65535 || ssim_tiles(H) > 65535) { set_error("gsr_ssim_map_backward: planes and H / 32 are grid dimensions, at most 65535"); return GSR_E_INVALID; }
-	if (!img1 || !img2 || !dL_dmap || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1) {
+	if (int rc = ssim_planes_check("gsr_ssim_map_backward", "planes", planes, H, W)) return rc;
+	if (!img1 || !img2 || !dL_dmap || !derivative_planes_ok(dm_dmu1, dm_dsigma1_sq, dm_dsigma12, true) || !dL_dimg1) {
 		set_error("gsr_ssim_map_backward: NULL argument");
 		return GSR_E_INVALID;
 	}

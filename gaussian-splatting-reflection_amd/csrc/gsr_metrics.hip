@@ -7,7 +7,8 @@
 //   * normal_mae_kernel: eval_mae.py / utils/mae_utils.py:3-29, the angle between predicted and ground-truth normals.
 // Block partials are added in a fixed order in double (block_sums and sums_reduce_kernel of gsr_reduce.hpp) and written to one row
 // of a caller-owned table: a test set needs one read-back at its end, and every number is bitwise reproducible.
-#include "gsr_internal.hpp"
+// Host side: sizes, the compositing triple, the table row and the scratch are checked by gsr_host.hpp and gsr_ssim.hpp.
+#include "gsr_host.hpp"
 #include "gsr_reduce.hpp"
 #include "gsr_ssim.hpp"
 
@@ -26,9 +27,7 @@ __device__ __forceinline__ float composite(float t, float a, float bg) {
 }
 
 struct Presentation {
-	const float* alpha;      // [H,W] or NULL: rendered image composited with clamp(alpha, 0, 1)
-	const float* gt_mask;    // [H,W] or NULL: ground truth composited with it
-	const float* background; // [C]
+	Compositing cp;          // (the rendered image is composited with clamp(alpha, 0, 1))
 	int clamp, quantize;
 };
 
@@ -42,7 +41,7 @@ image_metrics_kernel(const float* __restrict__ img, const float* __restrict__ gt
 	{
 		const float* const x = img + plane;
 		const float* const y = gt + plane;
-		const float bg = pr.background ? pr.background[blockIdx.z] : 0.f;
+		const float bg = pr.cp.background ? pr.cp.background[blockIdx.z] : 0.f;
 		float (*const dst[2])[SSIM_HALO + 1] = {ta, tb};
 		// the padding of the convolution surrounds the PRESENTED image: outside the image both planes stay zero
 		ssim_stage_tiles<2>([&](bool in, size_t o, float (&t)[2]) {
@@ -50,8 +49,8 @@ image_metrics_kernel(const float* __restrict__ img, const float* __restrict__ gt
 			if (in) {
 				v = x[o]; g = y[o];
 				if (pr.clamp) v = fminf(fmaxf(v, 0.f), 1.f);
-				if (pr.alpha) v = composite(v, fminf(fmaxf(pr.alpha[o], 0.f), 1.f), bg);
-				if (pr.gt_mask) g = composite(g, pr.gt_mask[o], bg);
+				if (pr.cp.alpha) v = composite(v, fminf(fmaxf(pr.cp.alpha[o], 0.f), 1.f), bg);
+				if (pr.cp.gt_mask) g = composite(g, pr.cp.gt_mask[o], bg);
 				if (pr.quantize) { v = quantize8(v); g = quantize8(g); }
 			}
 			t[0] = v; t[1] = g;
@@ -130,23 +129,18 @@ extern "C" int gsr_image_metrics(const float* img, const float* gt, int C, int H
                                  const float* background, double* row, float* scratch, size_t scratch_floats, uint8_t* img_u8, uint8_t* gt_u8,
                                  void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
-	if (C <= 0 || H <= 0 || W <= 0) { set_error("gsr_image_metrics: invalid size C = %d, H = %d, W = %d", C, H, W); return GSR_E_INVALID; }
-	if (C > 65535 || ssim_tiles(H) > 65535) { set_error("gsr_image_metrics: C and H / 32 are grid dimensions, at most 65535"); return GSR_E_INVALID; }
+	const Presentation pr = {{alpha, gt_mask, background}, (flags & GSR_PRESENT_CLAMP) != 0, (flags & GSR_PRESENT_QUANT8) != 0};
+	if (int rc = ssim_planes_check("gsr_image_metrics", "C", C, H, W)) return rc;
 	if (!img || !gt || !row) { set_error("gsr_image_metrics: NULL image or table row"); return GSR_E_INVALID; }
 	if (flags & ~(GSR_PRESENT_CLAMP | GSR_PRESENT_QUANT8)) { set_error("gsr_image_metrics: unknown presentation flags %d", flags); return GSR_E_INVALID; }
 	if ((img_u8 || gt_u8) && !(flags & GSR_PRESENT_QUANT8)) {
 		set_error("gsr_image_metrics: a uint8 output needs GSR_PRESENT_QUANT8 (it holds the quantised image)");
 		return GSR_E_INVALID;
 	}
-	if ((alpha || gt_mask) && !background) { set_error("gsr_image_metrics: alpha or gt_mask given without a background"); return GSR_E_INVALID; }
-	if (reinterpret_cast<uintptr_t>(row) & 7u) { set_error("gsr_image_metrics: the table row must be 8-byte aligned; got %p", (const void*)row); return GSR_E_INVALID; }
+	if (int rc = compositing_check("gsr_image_metrics", pr.cp)) return rc;
+	if (int rc = aligned_check("gsr_image_metrics", "the table row", row, 8)) return rc;
 	const size_t blocks = image_metrics_blocks(C, H, W);
-	if (!scratch || scratch_floats < 4 * blocks) {
-		set_error("gsr_image_metrics: scratch of %zu floats given, gsr_image_metrics_scratch_floats(C,H,W) = %zu needed", scratch ? scratch_floats : (size_t)0, 4 * blocks);
-		return GSR_E_INVALID;
-	}
-	GSR_REQUIRE_ALIGNED16_IN("gsr_image_metrics", scratch, "scratch");
-	const Presentation pr = {alpha, gt_mask, background, (flags & GSR_PRESENT_CLAMP) != 0, (flags & GSR_PRESENT_QUANT8) != 0};
+	if (int rc = scratch_check("gsr_image_metrics", scratch, scratch_floats, 4 * blocks, "floats", "gsr_image_metrics_scratch_floats(C,H,W)", 16)) return rc;
 	dim3 grid(ssim_tiles(W), ssim_tiles(H), C);
 	image_metrics_kernel<<<grid, 256, 0, stream>>>(img, gt, H, W, ssim_window(), (float)(0.01 * 0.01), (float)(0.03 * 0.03), pr, (float4*)scratch, img_u8, gt_u8);
 	sums_reduce_kernel<3, 4, true><<<1, 256, 0, stream>>>(scratch, blocks, row, (double)C * H * W);
@@ -162,17 +156,14 @@ extern "C" size_t gsr_normal_mae_scratch_floats(int H, int W) {
 extern "C" int gsr_normal_mae(const float* pred, const float* gt, int H, int W, float pred_divisor, float gt_divisor, float eps, double* row,
                               float* scratch, size_t scratch_floats, float* error_map, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
+	// (not image_check and positive_finite: H * W from 2^31 on and an infinite divisor are accepted here)
 	if (H <= 0 || W <= 0) { set_error("gsr_normal_mae: invalid size H = %d, W = %d", H, W); return GSR_E_INVALID; }
 	if (!pred || !gt || !row) { set_error("gsr_normal_mae: NULL normals or table row"); return GSR_E_INVALID; }
 	if (!(pred_divisor > 0.f) || !(gt_divisor > 0.f) || !(eps >= 0.f)) { set_error("gsr_normal_mae: divisors must be positive and eps non-negative"); return GSR_E_INVALID; }
-	if (reinterpret_cast<uintptr_t>(row) & 7u) { set_error("gsr_normal_mae: the table row must be 8-byte aligned; got %p", (const void*)row); return GSR_E_INVALID; }
+	if (int rc = aligned_check("gsr_normal_mae", "the table row", row, 8)) return rc;
 	const size_t HW = (size_t)H * W;
 	const size_t blocks = stream_blocks(HW);
-	if (!scratch || scratch_floats < 4 * blocks) {
-		set_error("gsr_normal_mae: scratch of %zu floats given, gsr_normal_mae_scratch_floats(H,W) = %zu needed", scratch ? scratch_floats : (size_t)0, 4 * blocks);
-		return GSR_E_INVALID;
-	}
-	GSR_REQUIRE_ALIGNED16_IN("gsr_normal_mae", scratch, "scratch");
+	if (int rc = scratch_check("gsr_normal_mae", scratch, scratch_floats, 4 * blocks, "floats", "gsr_normal_mae_scratch_floats(H,W)", 16)) return rc;
 	normal_mae_kernel<<<(unsigned)blocks, 256, 0, stream>>>(pred, gt, HW, pred_divisor, gt_divisor, eps, (float4*)scratch, error_map);
 	sums_reduce_kernel<3, 4, true><<<1, 256, 0, stream>>>(scratch, blocks, row, (double)HW);
 	GSR_LAUNCH_CHECK(0, stream);

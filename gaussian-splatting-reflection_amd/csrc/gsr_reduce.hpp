@@ -3,15 +3,11 @@
 // atomics: the order of every addition is fixed by the code, so the sums are bitwise reproducible, and that order is part of the
 // library's contract ("Block sums").  (Thousands of blocks adding into ONE address serialise at the memory side: measured
 // 0.32 ms for the 1080p loss with atomics, see DESIGN.md.)
+// (The grid of such a pass, stream_blocks, and the size of its partial buffer are gsr_host.hpp's.)
 #pragma once
-#include <algorithm>
 #include <hip/hip_runtime.h>
 
 namespace gsr {
-
-// Blocks of a grid-stride pass over n elements, 256 per block and trip: they fill the device and one block can add their partials.
-#define STREAM_BLOCKS_MAX 1024
-inline unsigned stream_blocks(size_t n) { return (unsigned)std::min<size_t>(STREAM_BLOCKS_MAX, (n + 255) / 256); }
 
 // ---- wave64 sums.  Classic GCN reduction: row_shr 1,2,4,8 inside each row of 16 lanes, then
 // row_bcast:15 / row_bcast:31 across the four rows; the total lands in lane 63.  hipcc does not fuse

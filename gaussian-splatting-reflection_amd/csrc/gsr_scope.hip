@@ -6,7 +6,7 @@
 //     each block leaves (sum of refl, count) over its outside points, sums_reduce_kernel adds the pairs in double in a fixed order.
 //   * backward: 1 mask byte read and 4 B of gradient written per point (accumulate: read and written on outside rows only).
 #include <cmath>
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include "../../include/gsr_hip_scope.h"
 #include "gsr_reduce.hpp"
 
@@ -70,13 +70,14 @@ env_scope_bwd_kernel(const uint8_t* __restrict__ outside, const float* __restric
 
 using namespace gsr;
 
-extern "C" size_t gsr_env_scope_scratch_floats(void) { return 2 * STREAM_BLOCKS_MAX; }
+extern "C" size_t gsr_env_scope_scratch_floats(void) { return stream_partials(2); }
 
 extern "C" int gsr_env_scope_forward(int P, const float* means3D, const float* refl, float cx, float cy, float cz, float radius2, uint8_t* inside,
                                      uint8_t* outside, float* sums, float* scratch, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
 	if (P < 0) { set_error("gsr_env_scope_forward: invalid size (P = %d)", P); return GSR_E_INVALID; }
-	if (!std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(cz)) { set_error("gsr_env_scope_forward: the centre is not finite"); return GSR_E_INVALID; }
+	if (int rc = finite_check("gsr_env_scope_forward", "centre", cx, cy, cz)) return rc;
+	// (not placement_check: a radius of zero is a scope, an empty one)
 	if (!std::isfinite(radius2) || radius2 < 0.f) { set_error("gsr_env_scope_forward: radius2 must be finite and not negative"); return GSR_E_INVALID; }
 	if (P == 0) {
 		// nothing is read and no mask is written; a caller that asks for the sums gets (0, 0): the second stage over no block at all
@@ -116,7 +117,7 @@ extern "C" int gsr_env_scope_backward(int P, const uint8_t* outside, const float
 	if (accumulate != 0 && accumulate != 1) { set_error("gsr_env_scope_backward: accumulate must be 0 or 1 (got %d)", accumulate); return GSR_E_INVALID; }
 	if (P == 0) return 0;
 	const size_t n = (size_t)P;
-	const unsigned blocks = (unsigned)((n + 255) / 256);
+	const unsigned blocks = blocks_of(n);
 	{
 		StageTimer st_(GSR_STAGE_LOSS_BWD, stream);
 		if (accumulate) env_scope_bwd_kernel<true><<<blocks, 256, 0, stream>>>(outside, sums, g_loss, n, grad_refl);

@@ -33,6 +33,32 @@ inline const SsimWindow& ssim_window() {
 }
 // tiles along an image side of n pixels
 inline int ssim_tiles(int n) { return (n + SSIM_T - 1) / SSIM_T; }
+// What an entry that launches a (ssim_tiles(W), ssim_tiles(H), planes) grid refuses first: an empty size, then a grid dimension past
+// the limit.  `planes_name`: what the entry calls its planes ("C", "planes").  planes_in_grid = false: the kernel loops over them.
+static inline int ssim_planes_check(const char* entry, const char* planes_name, int planes, int H, int W, bool planes_in_grid = true) {
+	if (planes <= 0 || H <= 0 || W <= 0) { set_error("%s: invalid size %s = %d, H = %d, W = %d", entry, planes_name, planes, H, W); return GSR_E_INVALID; }
+	const bool tall = ssim_tiles(H) > 65535;
+	if (planes_in_grid && (planes > 65535 || tall)) { set_error("%s: %s and H / 32 are grid dimensions, at most 65535", entry, planes_name); return GSR_E_INVALID; }
+	if (tall) { set_error("%s: H / 32 is a grid dimension, at most 65535", entry); return GSR_E_INVALID; }
+	return 0;
+}
+
+// What the loss and the metrics composite with before they compare: v = rgb * alpha + (1 - alpha) * background[c], and the ground truth
+// likewise with gt_mask.  A kernel argument (Presentation of gsr_metrics.hip begins with it).
+struct Compositing {
+	const float* alpha;      // [H,W] or NULL
+	const float* gt_mask;    // [H,W] or NULL
+	const float* background; // [C]
+};
+static inline int compositing_check(const char* entry, const Compositing& cp) {
+	if ((cp.alpha || cp.gt_mask) && !cp.background) { set_error("%s: alpha or gt_mask given without a background", entry); return GSR_E_INVALID; }
+	return 0;
+}
+// The three derivative planes of the SSIM map travel together: all three where a backward requires them, otherwise all three or none.
+static inline bool derivative_planes_ok(const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12, bool required) {
+	const int given = (dm_dmu1 != nullptr) + (dm_dsigma1_sq != nullptr) + (dm_dsigma12 != nullptr);
+	return given == 3 || (!required && given == 0);
+}
 
 #ifdef __HIPCC__
 // Stage the zero-padded halo tiles of NS planes into LDS.  `fetch(in, o, t)` gives the NS values of the pixel at offset o of

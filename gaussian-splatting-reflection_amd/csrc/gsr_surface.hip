@@ -164,6 +164,7 @@ surface_bwd_kernel(const float* __restrict__ allmap, const float* __restrict__ r
 
 using namespace gsr;
 
+// (both keep their own size test, not gsr_host.hpp's image_check: an empty image is a no-op here and H * W from 2^31 on is accepted)
 extern "C" int gsr_surface_forward(const float* allmap, const float* raymat, float depth_ratio, int H, int W, float* surf_depth,
                                    float* surf_normal, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;

@@ -7,7 +7,7 @@
 // pairs for packed fp32 math:  {x, y | Tu.x, Tv.x} {Tu.y, Tv.y | Tu.z, Tv.z} {Tw.x, Tw.y | Tw.z, opacity} {n.x, n.y | n.z, refl}
 // {r, g | b, mask}   (Tu, Tv, Tw = rows of the 3x3 homography "transMat").
 #include <type_traits>
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include "gsr_tile_walk.hpp"
 #include "gsr_sort.hpp"
 #include "gsr_math.hpp"
@@ -1271,7 +1271,7 @@ using namespace gsr;
 // width, height: of the image whose keys `scratch` will sort (the training forward; the eval forward takes neither keys nor scratch).
 static int check_refl_descriptor(const char* entry, const gsr_refl_forward* refl, int width, int height) {
 	if (!refl) return 0;
-	if (!refl->cam || !refl->cubemap || !refl->fail_value || refl->L == 0 || !refl->cubemap_rgba || ((uintptr_t)refl->cubemap_rgba & 15) != 0 ||
+	if (!refl->cam || !refl->cubemap || !refl->fail_value || refl->L == 0 || !refl->cubemap_rgba || misaligned(refl->cubemap_rgba, 16) ||
 	    !refl->out_final || !refl->out_refl_color || !refl->out_normal_world) {
 		set_error("%s: incomplete reflection descriptor (cam, cubemap, fail_value, L, 16-byte aligned cubemap_rgba and the three outputs are required)", entry);
 		return GSR_E_INVALID;

@@ -5,7 +5,7 @@
 //     by segment table, so the 59 floats per Gaussian + cubemap update in a single launch.  A streaming, HBM-bound pass.
 //   * Raw-parameter step: the same pass with a per-segment activation (sigmoid, exp, normalize): chain rule in, activated copy out.
 #include <cstring>
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include "../../include/gsr_hip_train.h"   // the raw-parameter step's entries (added under ABI 102, declared apart from gsr_hip.h)
 #include "gsr_reduce.hpp"
 
@@ -161,8 +161,7 @@ static int adam_segments(const char* entry, const float* act, uint64_t n, uint64
 		s.kind[i] = g.kind; s.act_begin[i] = g.act_begin;
 	}
 	if (prev != n) { set_error("%s: segments must tile [0, n) in order", entry); return GSR_E_INVALID; }
-	if (((uintptr_t)act & 15u) != 0) { set_error("%s: act must be 16-byte aligned", entry); return GSR_E_INVALID; }
-	return 0;
+	return aligned_check(entry, "act", act, 16);
 }
 
 // The host side of every Adam entry: all checks, the bias corrections, the one launch.  The buffers are device memory, and exp_avg /
@@ -177,10 +176,7 @@ static int adam_step(const char* entry, float* raw, const float* grad, float* ex
 		return GSR_E_INVALID;
 	}
 	if (!raw || !grad || !exp_avg || !exp_avg_sq || step < 1) { set_error("%s: invalid argument (NULL buffer or step < 1)", entry); return GSR_E_INVALID; }
-	if ((((uintptr_t)raw | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15u) != 0) {
-		set_error("%s: buffers must be 16-byte aligned", entry);
-		return GSR_E_INVALID;
-	}
+	if (int rc = pointers_check(entry, {raw, grad, exp_avg, exp_avg_sq}, 16, "buffers")) return rc;
 	AdamSegs s;
 	if (int rc = adam_segments(entry, act, n, n_act, segments, num_segments, s)) return rc;
 	// bias corrections in double on the host, as Python floats are in torch/optim/adam.py
@@ -189,7 +185,7 @@ static int adam_step(const char* entry, float* raw, const float* grad, float* ex
 	const unsigned long long nvec = (range_end - range_begin + 3) / 4;
 	{
 		StageTimer st_(GSR_STAGE_ADAM, stream);
-		adam_kernel<true><<<(unsigned)((nvec + 255) / 256), 256, 0, stream>>>(raw, grad, exp_avg, exp_avg_sq, act, range_begin, range_end, s, beta1, beta2, eps,
+		adam_kernel<true><<<blocks_of(nvec), 256, 0, stream>>>(raw, grad, exp_avg, exp_avg_sq, act, range_begin, range_end, s, beta1, beta2, eps,
 		                                                                      (float)bc1, (float)sqrt(bc2));
 	}
 	GSR_LAUNCH_CHECK(0, stream);
@@ -230,13 +226,13 @@ extern "C" int gsr_activate(const float* raw, float* act, uint64_t n, uint64_t n
 	hipStream_t stream = (hipStream_t)stream_;
 	if (n == 0) return 0;
 	if (!raw) { set_error("gsr_activate: invalid argument (NULL raw)"); return GSR_E_INVALID; }
-	if (((uintptr_t)raw & 15u) != 0) { set_error("gsr_activate: raw must be 16-byte aligned"); return GSR_E_INVALID; }
+	if (int rc = aligned_check("gsr_activate", "raw", raw, 16)) return rc;
 	AdamSegs s;
 	if (int rc = adam_segments("gsr_activate", act, n, n_act, segments, num_segments, s)) return rc;
 	const unsigned long long nvec = (n + 3) / 4;
 	{
 		StageTimer st_(GSR_STAGE_ADAM, stream);
-		adam_kernel<false><<<(unsigned)((nvec + 255) / 256), 256, 0, stream>>>(const_cast<float*>(raw), nullptr, nullptr, nullptr, act, 0ull, n, s, 0.f, 0.f,
+		adam_kernel<false><<<blocks_of(nvec), 256, 0, stream>>>(const_cast<float*>(raw), nullptr, nullptr, nullptr, act, 0ull, n, s, 0.f, 0.f,
 		                                                                           0.f, 1.f, 1.f);
 	}
 	GSR_LAUNCH_CHECK(0, stream);
@@ -275,7 +271,8 @@ normal_loss_bwd_kernel(const float* __restrict__ rend, const float* __restrict__
 		g_surf[c * HW + p] = g * r;
 	}
 }
-extern "C" size_t gsr_normal_loss_scratch_floats(void) { return 2 * STREAM_BLOCKS_MAX; }
+// (both entries keep their own size test, not image_check: they accept H * W from 2^31 on; DESIGN.md, "Out of scope / next")
+extern "C" size_t gsr_normal_loss_scratch_floats(void) { return stream_partials(2); }
 extern "C" int gsr_normal_loss_forward(const float* rend_normal, const float* surf_normal, const float* mask, int H, int W, float* sum2,
                                        float* scratch, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
@@ -295,7 +292,7 @@ extern "C" int gsr_normal_loss_backward(const float* rend_normal, const float* s
 		return GSR_E_INVALID;
 	}
 	const size_t HW = (size_t)H * W;
-	normal_loss_bwd_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, stream>>>(rend_normal, surf_normal, mask, HW, g_sum, g_rend_normal, g_surf_normal);
+	normal_loss_bwd_kernel<<<blocks_of(HW), 256, 0, stream>>>(rend_normal, surf_normal, mask, HW, g_sum, g_rend_normal, g_surf_normal);
 	GSR_LAUNCH_CHECK(0, stream);
 	return 0;
 }

@@ -9,7 +9,7 @@
 //                          LDS beside its 8-bit form, both filled once per block.
 // The colour index is the reference's float32 arithmetic bit for bit: subtract, IEEE divide, multiply, round half to even, each
 // rounded on its own.  Contraction is switched off for the whole file (hipcc would turn a * b + c into one rounding).
-#include "gsr_internal.hpp"
+#include "gsr_host.hpp"
 #include <algorithm>
 
 #pragma clang fp contract(off)
@@ -267,6 +267,7 @@ extern "C" size_t gsr_present_view_scratch_floats(int C, int H, int W, int flags
 extern "C" int gsr_present_view(const float* src, int C, int H, int W, int flags, const float* table, float* out_f32, uint8_t* out_u8,
                                 float* scratch, size_t scratch_floats, void* stream_) {
 	hipStream_t stream = (hipStream_t)stream_;
+	// (its own size test: no SSIM grid here, and W has a limit of its own)
 	if (C <= 0 || H <= 0 || W <= 0 || W > (1 << 30)) { set_error("gsr_present_view: invalid size C = %d, H = %d, W = %d", C, H, W); return GSR_E_INVALID; }
 	if (C != 1 && C != 3) { set_error("gsr_present_view: C = %d channels, expected 1 or 3", C); return GSR_E_INVALID; }
 	if (!src) { set_error("gsr_present_view: NULL src"); return GSR_E_INVALID; }
@@ -281,14 +282,9 @@ extern "C" int gsr_present_view(const float* src, int C, int H, int W, int flags
 	if (lut && !table) { set_error("gsr_present_view: GSR_VIEW_COLORMAP without a colour table"); return GSR_E_INVALID; }
 	const size_t HW = (size_t)H * W;
 	const size_t need = gsr_present_view_scratch_floats(C, H, W, flags);
-	if (lut) {
-		if (!scratch || scratch_floats < need) {
-			set_error("gsr_present_view: scratch of %zu floats given, gsr_present_view_scratch_floats(C,H,W,flags) = %zu needed", scratch ? scratch_floats : (size_t)0, need);
-			return GSR_E_INVALID;
-		}
-		GSR_REQUIRE_ALIGNED16_IN("gsr_present_view", scratch, "scratch");
-	}
-	const size_t bx = ((size_t)W + 255) / 256, by = ((size_t)H + 3) / 4;
+	if (lut)
+		if (int rc = scratch_check("gsr_present_view", scratch, scratch_floats, need, "floats", "gsr_present_view_scratch_floats(C,H,W,flags)", 16)) return rc;
+	const size_t bx = blocks_of((size_t)W), by = ((size_t)H + 3) / 4;
 	const size_t sx = ((size_t)W + VIEW_TILE_W - 1) / VIEW_TILE_W, sy = ((size_t)H + VIEW_TILE_H - 1) / VIEW_TILE_H;
 	if (bx * by > 0x7fffffffu || sx * sy > 0x7fffffffu) { set_error("gsr_present_view: invalid size H = %d, W = %d: more than 2^31 blocks", H, W); return GSR_E_INVALID; }
 	uint32_t* const slots = (uint32_t*)scratch;
