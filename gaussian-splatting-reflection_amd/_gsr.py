@@ -189,6 +189,15 @@ ABI = [
         ("gsr_tsdf_integrate_contracted", I, [P, P, I, F, F, F, F, F, F, F, P, I, I, P, P, P]),
         ("gsr_points_fuse_view", I, [P, U64, P, P, P, P, I, I, P, P, F, P]),
         ("gsr_uncontract_points", I, [P, P, U64, F, F, F, F, F, P])]),
+    # the block-sparse TSDF volume: gsr_mesh.SparseTSDFVolume, utils.mesh_utils extract_mesh_bounded(sparse=True)
+    ("gsr_hip_sparse.h", "csrc/gsr_sparse.hip", True, [
+        ("gsr_sparse_tsdf_touch", I, [P, I, I, I, F, F, F, F, P, P, F, I, I, P, P, F, F, P]),
+        ("gsr_sparse_tsdf_allocate_scratch_bytes", c_size_t, [I, I, I]),
+        ("gsr_sparse_tsdf_allocate", I, [P, I, I, I, P, U64, P, P, c_size_t, P]),
+        ("gsr_sparse_tsdf_integrate", I, [P, U64, U64, P, P, P, I, I, I, F, F, F, F, P, P, P, F, I, I, P, P, F, F, P]),
+        ("gsr_sparse_mesh_scratch_bytes", c_size_t, [U64]),
+        ("gsr_sparse_mesh_count", I, [P, P, U64, U64, P, P, I, I, I, F, P, c_size_t, P, P]),
+        ("gsr_sparse_mesh_emit", I, [P, P, U64, U64, P, P, P, I, I, I, F, F, F, F, F, P, P, P, P, U64, U64, P])]),
 ]
 
 ENTRIES_BY_HEADER = {}          # {header file name: [entry names]}, what tests/test_cabi.py holds each header to

@@ -19,7 +19,7 @@ OUT = os.path.join(PKG, "libgsr_hip.so")
 OBJ_DIR = os.path.join(HERE, "_obj")
 SOURCES = ["gsr_common.hip", "gsr_gauss.hip", "gsr_surfel.hip", "gsr_cubemap.hip", "gsr_train.hip", "gsr_surface.hip", "gsr_densify.hip", "gsr_knn.hip",
            "gsr_metrics.hip", "gsr_viewer.hip", "gsr_loss.hip", "gsr_scope.hip", "gsr_envmap.hip", "gsr_mesh.hip", "gsr_meshclean.hip",
-           "gsr_unbounded.hip"]
+           "gsr_unbounded.hip", "gsr_sparse.hip"]
 
 
 def local_headers(sources=SOURCES):

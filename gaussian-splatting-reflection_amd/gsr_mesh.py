@@ -6,6 +6,9 @@ voxel grid, `TSDFVolume.extract` pulls the iso-surface out as an indexed triangl
 it.  Everything stays on the device; the one read-back is the 16 bytes that hold the vertex and triangle counts.  The reference took
 this from open3d (ScalableTSDFVolume) on the host; utils/mesh_utils.py has its GaussianExtractor on top of this module.
 
+`SparseTSDFVolume` is TSDFVolume in blocks of 8 x 8 x 8 nodes with storage only near the surface (include/gsr_hip_sparse.h,
+csrc/gsr_sparse.hip): the same surface where the dense volume fits, and boxes of upstream's voxel size where it cannot exist.
+
 `ContractedTSDFVolume` is the same for scenes that do not end at a box (include/gsr_hip_unbounded.h, csrc/gsr_unbounded.hip): the lattice
 lies in contracted space, `extract` maps the vertices back to the world, and `color_vertices` colours them from the views afterwards.
 
@@ -113,6 +116,160 @@ class TSDFVolume:
         """The iso-surface tsdf = 0 over the cells whose eight nodes have weight >= min_weight, as Mesh(vertices, faces, colors) on the
         device; an empty surface gives empty tensors.  Waits once, for the two counts."""
         return _iso_surface(self.tsdf, self.weight, self.color, self.dims, self.origin, self.voxel_size, min_weight, self.device)
+
+
+MAX_BLOCKS = 2 ** 31 - 1          # blocks of 8 x 8 x 8 nodes in the box of a SparseTSDFVolume
+MAX_SLOTS = 2 ** 22 - 1           # slots of its pool: 512 nodes each, below 2^31 in all
+
+
+def sparse_blocks(dims):
+    """(gx, gy, gz) of the block grid of a SparseTSDFVolume of `dims` nodes."""
+    return tuple((int(d) + 7) // 8 for d in dims)
+
+
+class SparseTSDFVolume:
+    """The volume of TSDFVolume (dims = (nx, ny, nz) nodes, node (i, j, k) at origin + voxel_size * (i, j, k)) stored in blocks of 8 x 8 x 8
+    nodes, of which only those near the surface get storage (include/gsr_hip_sparse.h): a direct table of one int32 per block, and a pool
+    of tsdf [capacity, 512], weight [capacity, 512] and, with color=True, color [capacity, 3, 512].  Use it in two phases: `touch` every
+    view, `allocate` once, `integrate` every view, `extract`; the surface is then the dense volume's.  The limits are 2^31 - 1 blocks in
+    the box and 2^22 - 1 allocated blocks, where the dense volume stops at 2^31 - 1 nodes."""
+
+    def __init__(self, origin, voxel_size, dims, device, color=True):
+        _gsr.require_entry(lib, "gsr_sparse_tsdf_touch")
+        self.origin = tuple(float(c) for c in origin)
+        self.voxel_size = float(voxel_size)
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.origin) != 3 or len(self.dims) != 3:
+            raise ValueError("SparseTSDFVolume: origin and dims have three components")
+        self.grid = sparse_blocks(self.dims)
+        if min(self.dims) < 2 or self.grid[0] * self.grid[1] * self.grid[2] > MAX_BLOCKS:
+            raise ValueError(f"SparseTSDFVolume: every dimension must be at least 2 and the box hold fewer than 2^31 blocks of 8 x 8 x 8 nodes "
+                             f"(got {self.dims})")
+        if not (np.isfinite(self.voxel_size) and self.voxel_size > 0):
+            raise ValueError(f"SparseTSDFVolume: voxel_size must be positive and finite (got {voxel_size})")
+        self.device = torch.device(device)
+        self.has_color = bool(color)
+        self.table = torch.full((self.grid[0] * self.grid[1] * self.grid[2],), -1, dtype=torch.int32, device=self.device)
+        self.device = self.table.device                       # ("cuda" as "cuda:0": what the views' tensors are compared with)
+        self.counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self._blocks = 0
+        self._pool(0)
+
+    def _pool(self, capacity):
+        """A zeroed pool of `capacity` slots with the slots in use copied over."""
+        old = (self.block_of_slot, self.tsdf, self.weight, self.color) if capacity else None
+        dev, n = self.device, self._blocks
+        self.block_of_slot = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        self.tsdf = torch.zeros((capacity, 512), dtype=torch.float32, device=dev)
+        self.weight = torch.zeros((capacity, 512), dtype=torch.float32, device=dev)
+        self.color = torch.zeros((capacity, 3, 512), dtype=torch.float32, device=dev) if self.has_color else None
+        if old is not None and n:
+            for new, was in zip((self.block_of_slot, self.tsdf, self.weight, self.color), old):
+                if new is not None:
+                    new[:n].copy_(was[:n])
+
+    blocks = property(lambda self: self._blocks, doc="allocated blocks (slots in use)")
+    capacity = property(lambda self: int(self.tsdf.shape[0]), doc="slots of the pool")
+
+    @property
+    def nbytes(self):
+        """Bytes of the table and the pool."""
+        return sum(t.numel() * t.element_size() for t in (self.table, self.block_of_slot, self.tsdf, self.weight, self.color) if t is not None)
+
+    def reset(self):
+        """A fresh volume: no block touched, none allocated; the pool is kept and zeroed."""
+        self.table.fill_(-1)
+        self.counts.zero_()
+        self._blocks = 0
+        for t in (self.tsdf, self.weight, self.color):
+            if t is not None:
+                t.zero_()
+
+    def _truncations(self, who, sdf_trunc, depth_trunc):
+        if depth_trunc is None:
+            raise ValueError(f"SparseTSDFVolume.{who}: depth_trunc is required")
+        return (5.0 * self.voxel_size if sdf_trunc is None else float(sdf_trunc)), float(depth_trunc)
+
+    def touch(self, depth, camera, alpha=None, alpha_min=0.5, sdf_trunc=None, depth_trunc=None):
+        """Marks the blocks this view's truncation band reaches (gsr_sparse_tsdf_touch), with a margin of one node; the arguments are
+        integrate's, and must be the same for the surface to be the dense one.  Runs on the current stream; nothing is read back."""
+        sdf_trunc, depth_trunc = self._truncations("touch", sdf_trunc, depth_trunc)
+        W, H, view, proj, maps = _view_inputs("SparseTSDFVolume.touch", "the volume", camera, self.device, depth=(depth, 1), alpha=(alpha, 1))
+        with torch.cuda.device(self.device):
+            check(lib.gsr_sparse_tsdf_touch(ptr(self.table), *self.dims, *self.origin, self.voxel_size, ptr(maps["depth"]), ptr(maps["alpha"]),
+                                            float(alpha_min), W, H, ptr(view), ptr(proj), sdf_trunc, depth_trunc, stream_ptr(self.device)),
+                  "gsr_sparse_tsdf_touch")
+
+    def _allocate_once(self, scratch):
+        with torch.cuda.device(self.device):
+            check(lib.gsr_sparse_tsdf_allocate(ptr(self.table), *self.dims, ptr(self.block_of_slot), self.capacity, ptr(self.counts), ptr(scratch),
+                                               scratch.numel(), stream_ptr(self.device)), "gsr_sparse_tsdf_allocate")
+
+    def allocate(self):
+        """Gives every touched block a slot, in ascending block index behind the slots in use (gsr_sparse_tsdf_allocate), growing the pool
+        when it is too small: a larger zeroed pool, the old slots copied, the entry run again (every waiting block then fits, so its
+        counts are known).  Returns the number of allocated blocks.  Waits once, for the 16 bytes of the two counts."""
+        scratch = torch.empty(int(lib.gsr_sparse_tsdf_allocate_scratch_bytes(*self.dims)), dtype=torch.uint8, device=self.device)
+        self._allocate_once(scratch)
+        allocated, wanted = (int(c) for c in self.counts.tolist())
+        self._blocks = allocated
+        if wanted > allocated:
+            if wanted > MAX_SLOTS:
+                raise ValueError(f"SparseTSDFVolume.allocate: {wanted} blocks are wanted, beyond the 2^22 - 1 of a pool (512 nodes each, below 2^31 "
+                                 "nodes in all)")
+            self._pool(wanted)
+            self._allocate_once(scratch)
+            self._blocks = wanted
+        return self._blocks
+
+    def integrate(self, depth, camera, rgb=None, alpha=None, alpha_min=0.5, sdf_trunc=None, depth_trunc=None):
+        """Fuses one view into the allocated blocks (gsr_sparse_tsdf_integrate); TSDFVolume.integrate's arguments.  Runs on the current
+        stream; nothing is read back."""
+        sdf_trunc, depth_trunc = self._truncations("integrate", sdf_trunc, depth_trunc)
+        if (rgb is None) != (self.color is None):
+            raise ValueError("SparseTSDFVolume.integrate: rgb is given exactly when the volume holds colour")
+        W, H, view, proj, maps = _view_inputs("SparseTSDFVolume.integrate", "the volume", camera, self.device, depth=(depth, 1), rgb=(rgb, 3),
+                                              alpha=(alpha, 1))
+        with torch.cuda.device(self.device):
+            check(lib.gsr_sparse_tsdf_integrate(ptr(self.block_of_slot), self._blocks, self.capacity, ptr(self.tsdf), ptr(self.weight), ptr(self.color),
+                                                *self.dims, *self.origin, self.voxel_size, ptr(maps["depth"]), ptr(maps["rgb"]), ptr(maps["alpha"]),
+                                                float(alpha_min), W, H, ptr(view), ptr(proj), sdf_trunc, depth_trunc, stream_ptr(self.device)),
+                  "gsr_sparse_tsdf_integrate")
+
+    def extract(self, min_weight=1.0):
+        """The iso-surface over the allocated blocks (gsr_sparse_mesh_count, gsr_sparse_mesh_emit) as Mesh(vertices, faces, colors) on the
+        device, vertices and faces in pool order; an empty surface gives empty tensors.  Waits once, for the two counts."""
+        dev, n = self.device, self._blocks
+        scratch = torch.empty(int(lib.gsr_sparse_mesh_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        pool = (ptr(self.table), ptr(self.block_of_slot), n, self.capacity, ptr(self.tsdf), ptr(self.weight))
+        with torch.cuda.device(dev):
+            check(lib.gsr_sparse_mesh_count(*pool, *self.dims, float(min_weight), ptr(scratch), scratch.numel(), ptr(counts), stream_ptr(dev)),
+                  "gsr_sparse_mesh_count")
+            nV, nT = (int(c) for c in counts.tolist())
+            verts = torch.empty((nV, 3), dtype=torch.float32, device=dev)
+            faces = torch.empty((nT, 3), dtype=torch.int32, device=dev)
+            colors = None if self.color is None else torch.empty((nV, 3), dtype=torch.float32, device=dev)
+            check(lib.gsr_sparse_mesh_emit(*pool, ptr(self.color), *self.dims, *self.origin, self.voxel_size, float(min_weight), ptr(scratch),
+                                           ptr(verts), ptr(colors), ptr(faces), nV, nT, stream_ptr(dev)), "gsr_sparse_mesh_emit")
+        return Mesh(verts, faces, colors)
+
+    def to_dense(self):
+        """(tsdf [nz, ny, nx], weight [nz, ny, nx], color [3, nz, ny, nx] | None) as TSDFVolume lays them out, zeros where nothing is
+        allocated: torch ops, for volumes below 2^31 nodes (what tests compare)."""
+        nx, ny, nz = self.dims
+        gx, gy, gz = self.grid
+        if nx * ny * nz > MAX_NODES:
+            raise ValueError(f"SparseTSDFVolume.to_dense: nx * ny * nz must be below 2^31 (got {self.dims})")
+        n, b = self._blocks, self.block_of_slot[:self._blocks].long()
+
+        def dense(pool, channels):
+            full = torch.zeros((gx * gy * gz, channels, 8, 8, 8), dtype=torch.float32, device=self.device)
+            full[b] = pool[:n].reshape(n, channels, 8, 8, 8)
+            # [bk, bj, bi, c, lk, lj, li] -> [c, bk, lk, bj, lj, bi, li]
+            full = full.reshape(gz, gy, gx, channels, 8, 8, 8).permute(3, 0, 4, 1, 5, 2, 6).reshape(channels, gz * 8, gy * 8, gx * 8)
+            return full[:, :nz, :ny, :nx].contiguous()
+        return dense(self.tsdf, 1)[0], dense(self.weight, 1)[0], None if self.color is None else dense(self.color, 3)
 
 
 class ContractedTSDFVolume:

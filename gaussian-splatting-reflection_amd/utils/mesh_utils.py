@@ -71,12 +71,16 @@ class GaussianExtractor:
         return centre, float((centres - centre).norm(dim=1).max())
 
     @torch.no_grad()
-    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True, bounds=None):
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True, bounds=None, sparse=False):
         """The bounded TSDF extraction upstream 2DGS calls by this name (the `mask_backgrond` spelling is upstream's): every kept view
         is fused into one dense volume of `voxel_size` nodes over `bounds` = ((xmin, ymin, zmin), (xmax, ymax, zmax)), truncated at
         `sdf_trunc` and ignoring depths beyond `depth_trunc`; with mask_backgrond, pixels whose rendered alpha is below 0.5 are left
         out.  bounds=None: the box around the sphere about the mean camera centre that holds every camera centre.  Returns
-        gsr_mesh.Mesh(vertices, faces, colors) on the device.  A box that needs 2^31 nodes or more: ValueError."""
+        gsr_mesh.Mesh(vertices, faces, colors) on the device.  A box that needs 2^31 nodes or more: ValueError.
+        sparse=True: the volume is a gsr_mesh.SparseTSDFVolume, which stores the blocks of 8 x 8 x 8 nodes near the surface only, as
+        upstream's ScalableTSDFVolume does: every view is touched, the blocks are allocated once, every view is fused, and the surface
+        is the dense volume's (its vertices and faces come in pool order).  Its limits are 2^31 - 1 blocks in the box and 2^22 - 1
+        allocated blocks; beyond them: ValueError."""
         if not self.depthmaps:
             raise ValueError("GaussianExtractor.extract_mesh_bounded: call reconstruction() first")
         if bounds is None:
@@ -89,16 +93,28 @@ class GaussianExtractor:
             raise ValueError(f"extract_mesh_bounded: voxel_size must be positive (got {voxel_size})")
         dims = [max(2, int(math.ceil((h - l) / voxel_size)) + 1) for l, h in zip(lo, hi)]
         nodes = dims[0] * dims[1] * dims[2]
+        views = list(zip(self.viewpoint_stack, self.depthmaps, self.rgbmaps, self.alphamaps))
+        mask = dict(alpha_min=0.5, sdf_trunc=sdf_trunc, depth_trunc=depth_trunc)
+        if sparse:
+            gx, gy, gz = gsr_mesh.sparse_blocks(dims)
+            if gx * gy * gz > gsr_mesh.MAX_BLOCKS:
+                raise ValueError(f"extract_mesh_bounded: a volume of {dims[0]} x {dims[1]} x {dims[2]} nodes has {gx * gy * gz} blocks of 8 x 8 x 8 "
+                                 "nodes, beyond the 2^31 - 1 of a sparse volume; pass a larger voxel_size or smaller bounds")
+            volume = gsr_mesh.SparseTSDFVolume(lo, voxel_size, dims, self.depthmaps[0].device, color=True)
+            for cam, depth, rgb, alpha in views:
+                volume.touch(depth, cam, alpha=alpha if mask_backgrond else None, **mask)
+            volume.allocate()            # (a ValueError beyond 2^22 - 1 allocated blocks)
+            for cam, depth, rgb, alpha in views:
+                volume.integrate(depth, cam, rgb=rgb, alpha=alpha if mask_backgrond else None, **mask)
+            return volume.extract()
         if nodes > gsr_mesh.MAX_NODES:
             # the edge count per axis scales with 1 / voxel_size: the smallest voxel whose node count fits, with a little room for the ceil
             fit = voxel_size * (nodes / gsr_mesh.MAX_NODES) ** (1.0 / 3.0) * 1.01
             raise ValueError(f"extract_mesh_bounded: a volume of {dims[0]} x {dims[1]} x {dims[2]} = {nodes} nodes is beyond the 2^31 - 1 of a "
-                             f"dense volume; voxel_size >= {fit:.6g} fits these bounds (or pass smaller bounds)")
-        device = self.depthmaps[0].device
-        volume = gsr_mesh.TSDFVolume(lo, voxel_size, dims, device, color=True)
-        for cam, depth, rgb, alpha in zip(self.viewpoint_stack, self.depthmaps, self.rgbmaps, self.alphamaps):
-            volume.integrate(depth, cam, rgb=rgb, alpha=alpha if mask_backgrond else None, alpha_min=0.5, sdf_trunc=sdf_trunc,
-                             depth_trunc=depth_trunc)
+                             f"dense volume; voxel_size >= {fit:.6g} fits these bounds (or pass smaller bounds, or sparse=True)")
+        volume = gsr_mesh.TSDFVolume(lo, voxel_size, dims, self.depthmaps[0].device, color=True)
+        for cam, depth, rgb, alpha in views:
+            volume.integrate(depth, cam, rgb=rgb, alpha=alpha if mask_backgrond else None, **mask)
         return volume.extract()
 
     def contracted_extent(self, centre, radius):
